@@ -19,9 +19,14 @@ Workloads (BASELINE.json ``configs``):
   into row bands (strong scaling, point-to-point halo tile rows); every other workload is weak scaling, no collective.
 
 Prints ONE JSON line (rank 0).  Extra objects: ``roofline`` (dominant kernel, HIP-event timed on the library's stream
-during the timed steps), ``rooflines`` / ``kernels`` (all kernel classes), ``cpu_baseline`` (the CPU oracle timed on this
-box's host cores on a bounded sample; rank 0, N = 1 only) and -- in the default run at N = 1 -- ``config3``, ``config4``,
-``config5``: the other single-GPU BASELINE configs measured with the same protocol, each with its own ``roofline``.
+during the timed steps), ``rooflines`` / ``kernels`` (all kernel classes).  A plain run does only that: set up, W warm-up steps,
+K timed steps, the line.  ``--full`` adds everything else at N = 1: ``cpu_baseline`` (the CPU oracle timed on this box's host
+cores on a bounded sample), the PCIe-inclusive / single-tile / operand-split side measurements, ``config3``, ``config4``,
+``config5`` (the other single-GPU BASELINE configs measured with the same protocol, each with its own ``roofline``), the other
+backbones and a generic model shape -- and, for the vr workload, the separate pass of the timed steps that records kernel events.
+
+``--dump-outputs DIR`` writes what the timed path returned in its last timed step as ``DIR/<name>.npy`` (see ``dump_outputs``);
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -209,6 +214,39 @@ def emit(line, detail, detail_path):
     print(s, flush=True)
 
 
+DUMP_BUDGET = 48 << 20       # bytes --dump-outputs writes at most (values and sample positions together)
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BUDGET, seed=0):
+    """Write each output as ``out_dir/<name>.npy``: float32 (float64 for float64 and integer outputs, which it holds exactly),
+    flattened.  When all of them in full would exceed ``budget`` bytes, every array gets the same share of its elements (at least
+    1024, or all of them), at positions drawn by a generator seeded with ``seed`` and the array's length -- the same positions run
+    after run for the same arguments -- and the sorted flat positions go beside it as ``<name>.index.npy`` (float64).  Returns
+    {name: elements written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {}
+    for name, t in outputs.items():
+        t = t.detach().reshape(-1)
+        flat[name] = (t, torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64)
+    size = lambda dt: 4 if dt == torch.float32 else 8
+    whole = sum(t.numel() * size(dt) for t, dt in flat.values())
+    frac = 1.0 if whole <= budget else budget / sum(t.numel() * (size(dt) + 8) for t, dt in flat.values())
+    written = {}
+    for name, (t, dt) in flat.items():
+        n = t.numel()
+        k = n if frac >= 1.0 else min(n, max(int(n * frac), 1024))
+        index_path = os.path.join(out_dir, name + ".index.npy")
+        if k < n:
+            idx = np.sort(np.random.default_rng([seed, n]).choice(n, size=k, replace=False))
+            np.save(index_path, idx.astype(np.float64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        elif os.path.exists(index_path):                 # (left by an earlier, sampled dump into the same directory)
+            os.remove(index_path)
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(dt).cpu().numpy())
+        written[name] = k
+    return written
+
+
 # ---- launching ------------------------------------------------------------------------------------------------------------
 def visible_gpu_count(env=None, sysfs="/sys/class/kfd/kfd/topology/nodes", dev_dir="/dev/dri"):
     """GPUs this process could open, counted WITHOUT touching the HIP runtime (the parent of a multi-rank run must not
@@ -365,7 +403,10 @@ class Bench:
         def check():
             assert int(self.nn_dev.item()) == nodes
 
-        return {"kind": "tiles", "step": step, "check": check, "nodes_per_step": nodes, "contexts": [ctx], "options": opts,
+        def outputs():
+            return {"classification": out[0], "confidence": out[1], "correction": out[2], "n_nodes": self.nn_dev}
+
+        return {"kind": "tiles", "step": step, "check": check, "outputs": outputs, "nodes_per_step": nodes, "contexts": [ctx], "options": opts,
                 "deg": DEG[conn], "conn": conn, "bf16": bf16, "split": matrix_path if matrix_path in ("bf16x3", "fp16x3") else None,
                 "unfused": unfused, "B": B, "S": S, "eng": eng, "gb": gb, "host": (depth, mask), "dev_in": (d_t, m_t),
                 "events_in_timed_region": True, "scaling": "weak", "gnn_type": gnn_type,
@@ -409,7 +450,11 @@ class Bench:
             for c in extra:
                 c.close()
 
-        return {"kind": "vr", "step": step, "check": lambda: None, "close": close, "nodes_per_step": nodes,
+        def outputs():          # the batches' [3, cells] results, in stream order
+            return {name: torch.cat([b[5][i] for b in dev_batches])
+                    for i, name in enumerate(("classification", "confidence", "correction"))}
+
+        return {"kind": "vr", "step": step, "check": lambda: None, "outputs": outputs, "close": close, "nodes_per_step": nodes,
                 "contexts": [e.ctx for e in engines], "options": {}, "deg": 8, "conn": "8-connected", "bf16": False, "split": None,
                 "unfused": False, "n_grids": len(grids), "batches": len(batches), "budget": budget, "streams": streams,
                 "events_in_timed_region": False, "scaling": "weak",
@@ -510,7 +555,14 @@ class Bench:
                     return None
             return hashlib.sha256(np.ascontiguousarray(host).tobytes()).hexdigest()
 
-        return {"kind": "survey", "step": step, "check": lambda: None, "nodes_per_step": n_proc * tile * tile, "sha256": stitched_sha256,
+        def outputs():          # the stitched [4, H, W] result (of a sharded run: this rank's band)
+            if "out" not in state:
+                return {}
+            o = state["out"] if shard is None else state["out"][2]
+            return {name: o[i] for i, name in enumerate(("classification", "confidence", "correction", "cleaned_depth"))}
+
+        return {"kind": "survey", "step": step, "check": lambda: None, "outputs": outputs, "nodes_per_step": n_proc * tile * tile,
+                "sha256": stitched_sha256,
                 "contexts": [pipe._engine.ctx], "options": {}, "deg": 8, "conn": "8-connected", "bf16": False, "split": None,
                 "unfused": False, "size": S, "tiles_total": ntr * ntc, "tiles_processed": n_proc, "tiles_skipped": n_skip,
                 "halo_bytes_all_ranks": halo, "events_in_timed_region": True, "scaling": "strong" if world > 1 else "weak",
@@ -552,11 +604,11 @@ class Bench:
                           "five host result grids out, H2D / D2H inside the clock; second of two calls"}
 
     # -- one timing protocol for all of them ------------------------------------------------------------------------------------
-    def measure(self, wl, steps, warmup):
+    def measure(self, wl, steps, warmup, kernel_pass=True):
         """W untimed steps, barrier + synchronize, K timed steps, barrier + synchronize; MAX over ranks.  HIP events around
         every kernel class are recorded inside the timed region -- except for the vr workload, which issues ~700 small launches
         per step: there the event pairs (1 400 records a step) are host work that slows the stream itself down, so its timed
-        steps run bare and the same K steps are repeated with events for the kernel breakdown."""
+        steps run bare and, with ``kernel_pass``, the same K steps are repeated with events for the kernel breakdown."""
         rt = self.rt
         ctxs = wl["contexts"]
         old = [{k: c.get_option(k) for k in wl["options"]} for c in ctxs]
@@ -575,7 +627,7 @@ class Bench:
                 wl["step"]()
             self.barrier()
             elapsed = time.perf_counter() - t0
-            if not wl["events_in_timed_region"]:
+            if not wl["events_in_timed_region"] and kernel_pass:
                 for c in ctxs:
                     c.profile(rt.K_NAMES)
                 for _ in range(steps):
@@ -600,7 +652,8 @@ class Bench:
             n = torch.tensor([wl["nodes_per_step"]], dtype=torch.int64, device=rdev)
             self.dist.all_reduce(n, op=self.dist.ReduceOp.SUM)
             nodes_all = int(n.item())
-        return {"elapsed": elapsed, "prof": prof, "steps": steps, "warmup": warmup, "nodes_all_ranks_per_step": nodes_all}
+        return {"elapsed": elapsed, "prof": prof, "steps": steps, "warmup": warmup, "nodes_all_ranks_per_step": nodes_all,
+                "kernel_pass": kernel_pass}
 
     def report(self, wl, m):
         """value / ms_per_step / rooflines / kernels of one measured workload (rank 0's kernel events)."""
@@ -702,7 +755,9 @@ class Bench:
                 "roofline": {k: dominant.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_frac",
                                                            "kernel", "avg_launch_ms")},
                 "rooflines": roofs, "kernels": kernels,
-                "kernel_events": "inside the timed region" if wl["events_in_timed_region"] else "separate pass of the same steps (timed steps ran bare)"}
+                "kernel_events": ("inside the timed region" if wl["events_in_timed_region"] else
+                                  "separate pass of the same steps (timed steps ran bare)" if m["kernel_pass"] else
+                                  "not recorded (timed steps ran bare; the separate pass runs under --full)")}
 
 
 def dtype_name(wl):
@@ -725,11 +780,17 @@ def main():
     ap.add_argument("--hidden", type=int, default=64, help="gnn_hidden_channels (config/config.py:43): 64 is the fused kernels' shape; "
                     "32 / 128 run the generic GEMM + aggregate kernels, anything else zero-padded to the next of those")
     ap.add_argument("--heads", type=int, default=4, help="gnn_heads (config/config.py:45): 1 / 2 / 4 fused (hidden 64), otherwise generic kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the timed steps (N = 1): the CPU baseline, the PCIe-inclusive / single-tile / split-path "
+                         "side measurements, config3 / config4 / config5, the other backbones and the generic shape, and the vr "
+                         "workload's separate kernel-event pass.  Off: the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64, at most 48 MiB in all: larger outputs as a fixed seeded sample, positions in DIR/<name>.index.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed steps (no config3 / config4 / config5 / PCIe-inclusive / split-path / single-tile side "
-                         "measurements, no CPU baseline): what the rocprofv3 passes run, so that a kernel's average duration in the "
-                         "trace is the full-batch one")
+                    help="with --full: only the timed steps and the vr workload's kernel-event pass (no config3 / config4 / config5 / "
+                         "PCIe-inclusive / split-path / single-tile side measurements, no CPU baseline)")
     ap.add_argument("--split-f16", action="store_true",
                     help="opt-in matrix path: float16 hi/lo operand split (fp16x3), float32 accumulation (|activations| < 65504)")
     ap.add_argument("--split-bf16", action="store_true",
@@ -764,6 +825,8 @@ def main():
                          "in full); stdout carries ONE compact line")
     ap.add_argument("--extras-survey-size", type=int, default=20000, help="side of the config5 survey measured beside the default headline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # N > 1 without a launcher: start the N ranks here, BEFORE anything touches the GPU (the device count comes from the KFD
     # topology in sysfs, not from the HIP runtime), wait for them and leave with their status.
@@ -797,8 +860,13 @@ def main():
         wl = bench.vr(args.vr_grids, args.vr_budget, args.vr_streams)
     else:
         wl = bench.survey(args.survey_size)
-    m = bench.measure(wl, args.steps, args.warmup)
+    m = bench.measure(wl, args.steps, args.warmup, kernel_pass=args.full)
     sha = wl["sha256"]() if (args.checksum and "sha256" in wl) else None          # (every rank: the band gather is point-to-point)
+
+    if rank == 0 and args.dump_outputs:
+        written = dump_outputs(wl["outputs"](), args.dump_outputs)
+        print(f"bench.py: outputs of the last timed step in {args.dump_outputs}: "
+              + ", ".join(f"{k} ({v} elements)" for k, v in written.items()), file=sys.stderr, flush=True)
 
     if rank == 0:
         rep = bench.report(wl, m)
@@ -831,7 +899,7 @@ def main():
             line["rehearsal"] = True
             line["rehearsal_note"] = (f"{world} ranks share ONE GPU and talk over gloo (host-staged halo rows): a functional rehearsal of "
                                       "the multi-rank code path, NOT a scaling measurement -- `value` earns no credit")
-        extras = not args.no_extras and world == 1
+        extras = args.full and not args.no_extras and world == 1
         plain = wl.get("gnn_type", "GAT") != "GAT"
         default_headline = wl["kind"] == "tiles" and not wl["unfused"] and not wl["bf16"] and not wl["split"] and not plain
         if plain:
@@ -849,7 +917,7 @@ def main():
                 torch.cuda.empty_cache()
                 return None
 
-        # The CPU baseline first: it is part of the contract and needs nothing of the GPU.
+        # --full: the CPU baseline first (it needs nothing of the GPU), then the side measurements.
         if extras and not args.no_cpu_baseline and wl["kind"] == "tiles" and not plain:
             def _cpu():
                 cb = cpu_baseline(args.cpu_runs, S, bench.model(7)[1], 100, wl["conn"])

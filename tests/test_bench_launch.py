@@ -191,3 +191,55 @@ def test_pmc_traffic_is_refused_for_other_kernels(tmp_path, monkeypatch):
     assert bench.pmc_traffic_table("other") == {} and bench.pmc_traffic_table(None) == {}
     (prof / "pmc_traffic.json").write_text(json.dumps({"gat_layer_fused_kernel": {"hbm_bytes_per_launch": 1.0}}))      # unstamped (rounds 1-3)
     assert bench.pmc_traffic_table("abc") == {}
+
+
+# ---- --full / --dump-outputs -----------------------------------------------------------------------------------------------
+def test_full_and_dump_outputs_options_exist_and_full_is_off_by_default():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr and not r.stdout.strip()
+
+
+def test_dump_outputs_writes_float_arrays_whole_when_small(tmp_path):
+    import numpy as np
+    import torch
+    outs = {"cls": torch.arange(10, dtype=torch.float32), "half": torch.ones(4, 3, dtype=torch.float16),
+            "n_nodes": torch.tensor([7], dtype=torch.int64), "d": torch.tensor([0.1], dtype=torch.float64)}
+    written = bench.dump_outputs(outs, str(tmp_path / "o"))
+    assert written == {"cls": 10, "half": 12, "n_nodes": 1, "d": 1}
+    assert sorted(p.name for p in (tmp_path / "o").iterdir()) == ["cls.npy", "d.npy", "half.npy", "n_nodes.npy"]
+    a = {n: np.load(tmp_path / "o" / f"{n}.npy") for n in outs}
+    assert a["cls"].dtype == np.float32 and np.array_equal(a["cls"], np.arange(10, dtype=np.float32))
+    assert a["half"].dtype == np.float32 and a["half"].shape == (12,)
+    assert a["n_nodes"].dtype == np.float64 and a["n_nodes"][0] == 7.0
+    assert a["d"].dtype == np.float64 and a["d"][0] == 0.1
+
+
+def test_dump_outputs_samples_large_outputs_within_budget_at_fixed_positions(tmp_path):
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    outs = {"a": torch.randn(3, 40000, generator=g), "b": torch.randn(50000, generator=g, dtype=torch.float64),
+            "n": torch.tensor([5], dtype=torch.int64)}
+    budget = 200_000
+    w1 = bench.dump_outputs(outs, str(tmp_path / "x"), budget=budget)
+    w2 = bench.dump_outputs(outs, str(tmp_path / "y"), budget=budget)
+    assert w1 == w2 and w1["n"] == 1 and 1024 <= w1["a"] < 120000 and 1024 <= w1["b"] < 50000
+    files = sorted(p.name for p in (tmp_path / "x").iterdir())
+    assert files == ["a.index.npy", "a.npy", "b.index.npy", "b.npy", "n.npy"]
+    assert sum(np.load(tmp_path / "x" / f).nbytes for f in files) <= budget
+    for name in ("a", "b"):
+        idx = np.load(tmp_path / "x" / f"{name}.index.npy")
+        val = np.load(tmp_path / "x" / f"{name}.npy")
+        assert idx.dtype == np.float64 and len(idx) == len(val) == w1[name]
+        assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < outs[name].numel()
+        assert np.array_equal(val, outs[name].reshape(-1).numpy()[idx.astype(np.int64)].astype(val.dtype))
+        assert np.array_equal(idx, np.load(tmp_path / "y" / f"{name}.index.npy"))
+        assert np.array_equal(val, np.load(tmp_path / "y" / f"{name}.npy"))
+    # a later whole dump into the same directory leaves no stale positions behind
+    bench.dump_outputs({"a": outs["a"][:, :10]}, str(tmp_path / "x"))
+    assert not (tmp_path / "x" / "a.index.npy").exists() and np.load(tmp_path / "x" / "a.npy").shape == (30,)

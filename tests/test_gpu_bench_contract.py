@@ -1,7 +1,8 @@
 """bench.py's ONE JSON line on a GPU, at small sizes: the driver's contract keys and a roofline whose fraction stays within (0, 1] --
-for the tile, configs[2], VR and survey workloads (each as its own child process, as the driver runs it), and the DEFAULT command
+for the tile, configs[2], VR and survey workloads (each as its own child process, as the driver runs it), and the `--full` command
 shape (extras on: cpu_baseline, config3 / config4 / config5 at small sizes): exactly one stdout line, under 4 KB, that starts with
-`{` -- round 3's default line was 23 KB and the driver's tail of stdout lost its head."""
+`{` -- round 3's default line was 23 KB and the driver's tail of stdout lost its head.  Since the side measurements moved
+behind `--full`, the tests that need them pass it; a plain run (no `--full`) is checked to carry none of them."""
 import json
 import os
 import subprocess
@@ -27,7 +28,7 @@ def _line(args):
 @pytest.mark.parametrize("args", [
     ["--tiles", "8", "--steps", "2", "--warmup", "1", "--no-extras"],
     ["--workload", "c3", "--tiles", "8", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"],
-    ["--workload", "vr", "--vr-grids", "300", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"],
+    ["--workload", "vr", "--vr-grids", "300", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"],
     ["--workload", "survey", "--survey-size", "2048", "--steps", "1", "--warmup", "0", "--no-extras", "--no-cpu-baseline"],
     ["--gnn-type", "GCN", "--tiles", "8", "--steps", "2", "--warmup", "1", "--no-extras"],
     ["--gnn-type", "GraphSAGE", "--tiles", "8", "--steps", "2", "--warmup", "1", "--no-extras"],
@@ -46,10 +47,10 @@ def test_bench_line_contract(args, gpu_device):
 
 
 def test_default_command_shape_prints_one_small_line(gpu_device, tmp_path):
-    """What the driver runs (`python bench.py --gpus 1 --steps K --warmup W`: every extra on), at small sizes."""
+    """`python bench.py --gpus 1 --steps K --warmup W --full` (every extra on), at small sizes."""
     side = tmp_path / "detail.json"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiles", "8",
-                        "--vr-grids", "300", "--extras-survey-size", "2048", "--cpu-runs", "1", "--detail", str(side)],
+                        "--vr-grids", "300", "--extras-survey-size", "2048", "--cpu-runs", "1", "--detail", str(side), "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     out_lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -108,3 +109,31 @@ def test_tile_workload_two_rank_rehearsal_counts_both_ranks(gpu_device):
     assert two["config"]["nodes_per_step_per_gpu"] == per_rank and "x2" in two["config"]["parallelism"]
     assert abs(one["value"] * one["ms_per_step"] * 1e-3 - per_rank) < 1e-6 * per_rank
     assert abs(two["value"] * two["ms_per_step"] * 1e-3 - 2 * per_rank) < 1e-6 * per_rank
+
+
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(gpu_device, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without `--full`: K timed steps and the line, no side measurement; with
+    `--dump-outputs DIR` the last timed step's [3, cells] result (as three float32 rows) and its node count (float64) -- the same
+    on a second run (seeded inputs, deterministic kernels), which is what lets two builds be compared output for output."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        j = _line(["--gpus", "1", "--steps", "3", "--warmup", "1", "--tiles", "8", "--detail", str(tmp_path / f"detail{i}.json"),
+                   "--dump-outputs", str(d)])
+        dumps.append({p.name[:-4]: np.load(p) for p in d.glob("*.npy")})
+        if i == 0:
+            line = j
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    for k in ("cpu_baseline", "gpu_over_cpu", "pcie_inclusive", "single_tile", "opt_in_split", "config3", "config4", "config5",
+              "generic_shape", "gnn_types"):
+        assert k not in line, k
+    a = dumps[0]
+    assert set(a) == {"classification", "confidence", "correction", "n_nodes"}
+    cells = 8 * 256 * 256
+    for k in ("classification", "confidence", "correction"):
+        assert a[k].dtype == np.float32 and a[k].shape == (cells,) and np.isfinite(a[k]).all()
+    assert a["n_nodes"].dtype == np.float64 and a["n_nodes"][0] == line["config"]["nodes_per_step_per_gpu"]
+    assert a["confidence"].max() > 0
+    for k in a:
+        assert np.array_equal(a[k], dumps[1][k]), k

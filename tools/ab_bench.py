@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of two builds of the library on the same box: `bench.py --no-extras` per workload with BGNN_LIB pointing at each .so, the
+"""A/B of two builds of the library on the same box: `bench.py --full --no-extras` per workload with BGNN_LIB pointing at each .so, the
 per-kernel-class times (HIP events, ms per step) side by side.
 
 A variant may also be an environment switch of ONE build: name=path:VAR=value[:VAR2=value2].
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run(lib, workload, steps, extra):
     with tempfile.NamedTemporaryFile(suffix=".json", delete=False) as f:
         side = f.name
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras", "--steps", str(steps), "--warmup", "3", "--detail", side]
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras", "--steps", str(steps), "--warmup", "3", "--detail", side]
     if workload != "tiles":
         args += ["--workload", workload]
     args += extra

@@ -11,19 +11,19 @@ cd /tmp && export TMPDIR=/tmp
 # the kernels these profiles are collected on (bench.py refuses PMC traffic stamped with another id)
 python3 -c "import sys; sys.path.insert(0, '$R'); from bathymetric_gnn_amd import runtime; print(runtime.build_id())" > $O/build_id.txt
 if [ "$STAGE" = all ] || [ "$STAGE" = bench ]; then
-python3 $R/bench.py --detail $O/bench_fused.detail.json > $O/bench_fused.json 2> $O/bench_fused.stderr
-python3 $R/bench.py --unfused --no-cpu-baseline --detail $O/bench_unfused.detail.json > $O/bench_unfused.json 2> $O/bench_unfused.stderr
-python3 $R/bench.py --split-bf16 --no-cpu-baseline --detail $O/bench_split.detail.json > $O/bench_split.json 2> $O/bench_split.stderr
-python3 $R/bench.py --split-f16 --no-cpu-baseline --detail $O/bench_split_f16.detail.json > $O/bench_split_f16.json 2> $O/bench_split_f16.stderr
-python3 $R/bench.py --workload c3 --no-cpu-baseline --detail $O/bench_c3.detail.json > $O/bench_c3.json 2> $O/bench_c3.stderr
-python3 $R/bench.py --bf16 --no-cpu-baseline --detail $O/bench_bf16_k8.detail.json > $O/bench_bf16_k8.json 2> $O/bench_bf16_k8.stderr
-python3 $R/bench.py --workload vr --vr-budget 50000 --vr-streams 1 --detail $O/bench_vr_50k_1ctx.detail.json > $O/bench_vr_50k_1ctx.json 2> $O/bench_vr_50k_1ctx.stderr
-python3 $R/bench.py --workload vr --vr-budget 50000 --vr-streams 2 --detail $O/bench_vr_50k_2ctx.detail.json > $O/bench_vr_50k_2ctx.json 2> $O/bench_vr_50k_2ctx.stderr
-python3 $R/bench.py --workload vr --vr-budget 50000 --vr-streams 4 --detail $O/bench_vr_50k.detail.json > $O/bench_vr_50k.json 2> $O/bench_vr_50k.stderr
-python3 $R/bench.py --workload vr --vr-budget 1000000 --vr-streams 1 --detail $O/bench_vr_1M.detail.json > $O/bench_vr_1M.json 2> $O/bench_vr_1M.stderr
-python3 $R/bench.py --workload survey --survey-size 20000 --steps 2 --warmup 0 --detail $O/bench_survey_20000.detail.json > $O/bench_survey_20000.json 2> $O/bench_survey_20000.stderr
+python3 $R/bench.py --full --detail $O/bench_fused.detail.json > $O/bench_fused.json 2> $O/bench_fused.stderr
+python3 $R/bench.py --full --unfused --no-cpu-baseline --detail $O/bench_unfused.detail.json > $O/bench_unfused.json 2> $O/bench_unfused.stderr
+python3 $R/bench.py --full --split-bf16 --no-cpu-baseline --detail $O/bench_split.detail.json > $O/bench_split.json 2> $O/bench_split.stderr
+python3 $R/bench.py --full --split-f16 --no-cpu-baseline --detail $O/bench_split_f16.detail.json > $O/bench_split_f16.json 2> $O/bench_split_f16.stderr
+python3 $R/bench.py --full --workload c3 --no-cpu-baseline --detail $O/bench_c3.detail.json > $O/bench_c3.json 2> $O/bench_c3.stderr
+python3 $R/bench.py --full --bf16 --no-cpu-baseline --detail $O/bench_bf16_k8.detail.json > $O/bench_bf16_k8.json 2> $O/bench_bf16_k8.stderr
+python3 $R/bench.py --full --workload vr --vr-budget 50000 --vr-streams 1 --detail $O/bench_vr_50k_1ctx.detail.json > $O/bench_vr_50k_1ctx.json 2> $O/bench_vr_50k_1ctx.stderr
+python3 $R/bench.py --full --workload vr --vr-budget 50000 --vr-streams 2 --detail $O/bench_vr_50k_2ctx.detail.json > $O/bench_vr_50k_2ctx.json 2> $O/bench_vr_50k_2ctx.stderr
+python3 $R/bench.py --full --workload vr --vr-budget 50000 --vr-streams 4 --detail $O/bench_vr_50k.detail.json > $O/bench_vr_50k.json 2> $O/bench_vr_50k.stderr
+python3 $R/bench.py --full --workload vr --vr-budget 1000000 --vr-streams 1 --detail $O/bench_vr_1M.detail.json > $O/bench_vr_1M.json 2> $O/bench_vr_1M.stderr
+python3 $R/bench.py --full --workload survey --survey-size 20000 --steps 2 --warmup 0 --detail $O/bench_survey_20000.detail.json > $O/bench_survey_20000.json 2> $O/bench_survey_20000.stderr
 for t in GCN GraphSAGE GIN; do
-  python3 $R/bench.py --gnn-type $t --detail $O/bench_$t.detail.json > $O/bench_$t.json 2> $O/bench_$t.stderr
+  python3 $R/bench.py --full --gnn-type $t --detail $O/bench_$t.detail.json > $O/bench_$t.json 2> $O/bench_$t.stderr
 done
 echo "bench stage done"
 fi
