@@ -28,6 +28,11 @@ EF_ZERO = 3
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED = -1, -2, -3, -4
 ABI_VERSION = 6
 MATRIX_PATHS = {"exact_f32": 0, "bf16x3": 1, "fp16x3": 2, "bf16": 3}
+# every int option of a context (include/bgnn.h, bgnn_ctx_set_option; the "diag_*" / "gemm_diag" ones only take non-zero values in
+# the diagnostic build)
+OPTION_NAMES = ("matrix_path", "fused", "fold_extractor", "ragged_atlas", "features_tiled", "fused_front", "fused_persistent",
+                "bf16_two_phase", "bf16_layer0_af", "stats_narrow", "fused_lds_pad_kb", "diag_mask", "diag_stamps", "gemm_waves",
+                "gemm_diag", "gemm_no_wres", "gemm_pair_major")
 
 
 GNN_TYPES = {"GAT": 0, "GCN": 1, "GraphSAGE": 2, "GIN": 3}      # BGNN_GNN_*
@@ -214,6 +219,13 @@ class Context:
         v = C.c_int()
         check(self.lib.bgnn_ctx_get_option(self.handle, name.encode(), C.byref(v)))
         return v.value
+
+    def copy_options_from(self, other: "Context"):
+        """Give this context every run-time switch of ``other`` (OPTION_NAMES)."""
+        for k in OPTION_NAMES:
+            v = other.get_option(k)
+            if self.get_option(k) != v:
+                self.set_option(k, v)
 
     def options(self, **kw):
         """``with ctx.options(matrix_path="bf16x3"): ...`` -- set, run, restore."""

@@ -265,15 +265,21 @@ class NativeVRProcessor:
 
     def _engine_at(self, i: int) -> TileBatchEngine:
         """The processor's i-th engine (0: the device's default library context; 1: a second context -- own HIP stream, own arenas --
-        created when batches are first pipelined, with the first one's run-time switches)."""
+        created when batches are first pipelined; ``_sync_options`` keeps its run-time switches equal to the first one's)."""
         from .. import runtime as rt
         while len(self._engines) <= i:
             ctx = rt.new_context(self._engine.ctx.device)
-            for k in ("matrix_path", "fused", "fold_extractor", "ragged_atlas", "fused_front", "features_tiled"):
-                ctx.set_option(k, self._engine.ctx.get_option(k))
+            ctx.copy_options_from(self._engine.ctx)
             self._engines.append(TileBatchEngine(self.model, self.graph_builder, self._engine.ctx.device, self.auto_correct_threshold,
                                                  self._engine.review_threshold, self._engine.norm_floor, ctx=ctx))
         return self._engines[i]
+
+    def _sync_options(self):
+        """Every run-time switch of the first engine's context (matrix_path, bf16_layer0_af, bf16_two_phase, ...) onto the other
+        engines' contexts: batches / chunks alternate between the contexts, so a switch set on the first one after the second was
+        made would otherwise give odd and even batches different rounding sequences.  Called at every submission."""
+        for eng in self._engines[1:]:
+            eng.ctx.copy_options_from(self._engine.ctx)
 
     def _second_engine(self) -> TileBatchEngine:
         return self._engine_at(1)
@@ -354,6 +360,7 @@ class NativeVRProcessor:
             return None
         if len(self._inflight) >= self.MAX_IN_FLIGHT:
             raise RuntimeError(f"{self.MAX_IN_FLIGHT} batches are already in flight: collect_batch() the oldest first")
+        self._sync_options()
         self._inflight.append(self._launch(self._engine_for_next()))
         return len(self._inflight)
 
@@ -421,6 +428,7 @@ class NativeVRProcessor:
         import ctypes as C
         from .. import runtime as rt
         thr = self.auto_correct_threshold if auto_correct_threshold is None else auto_correct_threshold
+        self._sync_options()
         tab = handler.refinement_table()
         n_grids = len(tab["cells"])
         stats = {"grids_processed": 0, "cells_processed": 0, "cells_classified_noise": 0, "cells_corrected": 0,

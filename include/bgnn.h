@@ -64,9 +64,17 @@ void *bgnn_ctx_stream(bgnn_ctx *ctx);
  * created (the variable in brackets); afterwards only this call changes them:
  *   "matrix_path"     0 exact f32 (default), 1 bf16x3, 2 fp16x3: opt-in operand-split MFMA paths [BGNN_SPLIT_BF16 / BGNN_SPLIT_F16]
  *                     (hi + lo parts of both operands, three 16-bit MFMAs, float32 accumulate; fp16x3 keeps its weight images scaled
- *                     into float16's normal range and lands as close to a float64 forward as the exact path, while |activations| < 65504);
+ *                     by one power of two into float16's normal range, while |activations| < 65504).  Distance to a float64 forward:
+ *                     fp16x3 (22-bit operands) within 4 x float32 arithmetic's own distance at every depth -- as close as the exact
+ *                     path near -20 m, up to 2.1 x the exact path's distance at -200 .. -10000 m with trained-like BatchNorm
+ *                     statistics or an outlier weight (per-column scales not built); bf16x3 (16-bit operands) within
+ *                     5e-5 + 2^8 x float32's distance (measured 17 .. 68 x; tests/test_gpu_conditioning.py);
  *                     3 bf16: layer activations stored as bf16 in HBM and multiplied on the bf16 MFMA, float32 softmax /
- *                     aggregation / accumulation (BASELINE config 3 "bf16 node features"; no 1e-4 contract) [BGNN_BF16]
+ *                     aggregation / accumulation (BASELINE config 3 "bf16 node features"; no 1e-4 contract) [BGNN_BF16].
+ *                     DEPTH LIMIT: layer 0's input h1 is stored un-normalised, so its depth-driven common mode eats bf16's 8
+ *                     significant bits.  The bound of tests/test_gpu_forward.py holds near -20 m with BatchNorm statistics that do
+ *                     not track that common mode; with statistics fitted across -20 .. -10000 m (a model trained on many surveys) it
+ *                     fails at every band (max |dlogit| 1.1 .. 36 against 0.3 .. 1.0; tests/test_gpu_conditioning.py, strict xfails)
  *   "fused"           1 (default): K4 fused with the next K3 / K5 + K6; 0: separate kernels           [BGNN_NO_FUSED]
  *   "fold_extractor"  1 (default): extractor layer 2 folded into lin of GAT layer 0; 0: unfolded chain [BGNN_NO_FOLD]
  *   "fused_front"     1 (default): feature extractor layer 1 runs inside the lin_0 GEMM where that GEMM takes its W-resident form

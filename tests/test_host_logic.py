@@ -175,3 +175,61 @@ def test_model_shapes_that_stay_refused_say_so_in_the_constructor():
             BathymetricGNN(in_channels=7, **kw)
     BathymetricGNN(in_channels=7, hidden_channels=80, heads=4)                            # 4 heads of 128: fits
     BathymetricGNN(in_channels=7, hidden_channels=100, heads=9, gnn_type="GCN")           # heads does not shape a plain backbone
+
+
+def test_pipelined_engines_share_every_context_option(monkeypatch):
+    """NativeVRProcessor alternates batches / chunks between two library contexts.  The second one must carry EVERY int option of
+    the first -- also one switched after the second context was made (bf16_layer0_af, bf16_two_phase: other rounding sequences) --
+    at every submit_batch and process_refinements; otherwise odd and even batches of one run would round differently."""
+    from types import SimpleNamespace
+    from bathymetric_gnn_amd import runtime as rt
+    from bathymetric_gnn_amd.scripts import inference_native as inf
+
+    class FakeCtx(rt.Context):                              # option bookkeeping only: no library, no device
+        def __init__(self, device=None):
+            self.device = device
+            self.opts = {k: 0 for k in rt.OPTION_NAMES}
+            self.opts.update(fused=1, fold_extractor=1, ragged_atlas=1, features_tiled=1, fused_front=1, bf16_two_phase=1,
+                             bf16_layer0_af=1, stats_narrow=-1, gemm_waves=8, gemm_pair_major=1)
+
+        def get_option(self, name):
+            return self.opts[name]
+
+        def set_option(self, name, value):
+            assert name in self.opts, name
+            self.opts[name] = rt.MATRIX_PATHS[value] if isinstance(value, str) else int(value)
+
+    monkeypatch.setattr(rt, "new_context", lambda device=None: FakeCtx(device))
+    monkeypatch.setattr(inf, "TileBatchEngine", lambda *a, ctx=None, **kw: SimpleNamespace(ctx=ctx))
+    p = object.__new__(inf.NativeVRProcessor)
+    p.model, p.graph_builder, p.auto_correct_threshold = None, None, 0.85
+    p._engine = SimpleNamespace(ctx=FakeCtx("dev"), review_threshold=0.6, norm_floor=0.01)
+    p._engines, p._inflight, p._next_engine = [p._engine], [], 0
+    primary = p._engine.ctx
+    primary.set_option("matrix_path", "bf16"); primary.set_option("gemm_waves", 4)
+    second = p._engine_at(1).ctx
+    assert second is not primary and second.opts == primary.opts             # made with every option, not a selection
+    seen = []
+
+    def launch(eng):
+        seen.append((eng.ctx, dict(eng.ctx.opts)))
+        return SimpleNamespace()
+    p._launch = launch
+    p._fill = SimpleNamespace(n=5)
+    for name, value in (("bf16_layer0_af", 0), ("bf16_two_phase", 0), ("stats_narrow", 1), ("matrix_path", "exact_f32")):
+        primary.set_option(name, value)
+        p._inflight.clear()
+        p.submit_batch(); p.submit_batch()                                   # one batch on each context
+        assert [c for c, _ in seen[-2:]] == [primary, second]
+        assert seen[-1][1] == seen[-2][1] == primary.opts, name
+    # process_refinements re-syncs before it touches its chunks
+    primary.set_option("bf16_layer0_af", 1); primary.set_option("fused", 0)
+
+    class Stop(Exception):
+        pass
+
+    def table():
+        raise Stop
+    with pytest.raises(Stop):
+        p.process_refinements(SimpleNamespace(refinement_table=table))
+    assert second.opts == primary.opts
