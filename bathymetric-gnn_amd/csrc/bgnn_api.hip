@@ -193,16 +193,12 @@ int bgnn_ctx_create(int device, void *stream, bgnn_ctx **out) {
     o.fold_extractor = getenv("BGNN_NO_FOLD") ? 0 : 1;
     o.ragged_atlas = getenv("BGNN_NO_ATLAS") ? 0 : 1;
     o.fused_front = getenv("BGNN_NO_FUSED_FRONT") ? 0 : 1;
-    o.fused_persistent = getenv("BGNN_PERSISTENT") ? 1 : 0;
     o.bf16_two_phase = getenv("BGNN_NO_TWO_PHASE") ? 0 : env_int("BGNN_TWO_PHASE", 1);
     o.bf16_layer0_af = getenv("BGNN_NO_LAYER0_AF") ? 0 : 1;
     o.stats_narrow = env_int("BGNN_STATS_NARROW", -1);
-    o.fused_lds_pad_kb = env_int("BGNN_FUSED_LDS_PAD", 0);
     o.diag_mask = env_int("BGNN_FUSED_DBG", 0);
     o.diag_stamps = getenv("BGNN_FUSED_STAMPS") ? 1 : 0;
-    o.gemm_waves = env_int("BGNN_GEMM_WAVES", 8);
     o.gemm_diag = env_int("BGNN_GEMM_DBG", 0);
-    o.gemm_no_wres = getenv("BGNN_NO_WRES") ? 1 : 0;
     o.gemm_pair_major = getenv("BGNN_NO_PAIR_MAJOR") ? 0 : 1;
   }
   *out = c;
@@ -212,10 +208,8 @@ int bgnn_ctx_create(int device, void *stream, bgnn_ctx **out) {
 static int *option_slot(bgnn_ctx *ctx, const char *name) {
   BgnnOpts &o = ctx->opts;
   struct { const char *n; int *p; } tab[] = {
-      {"matrix_path", &o.matrix_path}, {"fused", &o.fused}, {"fold_extractor", &o.fold_extractor}, {"ragged_atlas", &o.ragged_atlas}, {"features_tiled", &o.features_tiled}, {"fused_front", &o.fused_front}, {"fused_persistent", &o.fused_persistent}, {"bf16_two_phase", &o.bf16_two_phase}, {"bf16_layer0_af", &o.bf16_layer0_af}, {"stats_narrow", &o.stats_narrow},
-      {"fused_lds_pad_kb", &o.fused_lds_pad_kb},
-      {"diag_mask", &o.diag_mask}, {"diag_stamps", &o.diag_stamps}, {"gemm_waves", &o.gemm_waves},
-      {"gemm_diag", &o.gemm_diag}, {"gemm_no_wres", &o.gemm_no_wres}, {"gemm_pair_major", &o.gemm_pair_major}};
+      {"matrix_path", &o.matrix_path}, {"fused", &o.fused}, {"fold_extractor", &o.fold_extractor}, {"ragged_atlas", &o.ragged_atlas}, {"features_tiled", &o.features_tiled}, {"fused_front", &o.fused_front}, {"bf16_two_phase", &o.bf16_two_phase}, {"bf16_layer0_af", &o.bf16_layer0_af}, {"stats_narrow", &o.stats_narrow},
+      {"diag_mask", &o.diag_mask}, {"diag_stamps", &o.diag_stamps}, {"gemm_diag", &o.gemm_diag}, {"gemm_pair_major", &o.gemm_pair_major}};
   for (auto &t : tab) if (strcmp(t.n, name) == 0) return t.p;
   return nullptr;
 }
@@ -240,8 +234,8 @@ int bgnn_ctx_get_option(bgnn_ctx *ctx, const char *name, int *value) {
 }
 
 // diagnostic (not part of the documented ABI): read and clear the fused kernel's phase counters
-// (out: 64 counters -- 0..15 the one-block-per-workgroup kernels together, 16..31 the persistent kernel, 32..47 the 256 -> 64
-//  instance, 48..63 the heads instance)
+// (out: 64 counters -- 0..15 the fused layer kernels together, 16..31 unused, 32..47 the 256 -> 64 instance, 48..63 the heads
+//  instance)
 int bgnn_debug_stamps(bgnn_ctx *ctx, unsigned long long *out32) {
   if (!ctx || !out32) return BGNN_ERR_INVALID;
   (void)hipStreamSynchronize(ctx->stream);

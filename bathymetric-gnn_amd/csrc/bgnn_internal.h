@@ -77,11 +77,8 @@ struct BgnnOpts {
   int matrix_path = 0;       // 0 exact f32, 1 bf16x3, 2 fp16x3 (opt-in operand-split matrix paths), 3 bf16 activation storage + bf16 MFMA
   int fused = 1;             // 0: K3 / K4 / K5 / K6 as separate kernels
   int fold_extractor = 1;    // 0: run the extractor's second Linear and lin of layer 0 unfolded
-  int fused_persistent = 0;  // 1 (opt-in experiment): big uniform batches run the 256 -> 256 exact-f32 fused layer in its persistent
-                             // one-workgroup-per-CU form (bit-identical; measured 11.4 ms per launch against 10.15: DESIGN.md)
   int bf16_two_phase = 1;    // matrix_path = bf16: the 256 -> 256 fused layer in its two-phase form (aggregate all slabs to bf16 registers, then
-                             // the GEMM in four column passes: three workgroups per CU; bit-identical to the one-phase instance, 0 selects that;
-                             // 2: the 256 -> 64 instance in the same form too -- experiment, neutral)
+                             // the GEMM in four column passes: three workgroups per CU; bit-identical to the one-phase instance, 0 selects that)
   int bf16_layer0_af = 1;    // matrix_path = bf16, default model shape: layer 0 aggregates the extractor's 64-channel h1 and applies the folded lin_0
                              // weight per head afterwards, inside the fused launch (no front GEMM, no 512-byte lin_0 rows in HBM); 0: front GEMM + the
                              // ordinary two-phase launch.  Same mathematics, another rounding sequence (not bit-identical to 0)
@@ -90,10 +87,9 @@ struct BgnnOpts {
   int fused_front = 1;       // 1: extractor layer 1 runs inside the lin_0 GEMM where that GEMM's W-resident form is used (0: own launch)
   int features_tiled = 1;    // 1: LDS-tiled feature kernel with mirrored-edge slope reuse (K = 8 / 16); 0: thread-per-cell form (bit-identical)
   int ragged_atlas = 1;      // ragged batches: fused layers walk a shelf-packed canvas of the grids (0: per-grid 8x16 blocks)
-  int fused_lds_pad_kb = 0;    // experiment: pad the fused kernel's LDS request (occupancy)
   int diag_mask = 0;         // BGNN_DIAG builds only: phase ablation bits of the fused kernel
   int diag_stamps = 0;       // BGNN_DIAG builds only: per-phase s_memtime sums
-  int gemm_waves = 8, gemm_diag = 0, gemm_no_wres = 0;
+  int gemm_diag = 0;
   int gemm_pair_major = 1;   // exact-f32 lin_0 GEMM with the extractor in front: tile-pair-major MFMA order, the epilogue of pair p (bias, attention
                              // dots, transposed row stores) issued between the MFMAs of pair p + 1 (0: tile-major, epilogue after; bit-identical)
 };

@@ -53,14 +53,8 @@ struct BlockPos {
 // XCD-aware block order: consecutive work items (adjacent cell blocks, which share halo rows) run on
 // the same XCD and hit its L2.  Bijective for any n_blocks.
 template <int TH = TILE_H>
-__device__ __forceinline__ BlockPos decode_block_at(const TileBlocks &tb, int bid);
-template <int TH = TILE_H>
-__device__ __forceinline__ BlockPos decode_block(const TileBlocks &tb) { return decode_block_at<TH>(tb, blockIdx.x); }
-// (explicit index: a persistent workgroup walks bid = blockIdx.x + i * gridDim.x; with a grid that is a multiple of 8 it stays on
-//  its XCD's contiguous range of work items and the workgroups of an XCD process adjacent items at the same time)
-template <int TH>
-__device__ __forceinline__ BlockPos decode_block_at(const TileBlocks &tb, int bid) {
-  const int nb = tb.n_blocks;
+__device__ __forceinline__ BlockPos decode_block(const TileBlocks &tb) {
+  const int bid = blockIdx.x, nb = tb.n_blocks;
   const int xcd = bid & 7, q = nb >> 3, r = nb & 7;
   const int wid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   BlockPos p;
@@ -247,7 +241,7 @@ __device__ __forceinline__ void attention_coefficients_head(int my, int self_idx
 //              (exp(e - max) / (sum + 1e-16)).
 // A lane that owns TWO heads (H = 4: heads hl and hl + 2) runs them as the two halves of packed f32 operations
 // (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32): the same IEEE operations in the same order per head, so the pair form and the
-// single-head form agree bit for bit (the persistent kernel and the heads instances use the single form; tests/test_gpu_forward.py).
+// single-head form agree bit for bit (the heads instances use the single form; tests/test_gpu_forward.py).
 // exp through v_exp_f32 (2^x), one v_rcp_f32 per head instead of K + 1 divisions and one for the mean's 1 / count: ~1 ulp each,
 // far inside the 1e-4 bar.  leaky_relu(x, 0.2) = max(x, 0.2 x) for every x (one multiply + one max).
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -259,26 +253,7 @@ struct EdgeTerms {
   float mean[3];         // the self loop's attributes
 };
 
-template <int K>
-__device__ __forceinline__ void edge_terms(const int (&nb)[K], const float (&eraw)[K * 3], EdgeTerms<K> &t) {
-  float sum[3] = {0.f, 0.f, 0.f};
-  int deg = 0;
-#pragma unroll
-  for (int b = 0; b < K; ++b) {
-    t.present[b] = nb[b] >= 0;
-#pragma unroll
-    for (int f = 0; f < 3; ++f) {
-      t.e[b][f] = t.present[b] ? eraw[b * 3 + f] : 0.0f;
-      sum[f] += t.e[b][f];
-    }
-    deg += t.present[b] ? 1 : 0;
-  }
-  const float rc = __builtin_amdgcn_rcpf((float)(deg > 0 ? deg : 1));
-#pragma unroll
-  for (int f = 0; f < 3; ++f) t.mean[f] = sum[f] * rc;
-}
-
-// the same terms from the COMPACT edge storage (graph_build.hip, FeatureArgs): slot b's attributes are (length of its offset,
+// EdgeTerms from the COMPACT edge storage (graph_build.hip, FeatureArgs): slot b's attributes are (length of its offset,
 // nan_to_num(depth[target] - depth[source]), slope) -- the length is one of the tile's three unit lengths (x, y, diagonal), exactly
 // doubled for a dilated slot; the depth difference is the float32 subtraction the feature kernel takes.  Bit for bit the values
 // of the full table, in the same summation order.
@@ -390,37 +365,6 @@ __device__ __forceinline__ void attention_head_pair(const EdgeTerms<K> &t, const
     const f32x2_t o = lg[b] * rden;
     out0[b] = o.x; out1[b] = o.y;
   }
-}
-
-// one head, from the raw operands (`nb` = node ids of the K stencil sources (< 0: absent), `hs` = alpha_src of the K sources and
-// (slot K) of the node itself, `eraw` = the node's [K][3] edge attributes, `ad` = its alpha_dst, `v` = V[head][0..2])
-template <int K>
-__device__ __forceinline__ void attention_coefficients_head_vals(const int (&nb)[K], const float (&hs)[K + 1],
-                                                                 const float (&eraw)[K * 3], float ad, const float (&v)[3],
-                                                                 float *out) {
-  EdgeTerms<K> t;
-  edge_terms<K>(nb, eraw, t);
-  attention_head<K>(t, hs, ad, v, out);
-}
-
-// attention_coefficients_head with the node's own operands already in registers (ED == 3): `eraw` = its [K][3]
-// edge-attribute block, `ad` = its alpha_dst for head hh, `v` = V[hh][0..2].  Lets the caller issue those global loads before the
-// halo ids are known (one latency less on the workgroup's critical path).
-template <int H, int K, int HWID = HALO_W>
-__device__ __forceinline__ void attention_coefficients_head_pre(int self_idx, int hh, const int *hid, const float *has,
-                                                                const float (&eraw)[K * 3], float ad, const float (&v)[3],
-                                                                float *out) {
-  using Off = StencilOffsets<K>;
-  int nb[K];
-  float hs[K + 1];
-#pragma unroll
-  for (int b = 0; b < K; ++b) {
-    const int nidx = self_idx - Off::dr[b] * HWID - Off::dc[b];
-    nb[b] = hid[nidx];
-    hs[b] = has[nidx * H + hh];
-  }
-  hs[K] = has[self_idx * H + hh];
-  attention_coefficients_head_vals<K>(nb, hs, eraw, ad, v, out);
 }
 
 }  // namespace bgnn

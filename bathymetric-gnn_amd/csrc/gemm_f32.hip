@@ -289,7 +289,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wres64_kernel(GemmArgs a) {
   float *biasl = b0l + 64;                           // [NC]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const int NW = blockDim.x >> 6;                    // 8 (4 only in the occupancy experiment)
+  const int NW = blockDim.x >> 6;                    // 8 (launch_wres64)
   {
     const char *src = reinterpret_cast<const char *>(a.Wt);
     constexpr int NQ = WIMG * 4 / 1024;              // 1-KiB pieces
@@ -714,13 +714,12 @@ static int launch_wres64(bgnn_ctx *ctx, const GemmArgs &a) {
     configured.fetch_or(1ull << (ctx->device & 63), std::memory_order_relaxed);
   }
   const int per_cu = lds_bytes > 80 * 1024 ? 1 : 2;
-  const int nw = ctx->opts.gemm_waves;
-  hipLaunchKernelGGL(kern, dim3(ctx->num_cus * per_cu), dim3(64 * nw), lds_bytes, ctx->stream, a);
+  hipLaunchKernelGGL(kern, dim3(ctx->num_cus * per_cu), dim3(512), lds_bytes, ctx->stream, a);
   BGNN_HIP_CHECK(hipGetLastError());
   return BGNN_OK;
 }
 
-// ---- layer 0 "aggregate first" (matrix_path = bf16, gat_layer_fused.hip gat_layer_bf16_2p_kernel<K, 4, AF>) --------------------------
+// ---- layer 0 "aggregate first" (matrix_path = bf16, gat_layer_fused.hip gat_layer_bf16_2p_kernel<K, AF>) --------------------------
 // GATConv's sum over the in-edges is linear, so  sum_j alpha_ij (W h1_j + b)  =  W (sum_j alpha_ij h1_j) + b sum_j alpha_ij : layer 0 can
 // aggregate the extractor's 64-channel h1 (128 bytes per node as bf16) instead of the 256-channel lin_0 product (512 bytes) and apply
 // each head's 64 x 64 block of the folded lin_0 weight afterwards, inside the fused launch.  What is left of the front GEMM is this
@@ -853,7 +852,7 @@ int launch_extractor_af(bgnn_ctx *ctx, const float *x8, const float *W0t, const 
 bool gemm_front_available(const bgnn_ctx *ctx, int64_t max_rows, int NC, int split_mode) {
   if (!ctx->opts.fused_front || (NC != 64 && NC != 256)) return false;
   if (split_mode == 3) return true;                                  // bf16 output: always the W-resident form
-  return split_mode == 0 && !ctx->opts.gemm_no_wres && max_rows >= BGNN_WRES_MIN_ROWS;
+  return split_mode == 0 && max_rows >= BGNN_WRES_MIN_ROWS;
 }
 
 int launch_gemm_f32(bgnn_ctx *ctx, const float *X, int ldx, const float *Wt, const float *bias, float *Y, int ldy,
@@ -890,12 +889,11 @@ int launch_gemm_f32(bgnn_ctx *ctx, const float *X, int ldx, const float *Wt, con
              split_mode == 2 ? split_inv_scale : 1.0f};
   if (front_W0t) BGNN_REQUIRE(K == 64 && att_src && gemm_front_available(ctx, max_rows, NC, split_mode) && (split_mode != 3 || Wt_split),
                               "gemm: the fused front needs the W-resident K = 64 attention form");
-  const bool no_wres = ctx->opts.gemm_no_wres != 0;
   // the split image is only read by the W-resident ATT form (NC 64 or 256); with a split path switched on that form runs
   // at EVERY batch size, so that a node's result does not depend on how many other nodes share its batch
   if (split_mode == 3) BGNN_REQUIRE(K == 64 && att_src && (NC == 64 || NC == 256) && Wt_split, "gemm: bf16 output needs the W-resident form");
-  if (!(K == 64 && (!no_wres || split_mode == 3) && att_src && (NC == 64 || NC == 256))) Wt_split = nullptr;
-  if (K == 64 && (!no_wres || split_mode == 3) && (max_rows >= BGNN_WRES_MIN_ROWS || Wt_split)) {    // W-resident persistent form
+  if (!(K == 64 && att_src && (NC == 64 || NC == 256))) Wt_split = nullptr;
+  if (K == 64 && (max_rows >= BGNN_WRES_MIN_ROWS || Wt_split)) {    // W-resident persistent form
     switch (NC / 32) {
 #define BGNN_WRES_CASE(NT) case NT:                                                                                 \
         if (front_W0t) {                                                                                           \

@@ -30,9 +30,9 @@ ABI_VERSION = 6
 MATRIX_PATHS = {"exact_f32": 0, "bf16x3": 1, "fp16x3": 2, "bf16": 3}
 # every int option of a context (include/bgnn.h, bgnn_ctx_set_option; the "diag_*" / "gemm_diag" ones only take non-zero values in
 # the diagnostic build)
-OPTION_NAMES = ("matrix_path", "fused", "fold_extractor", "ragged_atlas", "features_tiled", "fused_front", "fused_persistent",
-                "bf16_two_phase", "bf16_layer0_af", "stats_narrow", "fused_lds_pad_kb", "diag_mask", "diag_stamps", "gemm_waves",
-                "gemm_diag", "gemm_no_wres", "gemm_pair_major")
+OPTION_NAMES = ("matrix_path", "fused", "fold_extractor", "ragged_atlas", "features_tiled", "fused_front",
+                "bf16_two_phase", "bf16_layer0_af", "stats_narrow", "diag_mask", "diag_stamps",
+                "gemm_diag", "gemm_pair_major")
 
 
 GNN_TYPES = {"GAT": 0, "GCN": 1, "GraphSAGE": 2, "GIN": 3}      # BGNN_GNN_*

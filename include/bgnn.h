@@ -79,8 +79,6 @@ void *bgnn_ctx_stream(bgnn_ctx *ctx);
  *   "fold_extractor"  1 (default): extractor layer 2 folded into lin of GAT layer 0; 0: unfolded chain [BGNN_NO_FOLD]
  *   "fused_front"     1 (default): feature extractor layer 1 runs inside the lin_0 GEMM where that GEMM takes its W-resident form
  *                     (same instructions, bit-identical, one launch and 512 B/node of traffic less); 0: own launch [BGNN_NO_FUSED_FRONT]
- *   "fused_persistent" 0 (default) / 1: opt-in experiment -- big uniform batches on the exact path run the 256 -> 256 fused layer as
- *                     one persistent workgroup per CU (bit-identical results, currently slower)            [BGNN_PERSISTENT]
  *   "ragged_atlas"    1 (default): for ragged batches the fused layers walk a shelf-packed canvas of the grids (denser 8x16
  *                     blocks); 0: per-grid blocks                                                      [BGNN_NO_ATLAS]
  *   "features_tiled"  1 (default): node features / stencil table / edge attributes by the LDS-tiled kernel that computes the
@@ -96,8 +94,8 @@ void *bgnn_ctx_stream(bgnn_ctx *ctx);
  *                     folded lin_0 weight per head afterwards, inside the fused launch (GATConv's sum is linear; no lin_0 GEMM launch, no
  *                     256-channel lin_0 rows in HBM; needs bf16_two_phase = 1); 0: lin_0 GEMM first (another rounding sequence)   [BGNN_NO_LAYER0_AF]
  *   "stats_narrow"    -1 (default): 16-wide box-statistics workgroups when the 64-wide launch would leave CUs idle; 0 / 1 force
- * plus experiment / diagnostic knobs ("fused_lds_pad_kb", "gemm_waves", "gemm_no_wres"; "diag_mask",
- * "diag_stamps", "gemm_diag" exist only in the diagnostic build of the library).  Unknown names -> BGNN_ERR_INVALID. */
+ * plus diagnostic knobs ("diag_mask", "diag_stamps", "gemm_diag": exist only in the diagnostic build of the library).
+ * Unknown names -> BGNN_ERR_INVALID. */
 int bgnn_ctx_set_option(bgnn_ctx *ctx, const char *name, int value);
 int bgnn_ctx_get_option(bgnn_ctx *ctx, const char *name, int *value);
 

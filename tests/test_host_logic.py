@@ -177,7 +177,7 @@ def test_model_shapes_that_stay_refused_say_so_in_the_constructor():
     BathymetricGNN(in_channels=7, hidden_channels=100, heads=9, gnn_type="GCN")           # heads does not shape a plain backbone
 
 
-def test_pipelined_engines_share_every_context_option(monkeypatch):
+def test_pipelined_engines_copy_every_context_option(monkeypatch):
     """NativeVRProcessor alternates batches / chunks between two library contexts.  The second one must carry EVERY int option of
     the first -- also one switched after the second context was made (bf16_layer0_af, bf16_two_phase: other rounding sequences) --
     at every submit_batch and process_refinements; otherwise odd and even batches of one run would round differently."""
@@ -190,7 +190,7 @@ def test_pipelined_engines_share_every_context_option(monkeypatch):
             self.device = device
             self.opts = {k: 0 for k in rt.OPTION_NAMES}
             self.opts.update(fused=1, fold_extractor=1, ragged_atlas=1, features_tiled=1, fused_front=1, bf16_two_phase=1,
-                             bf16_layer0_af=1, stats_narrow=-1, gemm_waves=8, gemm_pair_major=1)
+                             bf16_layer0_af=1, stats_narrow=-1, gemm_pair_major=1)
 
         def get_option(self, name):
             return self.opts[name]
@@ -206,7 +206,7 @@ def test_pipelined_engines_share_every_context_option(monkeypatch):
     p._engine = SimpleNamespace(ctx=FakeCtx("dev"), review_threshold=0.6, norm_floor=0.01)
     p._engines, p._inflight, p._next_engine = [p._engine], [], 0
     primary = p._engine.ctx
-    primary.set_option("matrix_path", "bf16"); primary.set_option("gemm_waves", 4)
+    primary.set_option("matrix_path", "bf16"); primary.set_option("gemm_pair_major", 0)
     second = p._engine_at(1).ctx
     assert second is not primary and second.opts == primary.opts             # made with every option, not a selection
     seen = []

@@ -14,12 +14,9 @@ sd = synthetic.synthetic_state_dict(seed=1234)
 model = BathymetricGNN(in_channels=7, edge_dim=3, dropout=0.0); model.load_state_dict({k: torch.as_tensor(v) for k,v in sd.items()}); model.to(dev).eval()
 ap = argparse.ArgumentParser()
 ap.add_argument("--connectivity", default="8-connected"); ap.add_argument("--matrix-path", default="exact_f32")
-ap.add_argument("--persistent", action="store_true", help="the 256 -> 256 exact instance in its persistent form (own counters)")
 args = ap.parse_args()
 gb=GraphBuilder(device=dev, connectivity=args.connectivity); eng=TileBatchEngine(model, gb, dev)
 eng.ctx.set_option("matrix_path", args.matrix_path)
-if args.persistent:
-    eng.ctx.set_option("fused_persistent", 1)
 B,S=128,256
 depth,mask,_=synthetic.synthetic_tile_batch(8,S,S,100,"V0"); depth=np.concatenate([depth]*16); mask=np.concatenate([mask]*16)
 d_t=torch.from_numpy(depth).to(dev).reshape(-1); m_t=torch.from_numpy(mask.view(np.uint8)).to(dev).reshape(-1)
@@ -38,15 +35,6 @@ for i,nm in enumerate(names): print("%-20s %10.0f cycles/block  %5.1f%%"%(nm, bu
 if buf[14]:
     print("in-kernel clock: %.0f MHz (s_memtime / s_memrealtime x 100 MHz over every workgroup's lifetime)" % (100.0 * buf[13] / buf[14]))
     print("workgroup lifetime: %.1f us" % (buf[14] / n / 100.0))
-
-if buf[31]:
-    # the persistent form of the 256 -> 256 instance: timers summed in registers, one set of atomics per workgroup (unperturbed)
-    pn = buf[31]; pnames = ["block-start wait + barrier", "phase A", "slab wait + barrier", "prefetch hooks", "gather + BN/ReLU", "MFMA (+ DMA requests)", "pre-epilogue barrier", "epilogue"]
-    order = [0, 1, 2, 3, 4, 5, 6] ; vals = [buf[16 + 0], buf[16 + 1], buf[16 + 2] , buf[16 + 3], buf[16 + 4], buf[16 + 5], buf[16 + 6], buf[16 + 7]]
-    lab = {0: "block-start wait + barrier", 1: "phase A", 2: "slab wait + barrier + prefetch hooks", 3: "gather + BN/ReLU", 4: "MFMA (+ DMA requests)", 5: "pre-epilogue wait + barrier", 6: "epilogue", 7: "loop bookkeeping"}
-    ptot = sum(vals)
-    print("persistent kernel: blocks", pn, "cycles/block", ptot / pn)
-    for i in range(8): print("  %-40s %10.0f cycles/block  %5.1f%%" % (lab[i], vals[i] / pn, 100 * vals[i] / ptot))
 
 for base, title in ((32, "256 -> 64 instance"), (48, "heads instance")):
     if buf[base + 15]:
