@@ -255,7 +255,7 @@ int bgnn_ctx_destroy(bgnn_ctx *ctx) {
   for (auto &r : ctx->prof_records) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
   for (auto &e : ctx->event_pool) (void)hipEventDestroy(e);
   for (auto &st : ctx->staging) { (void)hipEventDestroy(st.ev); (void)hipHostFree(st.p); }
-  for (int i = 0; i < 6; ++i) if (ctx->ws[i]) (void)hipFree(ctx->ws[i]);
+  for (int i = 0; i < 7; ++i) if (ctx->ws[i]) (void)hipFree(ctx->ws[i]);
   for (auto &e : ctx->table_cache) { (void)hipFree(e.d_tiles); (void)hipFree(e.d_items); }
   if (ctx->zero_page) (void)hipFree(ctx->zero_page);
   ctx->pool.trim();
@@ -713,10 +713,14 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, const fl
   const size_t o_ones = reserve(512);                     // (as wide as the widest layer: heads * hidden <= 512)
   std::fill(pk.begin() + o_ones, pk.begin() + o_ones + 512, 1.0f);
   // heads: first layers concatenated column-wise, second layers packed
+  const size_t o_raw = reserve(n_weights);               // the blob as given: the backward's untransposed weights
+  std::copy(w, w + n_weights, pk.begin() + o_raw);
+  size_t o_hW0 = reserve((size_t)HT * hid);
   size_t o_hW0t = reserve((size_t)hid * HT), o_hb0 = reserve(HT);
   size_t o_hW1 = reserve((size_t)d->num_classes * hh + 2 * hh), o_hb1 = reserve(d->num_classes + 2);
   for (int k = 0; k < nh; ++k) {
     for (int o = 0; o < hh; ++o) for (int i = 0; i < hid; ++i) pk[o_hW0t + (size_t)i * HT + k * hh + o] = p[(size_t)o * hid + i];
+    std::copy(p, p + (size_t)hh * hid, pk.begin() + o_hW0 + (size_t)k * hh * hid);
     p += (size_t)hh * hid;
     std::copy(p, p + hh, pk.begin() + o_hb0 + k * hh); p += hh;
     const int nout = k == 0 ? d->num_classes : 1;
@@ -897,6 +901,7 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, const fl
   m->hd_W0sp16 = gat && f16_ok ? m->blob + o_hW0sp16 : nullptr;
   m->hd_W0t = m->blob + o_hW0t; m->hd_b0 = m->blob + o_hb0; m->hd_W1 = m->blob + o_hW1; m->hd_b1 = m->blob + o_hb1;
   m->hd_tab = htab_ok ? m->blob + o_htab : nullptr;
+  m->raw = m->blob + o_raw; m->hd_W0 = m->blob + o_hW0;
   *out = m;
   return BGNN_OK;
 }
@@ -958,6 +963,7 @@ static void graph_free(bgnn_graph *g) {
   P.release(g->d_eattr); P.release(g->d_rowptr); P.release(g->d_edge_perm);
   P.release(g->d_slope); P.release(g->d_node_depth); P.release(g->d_tile_dist); P.release(g->d_atlas_tile_of);
   P.release(g->d_atlas);
+  P.release(g->d_tr_ptr); P.release(g->d_tr_slot); P.release(g->d_tr_dst);
   delete g;
 }
 
@@ -1292,10 +1298,58 @@ struct GridOut {             // optional fused node -> grid outputs (bgnn_infer_
   bool done = false;         // set when the fused tail wrote the grids
 };
 
+// The tape of a taped training forward (bgnn_forward_train_tape): byte offsets of the saved activations, every table
+// [row_capacity][width] float32 row-major.  Header (BgnnTapeHeader) at 0.
+struct TapeLayout {
+  size_t h0 = 0, h1 = 0;                    // extractor: ReLU(+dropout) output of its first Linear, output of its second
+  std::vector<size_t> xw, asd, z, hout;     // per GAT layer: lin output [HC], attention dots [2H], BatchNorm input [W], layer output [W]
+  std::vector<size_t> mean, rstd;           // per GAT layer: the batch statistics, float64 [W]
+  size_t hbd = 0;                           // the heads' hidden units after ReLU and dropout [head_hidden_total]
+  size_t total = 0;
+};
+
+static void tape_layout(const bgnn_model *m, const bgnn_graph *g, TapeLayout &t) {
+  const size_t rows = (size_t)std::max<int32_t>(g->row_capacity, 0), hid = (size_t)m->desc.hidden;
+  size_t off = 256;
+  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  t.h0 = take(rows * hid * 4); t.h1 = take(rows * hid * 4);
+  for (const BgnnLayer &L : m->layers) {
+    const size_t HC = (size_t)L.heads * hid, W = (size_t)L.width;
+    t.xw.push_back(take(rows * HC * 4)); t.asd.push_back(take(rows * 2 * L.heads * 4));
+    t.z.push_back(take(rows * W * 4)); t.hout.push_back(take(rows * W * 4));
+    t.mean.push_back(take(W * 8)); t.rstd.push_back(take(W * 8));
+  }
+  t.hbd = take(rows * (size_t)m->head_hidden_total * 4);
+  t.total = off;
+}
+
+// what the backward pass covers (BGNN_ERR_UNSUPPORTED + message otherwise)
+static int backward_supported(const bgnn_model *m) {
+  const bgnn_model_desc &d = m->desc;
+  if (d.gnn_type != BGNN_GNN_GAT) {
+    set_error("backward pass: only the GAT backbone has one (gnn_type=%s)", d.gnn_type == BGNN_GNN_GCN ? "GCN" : d.gnn_type == BGNN_GNN_SAGE ? "GraphSAGE" : "GIN");
+    return BGNN_ERR_UNSUPPORTED;
+  }
+  if (m->padded) {
+    set_error("backward pass: hidden_channels=%d / heads=%d run zero-padded; the training path exists for hidden 32 / 64 / 128 and "
+              "power-of-two head counts only", m->logical_hidden, m->logical_heads);
+    return BGNN_ERR_UNSUPPORTED;
+  }
+  for (const BgnnLayer &L : m->layers)
+    if (L.heads * d.hidden > 256) {
+      set_error("backward pass: layers wider than 256 columns are not supported (heads=%d x hidden_channels=%d = %d)", L.heads, d.hidden,
+                L.heads * d.hidden);
+      return BGNN_ERR_UNSUPPORTED;
+    }
+  return BGNN_OK;
+}
+
 // training-mode forward: BatchNorm statistics of this batch, written layer by layer ([sum of layer widths] each)
 struct TrainOut {
   float *mean, *var_unbiased;
   const bgnn_dropout *dp = nullptr;      // active dropout (bgnn_forward_train_dropout)
+  char *tape = nullptr;                  // taped forward: saved activations (TapeLayout)
+  const TapeLayout *tl = nullptr;
 };
 
 static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_auto, float thr_review,
@@ -1329,6 +1383,14 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
   void *bnws = nullptr;
   if (tr) BGNN_TRY(ctx_workspace(ctx, 5, bn_train_workspace_bytes(maxw >= 256 ? 256 : maxw), &bnws));
   size_t tr_off = 0;
+  // taped forward: the saved activations are COPIES of the forward's own tables (outputs and statistics stay bit-identical)
+  char *tape = tr ? tr->tape : nullptr;
+  const TapeLayout *tl = tr ? tr->tl : nullptr;
+  auto save = [&](size_t off, const void *src, size_t bytes) -> int {
+    BGNN_HIP_CHECK(hipMemcpyAsync(tape + off, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return BGNN_OK;
+  };
+  size_t bn_layer = 0;
   // training mode with active dropout: x [rows][width] *= keep / (1 - p) in place (stream ids: bgnn.h, bgnn_dropout)
   const bgnn_dropout *dp = tr ? tr->dp : nullptr;
   auto drop = [&](float *x, int width, float p, uint32_t stream) {
@@ -1339,9 +1401,12 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
     for (int c0 = 0; c0 < L.width && rc == BGNN_OK; c0 += 256) {
       const int w = std::min(256, L.width - c0);
       rc = launch_bn_train(ctx, z + c0, L.width, w, rows, dm, L.bn_w + c0, L.bn_b + c0, d.bn_eps, relu, bnws,
-                           tr->mean ? tr->mean + tr_off + c0 : nullptr, tr->var_unbiased ? tr->var_unbiased + tr_off + c0 : nullptr);
+                           tr->mean ? tr->mean + tr_off + c0 : nullptr, tr->var_unbiased ? tr->var_unbiased + tr_off + c0 : nullptr,
+                           tape ? (double *)(tape + tl->mean[bn_layer]) + c0 : nullptr,
+                           tape ? (double *)(tape + tl->rstd[bn_layer]) + c0 : nullptr);
     }
     tr_off += (size_t)L.width;
+    ++bn_layer;
     return rc;
   };
   // feature extractor (gnn.py:386): Linear(in,hid) ReLU [Dropout] Linear(hid,hid); then lin of layer 0
@@ -1446,6 +1511,12 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
       if (!layer0_done) {
       if (!front) BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, 8, hid, 1));
       if (!front && dp) BGNN_TRY(drop(Y, hid, dp->p_extractor, 1));
+      if (tape) {        // the folded chain never forms h0 (front form) or h1: the tape gets them from their own launches
+        float *h0 = (float *)(tape + tl->h0);
+        if (front) BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, h0, hid, dm, rows, 8, hid, 1));
+        else BGNN_TRY(save(tl->h0, Y, (size_t)rows * hid * sizeof(float)));
+        BGNN_TRY(launch_gemm_f32(ctx, h0, hid, m->fe_W1t, m->fe_b1, (float *)(tape + tl->h1), hid, dm, rows, hid, hid, 0));
+      }
       BGNN_TRY(launch_gemm_f32(ctx, front ? g->d_x8 : Y, front ? 8 : hid, m->l0f_Wt, m->l0f_b, X, L0.heads * hid, dm, rows, hid,
                                L0.heads * hid, 0, L0.att_src, L0.att_dst, asdX, L0.heads, hid, wsplit, smode,
                                front ? m->fe_W0t : nullptr, front ? m->fe_b0 : nullptr, front && smode == 0 ? m->l0f_Wpm : nullptr,
@@ -1456,6 +1527,10 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
       BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, X, hid, dm, rows, 8, hid, 1));
       if (dp) BGNN_TRY(drop(X, hid, dp->p_extractor, 1));
       BGNN_TRY(launch_gemm_f32(ctx, X, hid, m->fe_W1t, m->fe_b1, Y, hid, dm, rows, hid, hid, 0));
+      if (tape) {
+        BGNN_TRY(save(tl->h0, X, (size_t)rows * hid * sizeof(float)));
+        BGNN_TRY(save(tl->h1, Y, (size_t)rows * hid * sizeof(float)));
+      }
       BGNN_TRY(launch_gemm_f32(ctx, Y, L0.d_in, L0.Wt, nullptr, X, L0.heads * hid, dm, rows, L0.d_in, L0.heads * hid, 0,
                                L0.att_src, L0.att_dst, asdX, L0.heads, hid, nullptr, 0, nullptr, nullptr, nullptr, L0.Wt_blk));
     }
@@ -1475,6 +1550,10 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
     // GATConv(dropout = p) in training mode: the coefficients are thinned inside the plain aggregate kernel
     const bool att_drop = dp && dp->p_attention > 0.0f;
     const DropSpec att_spec = att_drop ? make_drop_spec(dp->p_attention, dp->seed, 16 + (uint32_t)l) : DropSpec{};
+    if (tape) {
+      BGNN_TRY(save(tl->xw[l], X, (size_t)rows * L.heads * hid * sizeof(float)));
+      BGNN_TRY(save(tl->asd[l], asdX, (size_t)rows * 2 * L.heads * sizeof(float)));
+    }
     if (l + 1 < nl) {
       const BgnnLayer &Ln = m->layers[l + 1];
       int rc = use_fused ? launch_fused_layer_next(ctx, g, L, Ln, hid, V3, X, asdX, Y, asdY) : BGNN_ERR_UNSUPPORTED;
@@ -1484,8 +1563,10 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
       rc = att_drop ? BGNN_ERR_UNSUPPORTED : launch_gat_aggregate_tiled(ctx, g, L, hid, d.edge_dim, X, asdX, Y, tr ? 0 : relu);
       if (rc == BGNN_ERR_UNSUPPORTED) rc = launch_gat_aggregate(ctx, g, L, hid, d.edge_dim, X, asdX, Y, tr ? 0 : relu, att_drop ? &att_spec : nullptr);
       BGNN_TRY(rc);
+      if (tape) BGNN_TRY(save(tl->z[l], Y, (size_t)rows * L.width * sizeof(float)));
       if (tr) BGNN_TRY(batch_norm(Y, L, relu));
       if (dp && relu) BGNN_TRY(drop(Y, L.width, dp->p_features, 64 + (uint32_t)l));
+      if (tape) BGNN_TRY(save(tl->hout[l], Y, (size_t)rows * L.width * sizeof(float)));
       BGNN_TRY(launch_gemm_f32(ctx, Y, Ln.d_in, Ln.Wt, nullptr, X, Ln.heads * hid, dm, rows, Ln.d_in, Ln.heads * hid, 0,
                                Ln.att_src, Ln.att_dst, asdX, Ln.heads, hid, nullptr, 0, nullptr, nullptr, nullptr, Ln.Wt_blk));
     } else {
@@ -1499,8 +1580,10 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
       rc = att_drop ? BGNN_ERR_UNSUPPORTED : launch_gat_aggregate_tiled(ctx, g, L, hid, d.edge_dim, X, asdX, Y, tr ? 0 : relu);
       if (rc == BGNN_ERR_UNSUPPORTED) rc = launch_gat_aggregate(ctx, g, L, hid, d.edge_dim, X, asdX, Y, tr ? 0 : relu, att_drop ? &att_spec : nullptr);
       BGNN_TRY(rc);
+      if (tape) BGNN_TRY(save(tl->z[l], Y, (size_t)rows * L.width * sizeof(float)));
       if (tr) BGNN_TRY(batch_norm(Y, L, relu));
       if (dp && relu) BGNN_TRY(drop(Y, L.width, dp->p_features, 64 + (uint32_t)l));     // (a single-layer backbone has no ReLU: never)
+      if (tape) BGNN_TRY(save(tl->hout[l], Y, (size_t)rows * L.width * sizeof(float)));
     }
   }
   if (o->hidden)                  // [N][logical hidden]: a padded model's pad columns (all zero) stay inside
@@ -1510,6 +1593,7 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
                            m->head_hidden_total, 1));
   if (dp && dp->p_heads > 0.0f)      // (the draw is indexed over the heads' own units; the table may carry pad columns up to a multiple of 32)
     BGNN_TRY(launch_dropout(ctx, hidb, head_count(&d) * (hid / 2), m->head_hidden_total, dm, rows, make_drop_spec(dp->p_heads, dp->seed, 2)));
+  if (tape) BGNN_TRY(save(tl->hbd, hidb, (size_t)rows * m->head_hidden_total * sizeof(float)));
   BGNN_TRY(launch_heads_final(ctx, m, hidb, m->head_hidden_total, dm, rows, thr_auto, thr_review, o));
   return BGNN_OK;
 }
@@ -1584,8 +1668,16 @@ int bgnn_forward_train(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float *bn_ba
   return bgnn_forward_train_dropout(ctx, m, g, nullptr, bn_batch_mean, bn_batch_var, o);
 }
 
+static int forward_train_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const bgnn_dropout *dropout, float *bn_batch_mean,
+                              float *bn_batch_var, const bgnn_outputs *o, void *tape, size_t tape_bytes);
+
 int bgnn_forward_train_dropout(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const bgnn_dropout *dropout, float *bn_batch_mean,
                                float *bn_batch_var, const bgnn_outputs *o) {
+  return forward_train_impl(ctx, m, g, dropout, bn_batch_mean, bn_batch_var, o, nullptr, 0);
+}
+
+static int forward_train_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const bgnn_dropout *dropout, float *bn_batch_mean,
+                              float *bn_batch_var, const bgnn_outputs *o, void *tape, size_t tape_bytes) {
   BGNN_REQUIRE(ctx && m && g && o, "bgnn_forward_train: NULL argument");
   if (dropout) {
     const float ps[4] = {dropout->p_extractor, dropout->p_attention, dropout->p_features, dropout->p_heads};
@@ -1606,7 +1698,151 @@ int bgnn_forward_train_dropout(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, cons
   // torch.nn.functional.batch_norm in training mode refuses a single row the same way
   BGNN_REQUIRE(c[0] != 1, "Expected more than 1 value per channel when training, got input size [1, %d]", m->layers[0].width);
   TrainOut tr{bn_batch_mean, bn_batch_var, dropout};
+  TapeLayout tl;
+  if (tape) {
+    BGNN_TRY(backward_supported(m));
+    tape_layout(m, g, tl);
+    BGNN_REQUIRE(tape_bytes >= tl.total, "bgnn_forward_train_tape: the tape has %zu bytes, this model and graph need %zu (bgnn_tape_bytes)",
+                 tape_bytes, tl.total);
+    BgnnTapeHeader h{};
+    const bgnn_dropout *dp = dropout;
+    h.s_ext = dp ? make_drop_spec(dp->p_extractor, dp->seed, 1).scale : 1.0f;
+    h.s_feat = dp ? make_drop_spec(dp->p_features, dp->seed, 0).scale : 1.0f;
+    h.s_heads = dp ? make_drop_spec(dp->p_heads, dp->seed, 2).scale : 1.0f;
+    h.att = dp ? make_drop_spec(dp->p_attention, dp->seed, 16) : DropSpec{};
+    BGNN_TRY(ctx_upload(ctx, &h, sizeof(h), tape));
+    tr.tape = (char *)tape; tr.tl = &tl;
+  }
   return forward_impl(ctx, m, g, 0.85f, 0.6f, o, nullptr, &tr);
+}
+
+size_t bgnn_tape_bytes(const bgnn_model *m, const bgnn_graph *g) {
+  if (!m || !g) { set_error("bgnn_tape_bytes: NULL argument"); return 0; }
+  if (backward_supported(m) != BGNN_OK) return 0;
+  TapeLayout tl;
+  tape_layout(m, g, tl);
+  return tl.total;
+}
+
+int bgnn_forward_train_tape(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const bgnn_dropout *dropout, float *bn_batch_mean,
+                            float *bn_batch_var, const bgnn_outputs *o, void *tape, size_t tape_bytes) {
+  BGNN_REQUIRE(tape, "bgnn_forward_train_tape: NULL tape");
+  return forward_train_impl(ctx, m, g, dropout, bn_batch_mean, bn_batch_var, o, tape, tape_bytes);
+}
+
+// ---- backward --------------------------------------------------------------------------------------------------------------
+// Offsets of every tensor of the weight blob (bgnn_model_weight_count order) -- of the gradient blob as well.
+struct GradOffsets {
+  size_t fe_W0, fe_b0, fe_W1, fe_b1;
+  struct Layer { size_t W, as, ad, ae, We, bias, bn_w, bn_b; };
+  std::vector<Layer> layers;
+  size_t hd_W0[3], hd_b0[3], hd_W1[3], hd_b1[3];
+};
+
+static void grad_offsets(const bgnn_model_desc &d, GradOffsets &g) {
+  const size_t hid = d.hidden, hh = hid / 2;
+  size_t o = 0;
+  g.fe_W0 = o; o += hid * d.in_channels; g.fe_b0 = o; o += hid; g.fe_W1 = o; o += hid * hid; g.fe_b1 = o; o += hid;
+  for (int l = 0; l < d.num_layers; ++l) {
+    const bool last = l == d.num_layers - 1;
+    const size_t H = last ? 1 : d.heads, D = l == 0 ? hid : hid * d.heads, HC = H * hid, W = last ? hid : HC;
+    GradOffsets::Layer L;
+    L.W = o; o += HC * D; L.as = o; o += HC; L.ad = o; o += HC; L.ae = o; o += HC; L.We = o; o += HC * d.edge_dim;
+    L.bias = o; o += W; L.bn_w = o; o += W; L.bn_b = o; o += W; o += 2 * W;      // (running_mean / running_var: no gradient)
+    g.layers.push_back(L);
+  }
+  for (int k = 0; k < (d.predict_correction ? 3 : 2); ++k) {
+    const size_t nout = k == 0 ? d.num_classes : 1;
+    g.hd_W0[k] = o; o += hh * hid; g.hd_b0[k] = o; o += hh; g.hd_W1[k] = o; o += nout * hh; g.hd_b1[k] = o; o += nout;
+  }
+}
+
+int bgnn_backward(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const void *tape, const bgnn_output_grads *gin, float *grad_weights) {
+  BGNN_REQUIRE(ctx && m && g && tape && gin && grad_weights, "bgnn_backward: NULL argument");
+  BGNN_REQUIRE(m->ctx == ctx && g->ctx == ctx, "bgnn_backward: model/graph belong to another context");
+  BGNN_TRY(backward_supported(m));
+  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  const bgnn_model_desc &d = m->desc;
+  const size_t nw = bgnn_model_weight_count(&d);
+  BGNN_HIP_CHECK(hipMemsetAsync(grad_weights, 0, nw * sizeof(float), ctx->stream));   // (running statistics: 0)
+  const int64_t rows = g->row_capacity;
+  if (rows <= 0) return BGNN_OK;
+  BGNN_REQUIRE(g->F == d.in_channels && g->ED == d.edge_dim, "bgnn_backward: graph does not fit the model");
+  TapeLayout tl;
+  tape_layout(m, g, tl);
+  GradOffsets go;
+  grad_offsets(d, go);
+  const char *tp = (const char *)tape;
+  auto T = [&](size_t off) { return (float *)(tp + off); };
+  const BgnnTapeHeader *hdr = (const BgnnTapeHeader *)tape;
+  const float *s_ext = (const float *)tape, *s_feat = s_ext + 1;
+  const int hid = d.hidden, hh = hid / 2, nc = d.num_classes, nh = head_count(&d), HT = m->head_hidden_total, ED = d.edge_dim;
+  const int n2 = nc + nh - 1, L = (int)m->layers.size();
+  const int64_t *dm = g->d_counts;
+  int Hmax = 1;
+  for (const BgnnLayer &Ly : m->layers) Hmax = std::max(Hmax, Ly.heads);
+  const int64_t slots = gat_bwd_slot_count(g);
+  // scratch (context slot 6): two row tables for the running gradient, dxw, d(attention dots), per-node dV shares, the per-slot
+  // alpha~ / dlogit tables, the heads' gradients, dV, then the reduction workspaces
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  const size_t oG0 = take((size_t)rows * 256 * 4), oG1 = take((size_t)rows * 256 * 4), oDXW = take((size_t)rows * 256 * 4);
+  const size_t oDASD = take((size_t)rows * 2 * Hmax * 4), oDVN = take((size_t)rows * Hmax * ED * 4);
+  const size_t oAL = take((size_t)slots * Hmax * 4), oDL = take((size_t)slots * Hmax * 4);
+  const size_t oDY2 = take((size_t)rows * n2 * 4), oDHID = take((size_t)rows * HT * 4), oDV = take(64 * 4);
+  const size_t oWG = take(wgrad_workspace_bytes()), oCS = take(colsum_workspace_bytes()), oBN = take(bn_backward_workspace_bytes(256));
+  void *ws;
+  BGNN_TRY(ctx_workspace(ctx, 6, off, &ws));
+  char *wb = (char *)ws;
+  float *G0 = (float *)(wb + oG0), *G1 = (float *)(wb + oG1), *DXW = (float *)(wb + oDXW), *DASD = (float *)(wb + oDASD);
+  float *DVN = (float *)(wb + oDVN), *AL = (float *)(wb + oAL), *DL = (float *)(wb + oDL), *DY2 = (float *)(wb + oDY2);
+  float *DHID = (float *)(wb + oDHID), *DV = (float *)(wb + oDV);
+  void *WG = wb + oWG, *CS = wb + oCS, *BNW = wb + oBN;
+  float *gw = grad_weights;
+  const float *raw = m->raw;
+
+  // heads (gnn.py:392-406): second layers, then the first layers, then dL/d(backbone output) = dhid . W0 (stacked)
+  BGNN_TRY(launch_heads_backward(ctx, m, T(tl.hbd), gin->class_logits, gin->class_probs, gin->confidence,
+                                 d.predict_correction ? gin->correction : nullptr, hdr, dm, rows, DY2, DHID));
+  const float *hL = T(tl.hout[L - 1]);
+  for (int k = 0; k < nh; ++k) {
+    const int nout = k == 0 ? nc : 1, col = k == 0 ? 0 : nc + k - 1;
+    BGNN_TRY(launch_wgrad(ctx, DY2 + col, n2, T(tl.hbd) + k * hh, HT, dm, rows, nout, hh, gw + go.hd_W1[k], hh, WG));
+    BGNN_TRY(launch_colsum(ctx, DY2 + col, n2, nout, nullptr, 0, 0, 1, dm, rows, gw + go.hd_b1[k], CS));
+    BGNN_TRY(launch_wgrad(ctx, DHID + k * hh, HT, hL, hid, dm, rows, hh, hid, gw + go.hd_W0[k], hid, WG));
+    BGNN_TRY(launch_colsum(ctx, DHID + k * hh, HT, hh, nullptr, 0, 0, 1, dm, rows, gw + go.hd_b0[k], CS));
+  }
+  BGNN_TRY(launch_gemm_f32(ctx, DHID, HT, m->hd_W0, nullptr, G0, hid, dm, rows, HT, hid, 0));
+  // GAT layers, last to first.  Invariant: G0 = dL/d(output of layer l) [rows][width]
+  for (int l = L - 1; l >= 0; --l) {
+    const BgnnLayer &Ly = m->layers[l];
+    const GradOffsets::Layer &O = go.layers[l];
+    const int W = Ly.width, H = Ly.heads, HC = H * hid, D = Ly.d_in;
+    const int relu = l + 1 < L ? 1 : 0;
+    // BatchNorm (+ ReLU + feature dropout) backward: G0 becomes dL/dz; then the GAT bias
+    BGNN_TRY(launch_bn_backward(ctx, G0, relu ? T(tl.hout[l]) : nullptr, T(tl.z[l]), W, (const double *)T(tl.mean[l]),
+                                (const double *)T(tl.rstd[l]), Ly.bn_w, relu, s_feat, dm, rows, BNW, gw + O.bn_w, gw + O.bn_b));
+    BGNN_TRY(launch_colsum(ctx, G0, W, W, nullptr, 0, 0, 1, dm, rows, gw + O.bias, CS));
+    // attention (concat, or the last layer's single head: the aggregate's gradient is dL/dz itself)
+    BGNN_TRY(launch_gat_backward(ctx, g, Ly, hid, ED, hdr, 16 + (uint32_t)l, T(tl.xw[l]), T(tl.asd[l]), G0, AL, DL, DASD, DVN, DXW));
+    BGNN_TRY(launch_colsum(ctx, T(tl.xw[l]), HC, HC, DASD, 2 * H, 0, hid, dm, rows, gw + O.as, CS));
+    BGNN_TRY(launch_colsum(ctx, T(tl.xw[l]), HC, HC, DASD, 2 * H, H, hid, dm, rows, gw + O.ad, CS));
+    BGNN_TRY(launch_colsum(ctx, DVN, H * ED, H * ED, nullptr, 0, 0, 1, dm, rows, DV, CS));
+    BGNN_TRY(launch_gat_edge_param_grads(ctx, DV, raw + O.ae, raw + O.We, H, hid, ED, gw + O.ae, gw + O.We));
+    // lin: dW = dxw^T . h_in, dL/dh_in = dxw . W
+    const float *hin = l > 0 ? T(tl.hout[l - 1]) : T(tl.h1);
+    BGNN_TRY(launch_wgrad(ctx, DXW, HC, hin, D, dm, rows, HC, D, gw + O.W, D, WG));
+    BGNN_TRY(launch_gemm_f32(ctx, DXW, HC, raw + O.W, nullptr, G1, D, dm, rows, HC, D, 0));
+    std::swap(G0, G1);
+  }
+  // feature extractor (gnn.py:386): Linear, ReLU, Dropout, Linear
+  BGNN_TRY(launch_wgrad(ctx, G0, hid, T(tl.h0), hid, dm, rows, hid, hid, gw + go.fe_W1, hid, WG));
+  BGNN_TRY(launch_colsum(ctx, G0, hid, hid, nullptr, 0, 0, 1, dm, rows, gw + go.fe_b1, CS));
+  BGNN_TRY(launch_gemm_f32(ctx, G0, hid, raw + go.fe_W1, nullptr, G1, hid, dm, rows, hid, hid, 0));
+  BGNN_TRY(launch_relu_drop_bwd(ctx, G1, hid, T(tl.h0), hid, hid, dm, rows, s_ext));
+  BGNN_TRY(launch_wgrad(ctx, G1, hid, g->d_x8, 8, dm, rows, hid, d.in_channels, gw + go.fe_W0, d.in_channels, WG));
+  BGNN_TRY(launch_colsum(ctx, G1, hid, hid, nullptr, 0, 0, 1, dm, rows, gw + go.fe_b0, CS));
+  return BGNN_OK;
 }
 
 int bgnn_infer_tiles(bgnn_ctx *ctx, bgnn_model *m, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, float thr_auto,

@@ -11,6 +11,7 @@
 #include <atomic>
 
 #include "../../include/bgnn.h"
+#include "../../include/bgnn_train.h"
 
 namespace bgnn {
 
@@ -111,8 +112,9 @@ struct bgnn_ctx {
   std::vector<bgnn::ProfRecord> prof_records;
   std::vector<hipEvent_t> event_pool;
   // forward workspace (grow-only)
-  void *ws[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t ws_bytes[6] = {0, 0, 0, 0, 0, 0};
+  // (slots 0-5: forward and sub-module calls; 6: bgnn_backward's scratch)
+  void *ws[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t ws_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
   // pinned staging for host->device tables: a table is copied into a pinned buffer at call time and DMA'd from there,
   // so the caller's (often function-local, pageable) source may go away while the copy is still queued behind
   // other stream work; a buffer is reused once its event has completed
@@ -179,6 +181,8 @@ struct bgnn_model {
   float *hd_W0t, *hd_b0;      // [hid][head_hidden_total], [head_hidden_total]
   float *hd_W0sp = nullptr, *hd_W0sp16 = nullptr;   // hd_W0t as bf16 / float16 hi / lo split images
   float hd_W0sp16_inv = 1.0f, l0f_Wsp16_inv = 1.0f; // 2^-S of the float16 images (pack_split)
+  float *raw = nullptr;       // the caller's weight blob as given (bgnn_model_weight_count order): the backward's untransposed weights
+  float *hd_W0 = nullptr;     // the heads' first layers untransposed, stacked [head_hidden_total][hid] (pad rows zero)
   float *hd_W1, *hd_b1;       // second layers packed: cls [classes][hid/2], conf [hid/2], corr [hid/2]; biases
   float *hd_tab = nullptr;    // fused heads epilogue's LDS image, [296]: b0 [96] | second-layer rows [<= 6][32] | their biases [8]
   // The fused layer kernels rebuild a slot's attributes in the CANONICAL order (distance, depth_difference, slope).  For a graph built
@@ -253,6 +257,11 @@ struct bgnn_graph {
   BgnnTileMeta *d_atlas_tile = nullptr;   // the canvas as ONE tile {h, w, cell_off = 0}
   int32_t *d_atlas_pos = nullptr;         // [n_tiles][2] = (row, column) of each grid's origin on the canvas
   int32_t atlas_h = 0, atlas_w = 0;
+  // backward pass (bgnn_backward): the out-edges of every node, built on first use (gat_backward.hip, ensure_transposed_index)
+  mutable bool tr_valid = false;
+  mutable int32_t *d_tr_ptr = nullptr;    // [rows + 1]
+  mutable int32_t *d_tr_slot = nullptr;   // slot of the edge in the backward's per-slot tables
+  mutable int32_t *d_tr_dst = nullptr;    // its target node
 };
 
 namespace bgnn {
@@ -318,6 +327,11 @@ inline DropSpec make_drop_spec(float p, uint64_t seed, uint32_t stream) {
   d.seed = seed; d.stream = stream;
   return d;
 }
+// The head of a tape (bgnn_forward_train_tape): what the backward needs to know about the forward's dropouts, read by its kernels
+struct BgnnTapeHeader {
+  float s_ext, s_feat, s_heads, pad;   // 1 / (1 - p) of the extractor / feature / head dropouts (1 when off)
+  DropSpec att;                        // attention dropout (thr 0: off; the stream is 16 + layer)
+};
 // x [M][width] (leading dimension ld) *= keep / (1 - p), in place; M from d_m
 int launch_dropout(bgnn_ctx *ctx, float *x, int width, int ld, const int64_t *d_m, int64_t max_rows, const DropSpec &d);
 int launch_gat_aggregate(bgnn_ctx *ctx, const bgnn_graph *g, const BgnnLayer &L, int C, int ED, const float *xw,
@@ -343,7 +357,30 @@ int launch_neighbor_reduce(bgnn_ctx *ctx, const bgnn_graph *g, int mode, const f
                            const float *scale, const float *shift, int relu, float *out, int ldo, float *copy_self);
 size_t bn_train_workspace_bytes(int W);
 int launch_bn_train(bgnn_ctx *ctx, float *z, int ld, int W, int64_t max_rows, const int64_t *d_m, const float *bn_w,
-                    const float *bn_b, float eps, int relu, void *workspace, float *batch_mean, float *batch_var_unbiased);
+                    const float *bn_b, float eps, int relu, void *workspace, float *batch_mean, float *batch_var_unbiased,
+                    double *stat_mean = nullptr, double *stat_rstd = nullptr);
+// ---- backward pass (bgnn_backward) ----
+size_t bn_backward_workspace_bytes(int W);
+int launch_bn_backward(bgnn_ctx *ctx, float *d, const float *h, const float *z, int W, const double *mean, const double *rstd,
+                       const float *bn_w, int relu, const float *drop_scale, const int64_t *d_m, int64_t max_rows, void *workspace,
+                       float *d_bn_w, float *d_bn_b);
+size_t wgrad_workspace_bytes();
+int launch_wgrad(bgnn_ctx *ctx, const float *dY, int ldy, const float *X, int ldx, const int64_t *d_m, int64_t max_rows, int n_out,
+                 int n_in, float *dW, int ldw, void *workspace);
+size_t colsum_workspace_bytes();
+int launch_colsum(bgnn_ctx *ctx, const float *X, int ld, int W, const float *S, int lds, int s_off, int s_div, const int64_t *d_m,
+                  int64_t max_rows, float *out, void *workspace);
+int launch_relu_drop_bwd(bgnn_ctx *ctx, float *d, int ldd, const float *h, int ldh, int W, const int64_t *d_m, int64_t max_rows,
+                         const float *scale);
+int ensure_transposed_index(const bgnn_graph *g);
+int64_t gat_bwd_slot_count(const bgnn_graph *g);
+int launch_gat_backward(bgnn_ctx *ctx, const bgnn_graph *g, const BgnnLayer &L, int C, int ED, const BgnnTapeHeader *hdr,
+                        uint32_t att_stream, const float *xw, const float *asd, const float *grad_out, float *alpha_t, float *dlogit,
+                        float *dasd, float *dVn, float *dxw);
+int launch_gat_edge_param_grads(bgnn_ctx *ctx, const float *dV, const float *att_edge, const float *W_e, int H, int C, int ED,
+                                float *d_att_edge, float *d_W_e);
+int launch_heads_backward(bgnn_ctx *ctx, const bgnn_model *m, const float *hb, const float *dlog, const float *dprob, const float *dconf,
+                          const float *dcorr, const BgnnTapeHeader *hdr, const int64_t *d_m, int64_t max_rows, float *dY2, float *dhid);
 int launch_heads_final(bgnn_ctx *ctx, const bgnn_model *m, const float *hid, int ldh, const int64_t *d_m,
                        int64_t max_rows, float thr_auto, float thr_review, const bgnn_outputs *o);
 

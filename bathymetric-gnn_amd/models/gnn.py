@@ -5,7 +5,8 @@ The module tree and parameter names equal the reference's (and torch_geometric's
 ``model.feature_extractor.mlp[0].in_features`` (read at ``scripts/inference_native.py:147``) works.
 The torch parameters are only the weight container: ``forward`` packs them once into the library's
 blob (``bgnn_model_create``) and runs the hand-written HIP kernels (``bgnn_forward``).  Inference
-(eval) semantics, plus the training-mode FORWARD: batch-statistics BatchNorm and the reference's four dropouts (counter-based draws).
+(eval) semantics, and training: in ``train()`` mode batch-statistics BatchNorm and the reference's four dropouts (counter-based
+draws), and -- for the GAT backbone -- a backward pass on HIP kernels (``bgnn_backward``) that fills every parameter's ``.grad``.
 """
 from __future__ import annotations
 
@@ -276,6 +277,46 @@ class BathymetricGNN(nn.Module):
             parts += [sd[h + ".mlp.0.weight"], sd[h + ".mlp.0.bias"], sd[h + ".mlp.3.weight"], sd[h + ".mlp.3.bias"]]
         return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
 
+    def grad_slots(self, graph_edge_dim: Optional[int] = None):
+        """[(parameter name or None, offset, numel)] covering the blob of ``pack_weights`` -- and the gradient blob of
+        ``bgnn_backward`` -- in order.  None marks the slots that are no parameter: BatchNorm running statistics, and the zero edge
+        weights a model with ``edge_dim=None`` is packed with."""
+        ed = self._edge_width(graph_edge_dim)
+        sd = {k: v for k, v in self.state_dict().items() if v.dtype.is_floating_point}
+        params = dict(self.named_parameters())
+        slots, off = [], 0
+
+        def put(name, n=None):
+            nonlocal off
+            n = sd[name].numel() if n is None else n
+            slots.append((name if name in params else None, off, n))
+            off += n
+        for p in ("feature_extractor.mlp.0", "feature_extractor.mlp.3"):
+            put(p + ".weight"); put(p + ".bias")
+        for l in range(self.num_gnn_layers):
+            c, n = f"gnn.convs.{l}.", f"gnn.norms.{l}.module."
+            if self.gnn_type == "GAT":
+                put(c + "lin.weight"); put(c + "att_src"); put(c + "att_dst")
+                if self.edge_dim is None:
+                    hc = sd[c + "att_src"].numel()
+                    slots += [(None, off, hc), (None, off + hc, hc * ed)]
+                    off += hc + hc * ed
+                else:
+                    put(c + "att_edge"); put(c + "lin_edge.weight")
+                put(c + "bias")
+            elif self.gnn_type == "GCN":
+                put(c + "lin.weight"); put(c + "bias")
+            elif self.gnn_type == "GraphSAGE":
+                put(c + "lin_l.weight"); put(c + "lin_l.bias"); put(c + "lin_r.weight")
+            else:
+                put(c + "nn.0.weight"); put(c + "nn.0.bias"); put(c + "nn.2.weight"); put(c + "nn.2.bias")
+            for k in ("weight", "bias", "running_mean", "running_var"):
+                put(n + k)
+        for h in ["classification_head", "confidence_head"] + (["correction_head"] if self.predict_correction else []):
+            for k in (".mlp.0.weight", ".mlp.0.bias", ".mlp.3.weight", ".mlp.3.bias"):
+                put(h + k)
+        return slots
+
     def _weights_version(self):
         """(storage, version counter) of every parameter and buffer: changes whenever a weight is written or moved.  The LIST of
         tensors is cached -- walking the module tree costs ~0.2 ms, as much as the host side of a whole 50 000-node batch -- beside
@@ -398,7 +439,8 @@ class BathymetricGNN(nn.Module):
         return g, (x, ei, ea)
 
     def _run(self, data, thr_auto: float, thr_review: float, with_flags: bool, want_hidden: bool = False,
-             train: bool = False):
+             train: bool = False, tape_info: Optional[dict] = None):
+        """``tape_info`` (a dict; training mode): run the taped forward and leave in it what ``_TrainStep.backward`` needs."""
         ctx = rt.get_context(self._device_of(data))
         g, keep = self._graph_of(data, ctx)
         if g.num_features != self.in_channels:
@@ -437,9 +479,21 @@ class BathymetricGNN(nn.Module):
             mean = torch.empty(sum(widths), dtype=torch.float32, device=dev)
             var = torch.empty_like(mean)
             dp = self._dropout_spec()
+            tape = None
+            if tape_info is not None:
+                nbytes = int(ctx.lib.bgnn_tape_bytes(model_h, g._handle))
+                if nbytes == 0:                         # no backward pass for this model: the forward runs, backward() raises
+                    tape_info["refusal"] = ctx.lib.bgnn_last_error().decode(errors="replace")
+                else:
+                    tape = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                tape_info.update(tape=tape, ctx=ctx, graph=g, keep=keep, handle=model_h, key=(id(ctx), g.edge_dim))
             ctx.begin()
-            rt.check(ctx.lib.bgnn_forward_train_dropout(ctx.handle, model_h, g._handle, C.byref(dp) if dp is not None else None,
-                                                        rt.ptr(mean), rt.ptr(var), C.byref(o)))
+            if tape is not None:
+                rt.check(ctx.lib.bgnn_forward_train_tape(ctx.handle, model_h, g._handle, C.byref(dp) if dp is not None else None,
+                                                         rt.ptr(mean), rt.ptr(var), C.byref(o), rt.ptr(tape), tape.numel()))
+            else:
+                rt.check(ctx.lib.bgnn_forward_train_dropout(ctx.handle, model_h, g._handle, C.byref(dp) if dp is not None else None,
+                                                            rt.ptr(mean), rt.ptr(var), C.byref(o)))
             ctx.end()
             with torch.no_grad():                       # torch.nn.BatchNorm1d's bookkeeping (momentum None = cumulative average)
                 off = 0
@@ -452,6 +506,8 @@ class BathymetricGNN(nn.Module):
                         bn.running_var.mul_(1.0 - f).add_(var[off:off + w].to(bn.running_var.device), alpha=f)
                     off += w
         elif N > 0:
+            if tape_info is not None:
+                tape_info.update(tape=None, ctx=ctx, graph=g, keep=keep, handle=model_h, key=(id(ctx), g.edge_dim))
             ctx.begin()
             rt.check(ctx.lib.bgnn_forward(ctx.handle, model_h, g._handle, C.c_float(thr_auto), C.c_float(thr_review),
                                           C.byref(o)))
@@ -515,16 +571,89 @@ class BathymetricGNN(nn.Module):
         """class_logits [N,C], class_probs [N,C], predicted_class [N] i64, confidence [N],
         correction [N] (reference :360-408).
 
-        ``eval()``: running statistics, dropout the identity.  ``train()`` (forward only, there is no backward pass
-        here): every BatchNorm layer normalises with the statistics of this batch and moves its running statistics, and
-        the four dropouts of the reference are active with their modules' probabilities (``bgnn_forward_train_dropout``;
-        see ``_dropout_spec`` for the seed)."""
+        ``eval()``: running statistics, dropout the identity.  ``train()``: every BatchNorm layer normalises with the statistics
+        of this batch and moves its running statistics, and the four dropouts of the reference are active with their modules'
+        probabilities (``bgnn_forward_train_dropout``; see ``_dropout_spec`` for the seed).  With autograd recording and a
+        parameter that requires grad, the forward also keeps a tape (``bgnn_forward_train_tape``; same output values) and
+        class_logits / class_probs / confidence / correction carry a ``grad_fn``: ``backward()`` computes every parameter's
+        gradient on the GPU (``bgnn_backward``; GAT backbone only -- other models raise ``NotImplementedError`` there)."""
         if not self.training:
             return self._run(data, 0.85, 0.6, with_flags=False)
-        return self._run(data, 0.85, 0.6, with_flags=False, train=True)
+        if not torch.is_grad_enabled():
+            return self._run(data, 0.85, 0.6, with_flags=False, train=True)
+        slots = [(n, off, k) for n, off, k in self.grad_slots(self._graph_edge_dim(data)) if n is not None]
+        named = dict(self.named_parameters())
+        params = [named[n] for n, _, _ in slots]
+        if not any(p.requires_grad for p in params):
+            return self._run(data, 0.85, 0.6, with_flags=False, train=True)
+        box = {"slots": slots}
+        res = _TrainStep.apply(self, data, box, *params)
+        keys = ["class_logits", "class_probs", "confidence"] + (["correction"] if self.predict_correction else [])
+        out = dict(zip(keys, res))
+        out["predicted_class"] = box.pop("predicted_class")
+        return {k: out[k] for k in ("class_logits", "class_probs", "predicted_class", "confidence", "correction") if k in out}
+
+    def _graph_edge_dim(self, data) -> Optional[int]:
+        if isinstance(data, GraphData):
+            return data.edge_dim
+        ea = getattr(data, "edge_attr", None)
+        return int(ea.shape[1]) if ea is not None and ea.dim() == 2 else 1
 
     def predict(self, data, auto_correct_threshold: float = 0.85, review_threshold: float = 0.6):
         """forward + deployment flags (reference :410-451)."""
         self.eval()
         with torch.no_grad():
             return self._run(data, auto_correct_threshold, review_threshold, with_flags=True)
+
+
+class _TrainStep(torch.autograd.Function):
+    """The training-mode forward of ``BathymetricGNN`` as one autograd node.  Inputs: the model, the graph, a side dict and the
+    model's parameters in ``pack_weights`` order (so that autograd accumulates into each ``param.grad``); outputs: class_logits,
+    class_probs, confidence[, correction].  The tape (one device tensor from torch's caching allocator) is a saved tensor, freed
+    with the graph of the step; the parameters are saved too, so that torch refuses a backward after they were modified in place."""
+
+    @staticmethod
+    def forward(fctx, model, data, box, *params):
+        info = {}
+        fctx.set_materialize_grads(False)               # (an output the loss does not use passes NULL to the kernels)
+        out = model._run(data, 0.85, 0.6, with_flags=False, train=True, tape_info=info)
+        box["predicted_class"] = out["predicted_class"]
+        fctx.model, fctx.info, fctx.slots = model, info, box["slots"]
+        tape = info.get("tape")
+        fctx.has_tape = tape is not None
+        fctx.save_for_backward(*(([tape] if tape is not None else []) + list(params)))
+        res = [out["class_logits"], out["class_probs"], out["confidence"]]
+        if "correction" in out:
+            res.append(out["correction"])
+        return tuple(res)
+
+    @staticmethod
+    def backward(fctx, *grads):
+        info, model = fctx.info, fctx.model
+        if "refusal" in info:
+            raise NotImplementedError(info["refusal"])
+        saved = fctx.saved_tensors
+        tape = saved[0] if fctx.has_tape else None
+        params = saved[1:] if fctx.has_tape else saved
+        ctx, g = info["ctx"], info["graph"]
+        dev = ctx.device
+        gl = [None if x is None else x.detach().to(dev, torch.float32).contiguous() for x in grads]
+        # the packed model the forward ran on, if it is still there (a forward in between may have repacked it; the parameters
+        # are unchanged either way -- torch checked their versions above)
+        ent = (model._native or {}).get(info["key"])
+        model_h = ent[1] if ent is not None and ent[1] is info["handle"] else model.native(ctx, g.edge_dim)
+        n = int(ctx.lib.bgnn_model_weight_count(C.byref(model._desc(g.edge_dim))))
+        blob = torch.empty(n, dtype=torch.float32, device=dev)
+        if tape is None:                                # an empty batch: nothing flows
+            blob.zero_()
+        else:
+            og = rt.OutputGrads()
+            og.class_logits, og.class_probs, og.confidence = (None if t is None else t.data_ptr() for t in gl[:3])
+            og.correction = gl[3].data_ptr() if len(gl) > 3 and gl[3] is not None else None
+            ctx.begin()
+            rt.check(ctx.lib.bgnn_backward(ctx.handle, model_h, g._handle, rt.ptr(tape), C.byref(og), rt.ptr(blob)))
+            ctx.end()
+        res = []
+        for k, ((_, off, cnt), p) in enumerate(zip(fctx.slots, params)):
+            res.append(blob[off:off + cnt].view(p.shape).to(p.device) if fctx.needs_input_grad[3 + k] else None)
+        return (None, None, None, *res)

@@ -1,4 +1,4 @@
-"""ctypes binding of ``libbgnn_hip.so`` (C ABI: ``include/bgnn.h``) and per-GPU contexts.
+"""ctypes binding of ``libbgnn_hip.so`` (C ABI: ``include/bgnn.h``, training part ``include/bgnn_train.h``) and per-GPU contexts.
 
 There is deliberately no CPU fallback: if the library is missing or no GPU is visible the
 compute entry points raise.  PyTorch is used only as the container for device memory and
@@ -26,7 +26,7 @@ EDGE_FEATURE_IDS = {"distance": 0, "depth_difference": 1, "slope": 2}
 EF_ZERO = 3
 
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED = -1, -2, -3, -4
-ABI_VERSION = 6
+ABI_VERSION = 7
 MATRIX_PATHS = {"exact_f32": 0, "bf16x3": 1, "fp16x3": 2, "bf16": 3}
 # every int option of a context (include/bgnn.h, bgnn_ctx_set_option; the "diag_*" / "gemm_diag" ones only take non-zero values in
 # the diagnostic build)
@@ -65,6 +65,11 @@ class Dropout(C.Structure):
     """bgnn_dropout: the four dropout probabilities of a training-mode forward and the seed of its counter-based draws."""
     _fields_ = [("p_extractor", C.c_float), ("p_attention", C.c_float), ("p_features", C.c_float), ("p_heads", C.c_float),
                 ("seed", C.c_uint64)]
+
+
+class OutputGrads(C.Structure):
+    """bgnn_output_grads: device pointers of the gradients of the four differentiable outputs (any may be NULL)."""
+    _fields_ = [("class_logits", C.c_void_p), ("class_probs", C.c_void_p), ("confidence", C.c_void_p), ("correction", C.c_void_p)]
 
 
 # symbol -> (restype, argtypes); every symbol include/bgnn.h declares
@@ -111,6 +116,14 @@ _SIGNATURES = {
                                    C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_train.h declares (the backward pass, ABI 7)
+_TRAIN_SIGNATURES = {
+    "bgnn_tape_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p]),
+    "bgnn_forward_train_tape": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Dropout), C.c_void_p, C.c_void_p,
+                                          C.POINTER(Outputs), C.c_void_p, C.c_size_t]),
+    "bgnn_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OutputGrads), C.c_void_p]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -120,7 +133,7 @@ class BgnnError(RuntimeError):
 
 
 def load_library(path: Optional[str] = None):
-    """dlopen the HIP library and bind every symbol of include/bgnn.h.  Needs no GPU."""
+    """dlopen the HIP library and bind every symbol of include/bgnn.h and include/bgnn_train.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -131,7 +144,7 @@ def load_library(path: Optional[str] = None):
                 f"{p} not found: the HIP library is not built. Run `python __graft_entry__.py` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = C.CDLL(p)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

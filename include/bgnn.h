@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 6
+#define BGNN_ABI_VERSION 7
 
 #define BGNN_OK 0
 #define BGNN_ERR_INVALID (-1)     /* bad argument (-> ValueError in the Python mirror)   */
@@ -248,8 +248,7 @@ int bgnn_heads(bgnn_ctx *ctx, bgnn_model *model, const float *hidden, int64_t n_
 /* BathymetricGNN.forward with the module in train() mode and every dropout probability 0 (models/gnn.py:360-408 with
  * :151-154, :179-186 in training mode): each BatchNorm layer normalises with the mean and the biased variance of THIS
  * batch of nodes instead of its running statistics (torch.nn.BatchNorm1d, which torch_geometric's BatchNorm wraps).
- * Forward only -- there is no backward pass in this library.  Dropout with p > 0 draws from torch's generator and is
- * not reproduced: the host layer refuses that case.
+ * This call keeps no activations; bgnn_forward_train_tape below is the same forward for a later bgnn_backward.
  *   bn_batch_mean, bn_batch_var  DEVICE f32 [sum over layers of the layer width], layer after layer; either may be
  *       NULL.  bn_batch_var is the UNBIASED variance: what the caller blends into running_var
  *       (running = (1 - momentum) * running + momentum * batch), as running_mean with bn_batch_mean.
@@ -281,6 +280,8 @@ typedef struct bgnn_dropout {
 } bgnn_dropout;
 int bgnn_forward_train_dropout(bgnn_ctx *ctx, bgnn_model *model, bgnn_graph *graph, const bgnn_dropout *dropout,
                                float *bn_batch_mean, float *bn_batch_var, const bgnn_outputs *out);
+
+/* The backward pass of the training path (ABI 7) has its own header: include/bgnn_train.h. */
 
 /* BathymetricPipeline._process_tile (models/pipeline.py:243-314) and
  * NativeVRProcessor._extract_results_from_outputs (scripts/inference_native.py:181-204)

@@ -1,0 +1,79 @@
+"""One training step of BathymetricGNN (default shape: GAT, hidden 64, heads 4, 4 layers, edge_dim 3, dropout 0.1) on a batch of
+16 synthetic 256 x 256 V0 tiles, timed by phase on the GPU: the taped training forward, backward (bgnn_backward), weight repack +
+optimizer step (the repack timed on its own: host packing and upload of the blob), and the
+untaped training forward for comparison.  Prints one JSON line (milliseconds, medians over --steps) with the tape's bytes per node.
+
+    python tools/train_step_bench.py [--tiles 16] [--size 256] [--steps 10] [--warmup 3]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tiles", type=int, default=16)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    from bathymetric_gnn_amd import synthetic
+    from bathymetric_gnn_amd.data import GraphBuilder
+    from bathymetric_gnn_amd.models import BathymetricGNN
+    from bathymetric_gnn_amd import runtime as rt
+    dev = torch.device("cuda:0")
+    tiles = [synthetic.synthetic_tile(a.size, a.size, s, "V0") for s in range(a.tiles)]
+    g = GraphBuilder().build_graphs([t[0] for t in tiles], [t[1] for t in tiles], None, [(0.5, 0.5)] * a.tiles)
+    sd = synthetic.synthetic_state_dict(in_channels=7, seed=1234)
+    m = BathymetricGNN(in_channels=7, edge_dim=3, dropout=0.1)
+    m.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
+    m.to(dev).train()
+    opt = torch.optim.SGD(m.parameters(), lr=1e-6)
+    N = g.num_nodes
+    w = torch.randn(N, 3, device=dev)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    rec = {"taped_forward": [], "backward": [], "repack_and_step": [], "untaped_forward": []}
+    for it in range(a.warmup + a.steps):
+        m.dropout_seed = it
+        opt.zero_grad(set_to_none=True)
+        out, t_fwd = timed(lambda: m(g))
+        loss = (out["class_logits"] * w).sum() + out["confidence"].sum() + out["correction"].sum()
+        _, t_bwd = timed(loss.backward)
+        _, t_opt = timed(opt.step)
+        with torch.no_grad():
+            _, t_plain = timed(lambda: m(g))           # untaped training forward (repacks like every training forward)
+        ctx = rt.get_context(dev)
+        t0 = time.perf_counter()
+        m.invalidate_native()                          # the repack on its own: host packing + upload of the blob
+        m.native(ctx, 3)
+        torch.cuda.synchronize()
+        t_pack = (time.perf_counter() - t0) * 1e3
+        if it >= a.warmup:
+            rec["taped_forward"].append(t_fwd)
+            rec["backward"].append(t_bwd)
+            rec["untaped_forward"].append(t_plain)
+            rec["repack_and_step"].append(t_opt + t_pack)
+    tape_bytes = int(ctx.lib.bgnn_tape_bytes(m.native(ctx, 3), g._handle))
+    res = {"metric": "train_step_ms", "nodes": N, "tiles": a.tiles, "size": a.size,
+           **{k: round(float(np.median(v)), 3) for k, v in rec.items()},
+           "tape_bytes_per_node": round(tape_bytes / N, 1), "tape_gb": round(tape_bytes / 1e9, 3)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
