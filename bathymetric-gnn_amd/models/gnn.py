@@ -471,6 +471,8 @@ class BathymetricGNN(nn.Module):
         if hidden is not None:
             o.hidden = hidden.data_ptr()
         model_h = self.native(ctx, g.edge_dim)
+        if tape_info is not None and not (N > 0 and train):   # no tape (an empty batch: backward() hands out zero gradients)
+            tape_info.update(tape=None, ctx=ctx, graph=g, keep=keep, handle=model_h, key=(id(ctx), g.edge_dim))
         if N > 0 and train:
             if N == 1:
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size "
@@ -506,8 +508,6 @@ class BathymetricGNN(nn.Module):
                         bn.running_var.mul_(1.0 - f).add_(var[off:off + w].to(bn.running_var.device), alpha=f)
                     off += w
         elif N > 0:
-            if tape_info is not None:
-                tape_info.update(tape=None, ctx=ctx, graph=g, keep=keep, handle=model_h, key=(id(ctx), g.edge_dim))
             ctx.begin()
             rt.check(ctx.lib.bgnn_forward(ctx.handle, model_h, g._handle, C.c_float(thr_auto), C.c_float(thr_review),
                                           C.byref(o)))

@@ -37,6 +37,9 @@ def _loss_weights(N, nc, seed=7):
 
 
 def _loss(out, w):
+    """The fixed linear form of ``_loss_weights``, or ``w(out)`` when ``w`` is a loss callable."""
+    if callable(w):
+        return w(out)
     s = 0.0
     for k, v in w.items():
         if k in out:
@@ -44,9 +47,13 @@ def _loss(out, w):
     return s
 
 
-def oracle_grads(sd, x, ei, ea, dtype, drop, w, monkeypatch):
-    """{name: gradient} of the fixed loss through the oracle's training-mode forward, and the loss value."""
+def oracle_grads(sd, x, ei, ea, dtype, drop, w, monkeypatch, outputs=None, functional=None):
+    """{name: gradient} of the loss ``w`` (``_loss``) through the oracle's training-mode forward, and the loss value.  A parameter
+    the loss does not reach is absent.  ``outputs``: a dict that receives the forward's outputs (detached) and predicted_class.
+    ``functional``: stands in for ``torch.nn.functional`` inside the oracle (e.g. to give its ReLUs the kernels' patterns)."""
     monkeypatch.setattr(gat_cpu, "_t", _t_keep_graph)
+    if functional is not None:
+        monkeypatch.setattr(gat_cpu, "F", functional)
     P = {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=_is_param(k)) for k, v in sd.items()
          if np.asarray(v).dtype.kind == "f"}
     x = torch.as_tensor(x).to(dtype); ea = torch.as_tensor(ea).to(dtype); ei = torch.as_tensor(ei).to(torch.int64)
@@ -62,6 +69,8 @@ def oracle_grads(sd, x, ei, ea, dtype, drop, w, monkeypatch):
            "confidence": torch.sigmoid(gat_cpu._mlp2(h, P, "confidence_head.mlp.0", "confidence_head.mlp.3", dtype, hm[1])).squeeze(-1)}
     if "correction_head.mlp.0.weight" in P:
         out["correction"] = gat_cpu._mlp2(h, P, "correction_head.mlp.0", "correction_head.mlp.3", dtype, hm[2]).squeeze(-1)
+    if outputs is not None:
+        outputs.update({k: v.detach() for k, v in out.items()}, predicted_class=out["class_probs"].detach().argmax(-1))
     loss = _loss(out, w)
     loss.backward()
     monkeypatch.undo()
