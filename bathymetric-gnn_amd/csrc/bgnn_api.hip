@@ -1323,11 +1323,38 @@ static void tape_layout(const bgnn_model *m, const bgnn_graph *g, TapeLayout &t)
   t.total = off;
 }
 
+// The tape of the plain backbones (GraphSAGE, GIN), laid out as TapeLayout: header at 0, then in this order, each table
+// [row_capacity][hidden] float32 unless said otherwise, every one starting on a 256-byte boundary:
+//   h0, h1;  per layer: SAGE the neighbour mean | GIN s (sum of the neighbours + self) and u (ReLU output of nn.0), then z
+//   (BatchNorm input), hout (layer output), the batch statistics mean and rstd (float64 [hidden]);  hbd [head_hidden_total].
+struct PlainTapeLayout {
+  size_t h0 = 0, h1 = 0;
+  std::vector<size_t> agg, u;               // per layer: SAGE mean / GIN s; GIN u (SAGE: 0)
+  std::vector<size_t> z, hout, mean, rstd;
+  size_t hbd = 0;
+  size_t total = 0;
+};
+
+static void plain_tape_layout(const bgnn_model *m, const bgnn_graph *g, PlainTapeLayout &t) {
+  const size_t rows = (size_t)std::max<int32_t>(g->row_capacity, 0), hid = (size_t)m->desc.hidden;
+  const bool gin = m->desc.gnn_type == BGNN_GNN_GIN;
+  size_t off = 256;
+  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  t.h0 = take(rows * hid * 4); t.h1 = take(rows * hid * 4);
+  for (size_t l = 0; l < m->layers.size(); ++l) {
+    t.agg.push_back(take(rows * hid * 4)); t.u.push_back(gin ? take(rows * hid * 4) : 0);
+    t.z.push_back(take(rows * hid * 4)); t.hout.push_back(take(rows * hid * 4));
+    t.mean.push_back(take(hid * 8)); t.rstd.push_back(take(hid * 8));
+  }
+  t.hbd = take(rows * (size_t)m->head_hidden_total * 4);
+  t.total = off;
+}
+
 // what the backward pass covers (BGNN_ERR_UNSUPPORTED + message otherwise)
 static int backward_supported(const bgnn_model *m) {
   const bgnn_model_desc &d = m->desc;
-  if (d.gnn_type != BGNN_GNN_GAT) {
-    set_error("backward pass: only the GAT backbone has one (gnn_type=%s)", d.gnn_type == BGNN_GNN_GCN ? "GCN" : d.gnn_type == BGNN_GNN_SAGE ? "GraphSAGE" : "GIN");
+  if (d.gnn_type == BGNN_GNN_GCN) {
+    set_error("backward pass: the GCN backbone has none (the GAT, GraphSAGE and GIN backbones have one)");
     return BGNN_ERR_UNSUPPORTED;
   }
   if (m->padded) {
@@ -1344,12 +1371,20 @@ static int backward_supported(const bgnn_model *m) {
   return BGNN_OK;
 }
 
+// the tape layout of a model whose backward_supported() holds: GAT -> tl, GraphSAGE / GIN -> pl; returns its total bytes
+static size_t any_tape_layout(const bgnn_model *m, const bgnn_graph *g, TapeLayout &tl, PlainTapeLayout &pl) {
+  if (m->desc.gnn_type == BGNN_GNN_GAT) { tape_layout(m, g, tl); return tl.total; }
+  plain_tape_layout(m, g, pl);
+  return pl.total;
+}
+
 // training-mode forward: BatchNorm statistics of this batch, written layer by layer ([sum of layer widths] each)
 struct TrainOut {
   float *mean, *var_unbiased;
   const bgnn_dropout *dp = nullptr;      // active dropout (bgnn_forward_train_dropout)
-  char *tape = nullptr;                  // taped forward: saved activations (TapeLayout)
+  char *tape = nullptr;                  // taped forward: saved activations (TapeLayout: GAT, PlainTapeLayout: GraphSAGE / GIN)
   const TapeLayout *tl = nullptr;
+  const PlainTapeLayout *ptl = nullptr;
 };
 
 static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_auto, float thr_review,
@@ -1386,6 +1421,7 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
   // taped forward: the saved activations are COPIES of the forward's own tables (outputs and statistics stay bit-identical)
   char *tape = tr ? tr->tape : nullptr;
   const TapeLayout *tl = tr ? tr->tl : nullptr;
+  const PlainTapeLayout *ptl = tr ? tr->ptl : nullptr;
   auto save = [&](size_t off, const void *src, size_t bytes) -> int {
     BGNN_HIP_CHECK(hipMemcpyAsync(tape + off, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return BGNN_OK;
@@ -1398,12 +1434,16 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
   };
   auto batch_norm = [&](float *z, const BgnnLayer &L, int relu) {          // z [rows][L.width], in place (256 columns per launch)
     int rc = BGNN_OK;
+    double *s_mean = nullptr, *s_rstd = nullptr;    // taped: the statistics go to the tape as well
+    if (tape) {
+      s_mean = (double *)(tape + (tl ? tl->mean : ptl->mean)[bn_layer]);
+      s_rstd = (double *)(tape + (tl ? tl->rstd : ptl->rstd)[bn_layer]);
+    }
     for (int c0 = 0; c0 < L.width && rc == BGNN_OK; c0 += 256) {
       const int w = std::min(256, L.width - c0);
       rc = launch_bn_train(ctx, z + c0, L.width, w, rows, dm, L.bn_w + c0, L.bn_b + c0, d.bn_eps, relu, bnws,
                            tr->mean ? tr->mean + tr_off + c0 : nullptr, tr->var_unbiased ? tr->var_unbiased + tr_off + c0 : nullptr,
-                           tape ? (double *)(tape + tl->mean[bn_layer]) + c0 : nullptr,
-                           tape ? (double *)(tape + tl->rstd[bn_layer]) + c0 : nullptr);
+                           s_mean ? s_mean + c0 : nullptr, s_rstd ? s_rstd + c0 : nullptr);
     }
     tr_off += (size_t)L.width;
     ++bn_layer;
@@ -1430,6 +1470,11 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
     BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, 8, hid, 1));
     if (dp) BGNN_TRY(drop(Y, hid, dp->p_extractor, 1));
     BGNN_TRY(launch_gemm_f32(ctx, Y, hid, m->fe_W1t, m->fe_b1, X, hid, dm, rows, hid, hid, 0));
+    const size_t tab = (size_t)rows * hid * sizeof(float);   // (bytes of one [rows][hid] table of the tape)
+    if (ptl) {
+      BGNN_TRY(save(ptl->h0, Y, tab));
+      BGNN_TRY(save(ptl->h1, X, tab));
+    }
     float *dinv = asdX;
     if (d.gnn_type == BGNN_GNN_GCN) BGNN_TRY(launch_degree_inv_sqrt(ctx, g, dinv));
     const size_t nl = m->layers.size();
@@ -1464,19 +1509,28 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
       } else if (d.gnn_type == BGNN_GNN_SAGE) {       // [mean_j x_j | x_i] @ [lin_l ; lin_r]^T (BatchNorm folded) + bias, ReLU
         BGNN_TRY(launch_neighbor_reduce(ctx, g, 2, X, hid, nullptr, nullptr, nullptr, 0, Y, 2 * hid, Y + hid));
         if (tr) {
+          if (ptl)   // the mean half of the [mean | x] rows
+            BGNN_HIP_CHECK(hipMemcpy2DAsync(tape + ptl->agg[l], (size_t)hid * sizeof(float), Y, (size_t)2 * hid * sizeof(float),
+                                            (size_t)hid * sizeof(float), (size_t)rows, hipMemcpyDeviceToDevice, ctx->stream));
           BGNN_TRY(launch_gemm_f32(ctx, Y, 2 * hid, L.tr_Wt, L.tr_bias, X, hid, dm, rows, 2 * hid, hid, 0));
+          if (ptl) BGNN_TRY(save(ptl->z[l], X, tab));
           BGNN_TRY(batch_norm(X, L, relu));
           if (dp && relu) BGNN_TRY(drop(X, hid, dp->p_features, 64 + (uint32_t)l));
+          if (ptl) BGNN_TRY(save(ptl->hout[l], X, tab));
         } else {
           BGNN_TRY(launch_gemm_f32(ctx, Y, 2 * hid, L.Wt, L.b2, X, hid, dm, rows, 2 * hid, hid, relu));
         }
       } else {                                        // GIN: nn(sum_j x_j + x_i), nn = Linear ReLU Linear; BatchNorm; ReLU
         BGNN_TRY(launch_neighbor_reduce(ctx, g, 3, X, hid, nullptr, nullptr, nullptr, 0, Y, hid, nullptr));
+        if (ptl) BGNN_TRY(save(ptl->agg[l], Y, tab));
         BGNN_TRY(launch_gemm_f32(ctx, Y, hid, L.Wt, L.b1, X, hid, dm, rows, hid, hid, 1));
+        if (ptl) BGNN_TRY(save(ptl->u[l], X, tab));
         if (tr) {
           BGNN_TRY(launch_gemm_f32(ctx, X, hid, L.tr_Wt, L.tr_bias, Y, hid, dm, rows, hid, hid, 0));
+          if (ptl) BGNN_TRY(save(ptl->z[l], Y, tab));
           BGNN_TRY(batch_norm(Y, L, relu));
           if (dp && relu) BGNN_TRY(drop(Y, hid, dp->p_features, 64 + (uint32_t)l));
+          if (ptl) BGNN_TRY(save(ptl->hout[l], Y, tab));
         } else {
           BGNN_TRY(launch_gemm_f32(ctx, X, hid, L.Wt2, L.b2, Y, hid, dm, rows, hid, hid, relu));
         }
@@ -1593,7 +1647,7 @@ static int forward_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_a
                            m->head_hidden_total, 1));
   if (dp && dp->p_heads > 0.0f)      // (the draw is indexed over the heads' own units; the table may carry pad columns up to a multiple of 32)
     BGNN_TRY(launch_dropout(ctx, hidb, head_count(&d) * (hid / 2), m->head_hidden_total, dm, rows, make_drop_spec(dp->p_heads, dp->seed, 2)));
-  if (tape) BGNN_TRY(save(tl->hbd, hidb, (size_t)rows * m->head_hidden_total * sizeof(float)));
+  if (tape) BGNN_TRY(save(tl ? tl->hbd : ptl->hbd, hidb, (size_t)rows * m->head_hidden_total * sizeof(float)));
   BGNN_TRY(launch_heads_final(ctx, m, hidb, m->head_hidden_total, dm, rows, thr_auto, thr_review, o));
   return BGNN_OK;
 }
@@ -1699,11 +1753,12 @@ static int forward_train_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const
   BGNN_REQUIRE(c[0] != 1, "Expected more than 1 value per channel when training, got input size [1, %d]", m->layers[0].width);
   TrainOut tr{bn_batch_mean, bn_batch_var, dropout};
   TapeLayout tl;
+  PlainTapeLayout pl;
   if (tape) {
     BGNN_TRY(backward_supported(m));
-    tape_layout(m, g, tl);
-    BGNN_REQUIRE(tape_bytes >= tl.total, "bgnn_forward_train_tape: the tape has %zu bytes, this model and graph need %zu (bgnn_tape_bytes)",
-                 tape_bytes, tl.total);
+    const size_t need = any_tape_layout(m, g, tl, pl);
+    BGNN_REQUIRE(tape_bytes >= need, "bgnn_forward_train_tape: the tape has %zu bytes, this model and graph need %zu (bgnn_tape_bytes)",
+                 tape_bytes, need);
     BgnnTapeHeader h{};
     const bgnn_dropout *dp = dropout;
     h.s_ext = dp ? make_drop_spec(dp->p_extractor, dp->seed, 1).scale : 1.0f;
@@ -1711,7 +1766,9 @@ static int forward_train_impl(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const
     h.s_heads = dp ? make_drop_spec(dp->p_heads, dp->seed, 2).scale : 1.0f;
     h.att = dp ? make_drop_spec(dp->p_attention, dp->seed, 16) : DropSpec{};
     BGNN_TRY(ctx_upload(ctx, &h, sizeof(h), tape));
-    tr.tape = (char *)tape; tr.tl = &tl;
+    tr.tape = (char *)tape;
+    if (m->desc.gnn_type == BGNN_GNN_GAT) tr.tl = &tl;
+    else tr.ptl = &pl;
   }
   return forward_impl(ctx, m, g, 0.85f, 0.6f, o, nullptr, &tr);
 }
@@ -1720,8 +1777,8 @@ size_t bgnn_tape_bytes(const bgnn_model *m, const bgnn_graph *g) {
   if (!m || !g) { set_error("bgnn_tape_bytes: NULL argument"); return 0; }
   if (backward_supported(m) != BGNN_OK) return 0;
   TapeLayout tl;
-  tape_layout(m, g, tl);
-  return tl.total;
+  PlainTapeLayout pl;
+  return any_tape_layout(m, g, tl, pl);
 }
 
 int bgnn_forward_train_tape(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const bgnn_dropout *dropout, float *bn_batch_mean,
@@ -1732,9 +1789,14 @@ int bgnn_forward_train_tape(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const b
 
 // ---- backward --------------------------------------------------------------------------------------------------------------
 // Offsets of every tensor of the weight blob (bgnn_model_weight_count order) -- of the gradient blob as well.
+// Layer slots: GAT  W = lin.weight, as / ad / ae = att_src / att_dst / att_edge, We = lin_edge.weight, bias;
+//              GCN  W = lin.weight, bias;  GraphSAGE  W = lin_l.weight, bias = lin_l.bias, W2 = lin_r.weight;
+//              GIN  W = nn.0.weight, b1 = nn.0.bias, W2 = nn.2.weight, bias = nn.2.bias;
+// then every backbone's BatchNorm weight / bias (and its two running-statistics slots, which get no gradient).  Slots a backbone
+// does not have stay 0.
 struct GradOffsets {
   size_t fe_W0, fe_b0, fe_W1, fe_b1;
-  struct Layer { size_t W, as, ad, ae, We, bias, bn_w, bn_b; };
+  struct Layer { size_t W, as, ad, ae, We, bias, bn_w, bn_b, W2, b1; };
   std::vector<Layer> layers;
   size_t hd_W0[3], hd_b0[3], hd_W1[3], hd_b1[3];
 };
@@ -1743,10 +1805,19 @@ static void grad_offsets(const bgnn_model_desc &d, GradOffsets &g) {
   const size_t hid = d.hidden, hh = hid / 2;
   size_t o = 0;
   g.fe_W0 = o; o += hid * d.in_channels; g.fe_b0 = o; o += hid; g.fe_W1 = o; o += hid * hid; g.fe_b1 = o; o += hid;
-  for (int l = 0; l < d.num_layers; ++l) {
+  for (int l = 0; l < d.num_layers && d.gnn_type != BGNN_GNN_GAT; ++l) {      // (every plain layer maps hidden -> hidden)
+    GradOffsets::Layer L{};
+    L.W = o; o += hid * hid;
+    if (d.gnn_type == BGNN_GNN_GCN) { L.bias = o; o += hid; }
+    else if (d.gnn_type == BGNN_GNN_SAGE) { L.bias = o; o += hid; L.W2 = o; o += hid * hid; }
+    else { L.b1 = o; o += hid; L.W2 = o; o += hid * hid; L.bias = o; o += hid; }
+    L.bn_w = o; o += hid; L.bn_b = o; o += hid; o += 2 * hid;
+    g.layers.push_back(L);
+  }
+  for (int l = 0; l < d.num_layers && d.gnn_type == BGNN_GNN_GAT; ++l) {
     const bool last = l == d.num_layers - 1;
     const size_t H = last ? 1 : d.heads, D = l == 0 ? hid : hid * d.heads, HC = H * hid, W = last ? hid : HC;
-    GradOffsets::Layer L;
+    GradOffsets::Layer L{};
     L.W = o; o += HC * D; L.as = o; o += HC; L.ad = o; o += HC; L.ae = o; o += HC; L.We = o; o += HC * d.edge_dim;
     L.bias = o; o += W; L.bn_w = o; o += W; L.bn_b = o; o += W; o += 2 * W;      // (running_mean / running_var: no gradient)
     g.layers.push_back(L);
@@ -1767,9 +1838,13 @@ int bgnn_backward(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const void *tape,
   BGNN_HIP_CHECK(hipMemsetAsync(grad_weights, 0, nw * sizeof(float), ctx->stream));   // (running statistics: 0)
   const int64_t rows = g->row_capacity;
   if (rows <= 0) return BGNN_OK;
-  BGNN_REQUIRE(g->F == d.in_channels && g->ED == d.edge_dim, "bgnn_backward: graph does not fit the model");
+  const bool gat = d.gnn_type == BGNN_GNN_GAT;
+  BGNN_REQUIRE(g->F == d.in_channels && (!gat || g->ED == d.edge_dim), "bgnn_backward: graph does not fit the model");
   TapeLayout tl;
-  tape_layout(m, g, tl);
+  PlainTapeLayout pl;
+  any_tape_layout(m, g, tl, pl);
+  const size_t t_h0 = gat ? tl.h0 : pl.h0, t_hbd = gat ? tl.hbd : pl.hbd;
+  const std::vector<size_t> &t_hout = gat ? tl.hout : pl.hout;
   GradOffsets go;
   grad_offsets(d, go);
   const char *tp = (const char *)tape;
@@ -1781,40 +1856,75 @@ int bgnn_backward(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const void *tape,
   const int64_t *dm = g->d_counts;
   int Hmax = 1;
   for (const BgnnLayer &Ly : m->layers) Hmax = std::max(Hmax, Ly.heads);
-  const int64_t slots = gat_bwd_slot_count(g);
+  const int64_t slots = gat ? gat_bwd_slot_count(g) : 0;
   // scratch (context slot 6): two row tables for the running gradient, dxw, d(attention dots), per-node dV shares, the per-slot
-  // alpha~ / dlogit tables, the heads' gradients, dV, then the reduction workspaces
+  // alpha~ / dlogit tables, the heads' gradients, dV, then the reduction workspaces; the plain backbones use the three row tables
+  // (hidden wide) and a per-node 1 / in-degree in place of the attention tables
+  const size_t RW = gat ? 256 : (size_t)hid;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t oG0 = take((size_t)rows * 256 * 4), oG1 = take((size_t)rows * 256 * 4), oDXW = take((size_t)rows * 256 * 4);
-  const size_t oDASD = take((size_t)rows * 2 * Hmax * 4), oDVN = take((size_t)rows * Hmax * ED * 4);
+  const size_t oG0 = take((size_t)rows * RW * 4), oG1 = take((size_t)rows * RW * 4), oDXW = take((size_t)rows * RW * 4);
+  const size_t oDASD = take(gat ? (size_t)rows * 2 * Hmax * 4 : 0), oDVN = take(gat ? (size_t)rows * Hmax * ED * 4 : 0);
   const size_t oAL = take((size_t)slots * Hmax * 4), oDL = take((size_t)slots * Hmax * 4);
   const size_t oDY2 = take((size_t)rows * n2 * 4), oDHID = take((size_t)rows * HT * 4), oDV = take(64 * 4);
   const size_t oWG = take(wgrad_workspace_bytes()), oCS = take(colsum_workspace_bytes()), oBN = take(bn_backward_workspace_bytes(256));
+  const size_t oCI = take(gat ? 0 : (size_t)rows * 4);
   void *ws;
   BGNN_TRY(ctx_workspace(ctx, 6, off, &ws));
   char *wb = (char *)ws;
   float *G0 = (float *)(wb + oG0), *G1 = (float *)(wb + oG1), *DXW = (float *)(wb + oDXW), *DASD = (float *)(wb + oDASD);
   float *DVN = (float *)(wb + oDVN), *AL = (float *)(wb + oAL), *DL = (float *)(wb + oDL), *DY2 = (float *)(wb + oDY2);
-  float *DHID = (float *)(wb + oDHID), *DV = (float *)(wb + oDV);
+  float *DHID = (float *)(wb + oDHID), *DV = (float *)(wb + oDV), *CINV = (float *)(wb + oCI);
   void *WG = wb + oWG, *CS = wb + oCS, *BNW = wb + oBN;
   float *gw = grad_weights;
   const float *raw = m->raw;
 
   // heads (gnn.py:392-406): second layers, then the first layers, then dL/d(backbone output) = dhid . W0 (stacked)
-  BGNN_TRY(launch_heads_backward(ctx, m, T(tl.hbd), gin->class_logits, gin->class_probs, gin->confidence,
+  BGNN_TRY(launch_heads_backward(ctx, m, T(t_hbd), gin->class_logits, gin->class_probs, gin->confidence,
                                  d.predict_correction ? gin->correction : nullptr, hdr, dm, rows, DY2, DHID));
-  const float *hL = T(tl.hout[L - 1]);
+  const float *hL = T(t_hout[L - 1]);
   for (int k = 0; k < nh; ++k) {
     const int nout = k == 0 ? nc : 1, col = k == 0 ? 0 : nc + k - 1;
-    BGNN_TRY(launch_wgrad(ctx, DY2 + col, n2, T(tl.hbd) + k * hh, HT, dm, rows, nout, hh, gw + go.hd_W1[k], hh, WG));
+    BGNN_TRY(launch_wgrad(ctx, DY2 + col, n2, T(t_hbd) + k * hh, HT, dm, rows, nout, hh, gw + go.hd_W1[k], hh, WG));
     BGNN_TRY(launch_colsum(ctx, DY2 + col, n2, nout, nullptr, 0, 0, 1, dm, rows, gw + go.hd_b1[k], CS));
     BGNN_TRY(launch_wgrad(ctx, DHID + k * hh, HT, hL, hid, dm, rows, hh, hid, gw + go.hd_W0[k], hid, WG));
     BGNN_TRY(launch_colsum(ctx, DHID + k * hh, HT, hh, nullptr, 0, 0, 1, dm, rows, gw + go.hd_b0[k], CS));
   }
   BGNN_TRY(launch_gemm_f32(ctx, DHID, HT, m->hd_W0, nullptr, G0, hid, dm, rows, HT, hid, 0));
+  // GraphSAGE / GIN layers, last to first (every one hidden -> hidden).  Invariant: G0 = dL/d(output of layer l) [rows][hid]
+  if (!gat && d.gnn_type == BGNN_GNN_SAGE) BGNN_TRY(launch_plain_inv_count(ctx, g, CINV));
+  for (int l = L - 1; l >= 0 && !gat; --l) {
+    const BgnnLayer &Ly = m->layers[l];
+    const GradOffsets::Layer &O = go.layers[l];
+    const int relu = l + 1 < L ? 1 : 0;
+    const float *hin = l > 0 ? T(pl.hout[l - 1]) : T(pl.h1);
+    // BatchNorm (+ ReLU + feature dropout) backward: G0 becomes dL/dz; then the bias of the layer's last map
+    BGNN_TRY(launch_bn_backward(ctx, G0, relu ? T(pl.hout[l]) : nullptr, T(pl.z[l]), hid, (const double *)T(pl.mean[l]),
+                                (const double *)T(pl.rstd[l]), Ly.bn_w, relu, s_feat, dm, rows, BNW, gw + O.bn_w, gw + O.bn_b));
+    BGNN_TRY(launch_colsum(ctx, G0, hid, hid, nullptr, 0, 0, 1, dm, rows, gw + O.bias, CS));
+    if (d.gnn_type == BGNN_GNN_SAGE) {
+      // z = lin_l(mean) + lin_r(h): d lin_l.W = G^T mean, d lin_r.W = G^T h; dmean = G W_l (DXW), root = G W_r (G1)
+      BGNN_TRY(launch_wgrad(ctx, G0, hid, T(pl.agg[l]), hid, dm, rows, hid, hid, gw + O.W, hid, WG));
+      BGNN_TRY(launch_wgrad(ctx, G0, hid, hin, hid, dm, rows, hid, hid, gw + O.W2, hid, WG));
+      BGNN_TRY(launch_gemm_f32(ctx, G0, hid, raw + O.W, nullptr, DXW, hid, dm, rows, hid, hid, 0));
+      BGNN_TRY(launch_gemm_f32(ctx, G0, hid, raw + O.W2, nullptr, G1, hid, dm, rows, hid, hid, 0));
+      // dh_j = root_j + sum over the out-edges j -> i of dmean_i / max(cnt_i, 1)
+      BGNN_TRY(launch_plain_bwd_aggregate(ctx, g, 2, hid, G1, DXW, CINV, G0));
+    } else {
+      // z = nn.2(u), u = ReLU(nn.0(s)): d nn.2.W = G^T u; du = (G W_2) [u > 0] (DXW); d nn.0.b = sum du, d nn.0.W = du^T s;
+      // ds = du W_1 (G1)
+      BGNN_TRY(launch_wgrad(ctx, G0, hid, T(pl.u[l]), hid, dm, rows, hid, hid, gw + O.W2, hid, WG));
+      BGNN_TRY(launch_gemm_f32(ctx, G0, hid, raw + O.W2, nullptr, DXW, hid, dm, rows, hid, hid, 0));
+      BGNN_TRY(launch_relu_drop_bwd(ctx, DXW, hid, T(pl.u[l]), hid, hid, dm, rows, m->ones));
+      BGNN_TRY(launch_colsum(ctx, DXW, hid, hid, nullptr, 0, 0, 1, dm, rows, gw + O.b1, CS));
+      BGNN_TRY(launch_wgrad(ctx, DXW, hid, T(pl.agg[l]), hid, dm, rows, hid, hid, gw + O.W, hid, WG));
+      BGNN_TRY(launch_gemm_f32(ctx, DXW, hid, raw + O.W, nullptr, G1, hid, dm, rows, hid, hid, 0));
+      // s_i = sum_{j -> i} h_j + h_i: dh_j = ds_j + sum over the out-edges j -> i of ds_i
+      BGNN_TRY(launch_plain_bwd_aggregate(ctx, g, 3, hid, G1, G1, nullptr, G0));
+    }
+  }
   // GAT layers, last to first.  Invariant: G0 = dL/d(output of layer l) [rows][width]
-  for (int l = L - 1; l >= 0; --l) {
+  for (int l = L - 1; l >= 0 && gat; --l) {
     const BgnnLayer &Ly = m->layers[l];
     const GradOffsets::Layer &O = go.layers[l];
     const int W = Ly.width, H = Ly.heads, HC = H * hid, D = Ly.d_in;
@@ -1836,10 +1946,10 @@ int bgnn_backward(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const void *tape,
     std::swap(G0, G1);
   }
   // feature extractor (gnn.py:386): Linear, ReLU, Dropout, Linear
-  BGNN_TRY(launch_wgrad(ctx, G0, hid, T(tl.h0), hid, dm, rows, hid, hid, gw + go.fe_W1, hid, WG));
+  BGNN_TRY(launch_wgrad(ctx, G0, hid, T(t_h0), hid, dm, rows, hid, hid, gw + go.fe_W1, hid, WG));
   BGNN_TRY(launch_colsum(ctx, G0, hid, hid, nullptr, 0, 0, 1, dm, rows, gw + go.fe_b1, CS));
   BGNN_TRY(launch_gemm_f32(ctx, G0, hid, raw + go.fe_W1, nullptr, G1, hid, dm, rows, hid, hid, 0));
-  BGNN_TRY(launch_relu_drop_bwd(ctx, G1, hid, T(tl.h0), hid, hid, dm, rows, s_ext));
+  BGNN_TRY(launch_relu_drop_bwd(ctx, G1, hid, T(t_h0), hid, hid, dm, rows, s_ext));
   BGNN_TRY(launch_wgrad(ctx, G1, hid, g->d_x8, 8, dm, rows, hid, d.in_channels, gw + go.fe_W0, d.in_channels, WG));
   BGNN_TRY(launch_colsum(ctx, G1, hid, hid, nullptr, 0, 0, 1, dm, rows, gw + go.fe_b0, CS));
   return BGNN_OK;

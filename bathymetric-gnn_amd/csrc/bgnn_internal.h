@@ -381,6 +381,11 @@ int launch_gat_edge_param_grads(bgnn_ctx *ctx, const float *dV, const float *att
                                 float *d_att_edge, float *d_W_e);
 int launch_heads_backward(bgnn_ctx *ctx, const bgnn_model *m, const float *hb, const float *dlog, const float *dprob, const float *dconf,
                           const float *dcorr, const BgnnTapeHeader *hdr, const int64_t *d_m, int64_t max_rows, float *dY2, float *dhid);
+// GraphSAGE / GIN aggregate backward (plain_backward.hip): cinv[i] = 1 / max(in-edges of i, 1); then per node j
+// out_j = root_j + sum over the out-edges j -> i of c_i grad_i, c_i = cinv[i] (mode 2, mean) or 1 (mode 3, sum); out != grad
+int launch_plain_inv_count(bgnn_ctx *ctx, const bgnn_graph *g, float *cinv);
+int launch_plain_bwd_aggregate(bgnn_ctx *ctx, const bgnn_graph *g, int mode, int D, const float *root, const float *grad,
+                               const float *cinv, float *out);
 int launch_heads_final(bgnn_ctx *ctx, const bgnn_model *m, const float *hid, int ldh, const int64_t *d_m,
                        int64_t max_rows, float thr_auto, float thr_review, const bgnn_outputs *o);
 

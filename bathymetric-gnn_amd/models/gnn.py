@@ -6,7 +6,8 @@ The module tree and parameter names equal the reference's (and torch_geometric's
 The torch parameters are only the weight container: ``forward`` packs them once into the library's
 blob (``bgnn_model_create``) and runs the hand-written HIP kernels (``bgnn_forward``).  Inference
 (eval) semantics, and training: in ``train()`` mode batch-statistics BatchNorm and the reference's four dropouts (counter-based
-draws), and -- for the GAT backbone -- a backward pass on HIP kernels (``bgnn_backward``) that fills every parameter's ``.grad``.
+draws), and -- for the GAT, GraphSAGE and GIN backbones -- a backward pass on HIP kernels (``bgnn_backward``) that fills every
+parameter's ``.grad``.
 """
 from __future__ import annotations
 
@@ -576,7 +577,8 @@ class BathymetricGNN(nn.Module):
         probabilities (``bgnn_forward_train_dropout``; see ``_dropout_spec`` for the seed).  With autograd recording and a
         parameter that requires grad, the forward also keeps a tape (``bgnn_forward_train_tape``; same output values) and
         class_logits / class_probs / confidence / correction carry a ``grad_fn``: ``backward()`` computes every parameter's
-        gradient on the GPU (``bgnn_backward``; GAT backbone only -- other models raise ``NotImplementedError`` there)."""
+        gradient on the GPU (``bgnn_backward``; GAT, GraphSAGE and GIN backbones -- a GCN model raises ``NotImplementedError``
+        there)."""
         if not self.training:
             return self._run(data, 0.85, 0.6, with_flags=False)
         if not torch.is_grad_enabled():

@@ -19,13 +19,16 @@ extern "C" {
  * A taped training forward saves the activations the backward needs in a caller-owned DEVICE buffer (the tape); bgnn_backward
  * turns the gradients of the outputs into the gradient of every weight.  Covered: the GAT backbone, hidden 32 / 64 / 128,
  * power-of-two heads with heads * hidden <= 256, any layer count, 1..4 edge features, stencil and foreign (bgnn_graph_from_edges)
- * graphs, exact float32.  Anything else -> BGNN_ERR_UNSUPPORTED with a message naming the limit.  All sums are deterministic
- * (no float atomics): two backward calls on one tape give bit-identical gradients.
+ * graphs; the GraphSAGE and GIN backbones, hidden 32 / 64 / 128, any layer count, every graph their training forward accepts
+ * (stencil graphs, foreign graphs without explicit self loops); exact float32.  Anything else (GCN, zero-padded shapes, wider GAT
+ * layers) -> BGNN_ERR_UNSUPPORTED with a message naming the limit.  All sums are deterministic (no float atomics): two backward
+ * calls on one tape give bit-identical gradients.
  *
  * bgnn_tape_bytes: bytes of the tape for this model and graph (0 and bgnn_last_error() set when the model has no backward pass).
- *   Per node (rows of the graph): 4 * (2 hid + sum over layers of (heads_l hid + 2 heads_l + 2 width_l) + head units) bytes, plus
- *   16 bytes per channel of statistics -- 11 KB per node for the default shape (hidden 64, heads 4, 4 layers, edge_dim 3), about
- *   11.5 GB for 16 tiles of 256 x 256 (a count of the tables, not a measurement).
+ *   Per node (rows of the graph), GAT: 4 * (2 hid + sum over layers of (heads_l hid + 2 heads_l + 2 width_l) + head units) bytes,
+ *   plus 16 bytes per channel of statistics -- 11 KB per node for the default shape (hidden 64, heads 4, 4 layers, edge_dim 3),
+ *   about 11.5 GB for 16 tiles of 256 x 256.  GraphSAGE / GIN: 4 * (2 hid + layers * k hid + head units) bytes, k = 3 (SAGE: mean,
+ *   z, output) or 4 (GIN: s, u, z, output) -- 3.9 / 4.9 KB per node at hidden 64, 4 layers (counts of the tables, not measurements).
  * bgnn_forward_train_tape: bgnn_forward_train_dropout (same outputs and statistics, bit for bit) that also copies its activations
  *   into `tape` (tape_bytes >= bgnn_tape_bytes).  The tape stays valid until the caller frees it; several tapes may be live.
  * bgnn_backward: reads the tape of the same model and graph (neither changed since) and the output gradients `gin` (DEVICE, each

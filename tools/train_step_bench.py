@@ -1,9 +1,9 @@
-"""One training step of BathymetricGNN (default shape: GAT, hidden 64, heads 4, 4 layers, edge_dim 3, dropout 0.1) on a batch of
-16 synthetic 256 x 256 V0 tiles, timed by phase on the GPU: the taped training forward, backward (bgnn_backward), weight repack +
+"""One training step of BathymetricGNN (default shape: GAT, hidden 64, heads 4, 4 layers, edge_dim 3, dropout 0.1; --gnn-type picks
+GraphSAGE or GIN instead) on a batch of 16 synthetic 256 x 256 V0 tiles, timed by phase on the GPU: the taped training forward, backward (bgnn_backward), weight repack +
 optimizer step (the repack timed on its own: host packing and upload of the blob), and the
 untaped training forward for comparison.  Prints one JSON line (milliseconds, medians over --steps) with the tape's bytes per node.
 
-    python tools/train_step_bench.py [--tiles 16] [--size 256] [--steps 10] [--warmup 3]
+    python tools/train_step_bench.py [--gnn-type GAT|GraphSAGE|GIN] [--tiles 16] [--size 256] [--steps 10] [--warmup 3]
 """
 import argparse
 import json
@@ -20,6 +20,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gnn-type", default="GAT", choices=["GAT", "GraphSAGE", "GIN"])
     ap.add_argument("--tiles", type=int, default=16)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--steps", type=int, default=10)
@@ -32,8 +33,8 @@ def main():
     dev = torch.device("cuda:0")
     tiles = [synthetic.synthetic_tile(a.size, a.size, s, "V0") for s in range(a.tiles)]
     g = GraphBuilder().build_graphs([t[0] for t in tiles], [t[1] for t in tiles], None, [(0.5, 0.5)] * a.tiles)
-    sd = synthetic.synthetic_state_dict(in_channels=7, seed=1234)
-    m = BathymetricGNN(in_channels=7, edge_dim=3, dropout=0.1)
+    sd = synthetic.synthetic_state_dict(in_channels=7, seed=1234, gnn_type=a.gnn_type)
+    m = BathymetricGNN(in_channels=7, edge_dim=3, dropout=0.1, gnn_type=a.gnn_type)
     m.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
     m.to(dev).train()
     opt = torch.optim.SGD(m.parameters(), lr=1e-6)
@@ -69,7 +70,7 @@ def main():
             rec["untaped_forward"].append(t_plain)
             rec["repack_and_step"].append(t_opt + t_pack)
     tape_bytes = int(ctx.lib.bgnn_tape_bytes(m.native(ctx, 3), g._handle))
-    res = {"metric": "train_step_ms", "nodes": N, "tiles": a.tiles, "size": a.size,
+    res = {"metric": "train_step_ms", "gnn_type": a.gnn_type, "nodes": N, "tiles": a.tiles, "size": a.size,
            **{k: round(float(np.median(v)), 3) for k, v in rec.items()},
            "tape_bytes_per_node": round(tape_bytes / N, 1), "tape_gb": round(tape_bytes / 1e9, 3)}
     print(json.dumps(res))
