@@ -3,7 +3,7 @@
 from .graph_construction import GraphBuilder, GraphData, Data
 from .grid import BathymetricGrid
 from .tiling import Tile, TileSpec, TileManager, TileMerger
-from .vr_bag import RefinementGrid, VRBagHandler, VRBagWriter, SRBagHandler, SRBagWriter, detect_bag_type
+from .vr_bag import RefinementGrid, VRBagHandler, VRBagWriter, SRBagHandler, SRBagWriter, SidecarBuilder, detect_bag_type
 
 __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "TileSpec", "TileManager", "TileMerger",
-           "RefinementGrid", "VRBagHandler", "VRBagWriter", "SRBagHandler", "SRBagWriter", "detect_bag_type"]
+           "RefinementGrid", "VRBagHandler", "VRBagWriter", "SRBagHandler", "SRBagWriter", "SidecarBuilder", "detect_bag_type"]

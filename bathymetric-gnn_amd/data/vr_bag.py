@@ -5,8 +5,13 @@ base grid in Python (``VRBagHandler.iterate_refinements``, :243-298), writing co
 at a time (``VRBagWriter.update_refinement_batch``, :550-588).  h5py and GDAL are not part of this path:
 the handlers here work on the two structured arrays themselves (``from_arrays``), which is also what the
 device path (``NativeVRProcessor.process_refinements``) uploads as they are.  Opening a file needs h5py and
-raises ``ImportError`` without it, as the reference does (:118-119); the georeferenced ``SidecarBuilder``
-(GDAL) stays with the reference.
+raises ``ImportError`` without it, as the reference does (:118-119).
+
+``SidecarBuilder`` (reference :609-835) rasterises classification / confidence / correction / valid mask of the processed
+grids onto one georeferenced raster.  Only its constructor (shape, geotransform and CRS of GDAL's resampled view) and ``save``
+(GeoTIFF) need GDAL and stay with the reference; ``SidecarBuilder.from_georef`` takes those three values as arguments, and the
+rasterisation runs either on the host (``add_refinement_results``, vectorised) or on the device
+(``NativeVRProcessor.process_refinements(..., sidecar=builder)``: include/bgnn_sidecar.h, csrc/vr_sidecar.hip).
 
 Array formats (BAG 1.6, the fields the reference reads at :262-290):
   varres_metadata     [rows, cols] records: index u32, dimensions_x u32, dimensions_y u32, resolution_x f32,
@@ -431,6 +436,156 @@ class SRBagWriter:
     def __exit__(self, exc_type, exc_val, exc_tb):
         self.close()
         return False
+
+
+class SidecarBuilder:
+    """Sidecar raster of a native VR run (reference :609-835): float32 ``classification``, ``confidence``, ``correction`` (NaN where
+    nothing was painted) and ``valid_mask`` (0 / 1) on one grid ``shape`` with ``geotransform`` / ``crs``.
+
+    Every processed refinement grid is painted at its geographic position, each cell as a ``scale x scale`` block of pixels,
+    refinement row 0 at the south (``add_refinement_results``, reference :695-778).  Grids are applied in iteration order: where two
+    cover a pixel the later one's values stay; the valid mask is sticky (1 where any covering cell was valid); pixels outside the
+    raster are dropped.
+
+    ``SidecarBuilder(handler)`` is the reference's constructor: it reads the raster's georeferencing from GDAL's resampled view of
+    the BAG and raises ``ImportError`` without GDAL.  ``from_georef`` is the array interface.  After a device run
+    (``process_refinements(..., sidecar=self)``) the four planes live on the GPU (``planes_device()``); the host attributes are
+    filled from there on first access."""
+
+    MAX_PIXELS = 1 << 28            # BGNN_SIDECAR_MAX_PIXELS (include/bgnn_sidecar.h): the device images are 24 B per pixel
+
+    def __init__(self, handler):
+        self.handler = handler
+        try:
+            from osgeo import gdal  # noqa: F401
+        except ImportError:
+            raise ImportError("GDAL required for SidecarBuilder")
+        raise NotImplementedError("reading the resampled view's georeferencing with GDAL stays with the reference: "
+                                  "use SidecarBuilder.from_georef(handler, shape, geotransform, crs)")    # pragma: no cover
+
+    @classmethod
+    def from_georef(cls, handler, shape, geotransform, crs: str = "") -> "SidecarBuilder":
+        """A builder for a raster of ``shape`` = (rows, cols) with GDAL-style ``geotransform`` (origin x, pixel width, 0, origin y,
+        0, -pixel height) and ``crs`` -- what the reference reads from the resampled view (:679-691).  ``handler`` only has to
+        offer ``base_shape``."""
+        self = object.__new__(cls)
+        self.handler = handler
+        self.shape = (int(shape[0]), int(shape[1]))
+        if self.shape[0] < 1 or self.shape[1] < 1:
+            raise ValueError(f"raster shape {self.shape}: both sides must be at least 1")
+        self.geotransform = tuple(float(v) for v in geotransform)
+        if len(self.geotransform) != 6 or self.geotransform[1] == 0 or self.geotransform[5] == 0:
+            raise ValueError("geotransform: six values with non-zero pixel sizes")
+        self.crs = crs
+        gt = self.geotransform
+        self.resolution = abs(gt[1])
+        min_x, max_y = gt[0], gt[3]
+        self.bounds = (min_x, max_y + self.shape[0] * gt[5], min_x + self.shape[1] * gt[1], max_y)
+        self._planes = None            # [4, H, W] host planes, made on first access (a device run may never need them)
+        self._device = None            # [4, H, W] device tensor of a device run not yet downloaded
+        self._device_planes = self._device_ready = None
+        self._used = False
+        logger.info(f"SidecarBuilder initialized: {self.shape} at {self.resolution}m")
+        return self
+
+    # ---- the four planes ------------------------------------------------------------------------------------
+    def _host(self) -> np.ndarray:
+        if self._device is not None:
+            dev, self._device = self.planes_device(), None
+            self._planes = dev.cpu().numpy()
+        elif self._planes is None:
+            self._planes = np.empty((4,) + self.shape, np.float32)
+            self._planes[:3] = np.nan
+            self._planes[3] = 0
+        return self._planes
+
+    classification = property(lambda self: self._host()[0])
+    confidence = property(lambda self: self._host()[1])
+    correction = property(lambda self: self._host()[2])
+    valid_mask = property(lambda self: self._host()[3])
+
+    @property
+    def fresh(self) -> bool:
+        """True until something has been added (a device run needs a fresh builder)."""
+        return not self._used
+
+    def planes(self) -> np.ndarray:
+        """float32 [4, H, W] on the host: classification, confidence, correction, valid_mask (the builder's own storage)."""
+        return self._host()
+
+    def planes_device(self):
+        """The [4, H, W] device tensor a device run left (no download); ``None`` when there has been none."""
+        if self._device_ready is not None:                 # (written on the library's stream: wait for it once)
+            self._device_ready.synchronize()
+            self._device_ready = None
+        return self._device_planes
+
+    def _adopt_device(self, planes_t, ready=None):
+        """``process_refinements`` hands over the device planes and the event behind the kernel that completes them."""
+        self._device = self._device_planes = planes_t
+        self._device_ready = ready
+        self._used = True
+
+    # ---- placement (reference :711-752) -----------------------------------------------------------------------
+    def placement(self, table) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``(out_row_start, out_col_start, scale)`` as int64 arrays for every grid of a ``refinement_table()`` (the keys used:
+        ``base_row, base_col, dims_y, dims_x, res_x, res_y, sw_x, sw_y``), in float64 like the reference's per-grid Python
+        expressions: the float32 metadata widened, ``round`` half-to-even, the scale from ``res_x`` alone and at least 1, the
+        grid's height from ``res_y``."""
+        f8 = lambda k: np.asarray(table[k]).astype(np.float64)
+        base_shape = self.handler.base_shape
+        b, gt = self.bounds, self.geotransform
+        base_cell_width = (b[2] - b[0]) / base_shape[1]
+        base_cell_height = (b[3] - b[1]) / base_shape[0]
+        ref_x = (b[0] + f8("base_col") * base_cell_width) + f8("sw_x")
+        ref_y = (b[1] + f8("base_row") * base_cell_height) + f8("sw_y")
+        ref_top_y = ref_y + f8("dims_y") * f8("res_y")
+        col0 = np.rint((ref_x - gt[0]) / gt[1])
+        row0 = np.rint((gt[3] - ref_top_y) / abs(gt[5]))
+        scale = np.maximum(1, np.rint(f8("res_x") / self.resolution))
+        return row0.astype(np.int64), col0.astype(np.int64), scale.astype(np.int64)
+
+    @staticmethod
+    def _grid_table(grid):
+        one = lambda v, dt: np.array([v], dt)
+        return {"base_row": one(grid.base_row, np.int64), "base_col": one(grid.base_col, np.int64),
+                "dims_y": one(grid.dimensions[0], np.int64), "dims_x": one(grid.dimensions[1], np.int64),
+                "res_x": one(grid.resolution[0], np.float64), "res_y": one(grid.resolution[1], np.float64),
+                "sw_x": one(grid.sw_corner[0], np.float64), "sw_y": one(grid.sw_corner[1], np.float64)}
+
+    # ---- host rasterisation -------------------------------------------------------------------------------------
+    def add_refinement_results(self, grid: RefinementGrid, classification: np.ndarray, confidence: np.ndarray,
+                               correction: np.ndarray):
+        """Paint one processed grid (reference :695-778; same end state).  The raster window the grid's footprint overlaps is
+        assigned in one piece per plane: raster row ``R`` takes refinement row ``h - 1 - (R - row0) // scale``, raster column
+        ``C`` takes refinement column ``(C - col0) // scale``."""
+        planes = self._host()
+        self._used = True
+        self._device_planes = None                         # (a device run's tensor no longer holds the builder's state)
+        row0, col0, scale = (int(v[0]) for v in self.placement(self._grid_table(grid)))
+        h, w = int(grid.dimensions[0]), int(grid.dimensions[1])
+        r_lo, r_hi = max(0, row0), min(self.shape[0], row0 + h * scale)
+        c_lo, c_hi = max(0, col0), min(self.shape[1], col0 + w * scale)
+        if r_hi <= r_lo or c_hi <= c_lo:
+            return
+        src_r = (h - 1) - (np.arange(r_lo, r_hi) - row0) // scale
+        src_c = (np.arange(c_lo, c_hi) - col0) // scale
+        ix = np.ix_(src_r, src_c)
+        win = (slice(r_lo, r_hi), slice(c_lo, c_hi))
+        planes[0][win] = np.asarray(classification)[ix]
+        planes[1][win] = np.asarray(confidence)[ix]
+        planes[2][win] = np.asarray(correction)[ix]
+        np.putmask(planes[3][win], np.asarray(grid.valid_mask)[ix], np.float32(1.0))
+
+    def save(self, path):
+        """GeoTIFF export needs GDAL and stays with the reference (:780-834); without it: an error in the log, as there."""
+        try:
+            from osgeo import gdal  # noqa: F401
+        except ImportError:
+            logger.error("GDAL required for GeoTIFF export")
+            return
+        raise NotImplementedError("GeoTIFF export with GDAL stays with the reference: write planes() with "
+                                  "geotransform / crs")    # pragma: no cover
 
 
 def detect_bag_type(path) -> str:

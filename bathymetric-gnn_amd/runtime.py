@@ -124,6 +124,17 @@ _TRAIN_SIGNATURES = {
     "bgnn_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OutputGrads), C.c_void_p]),
 }
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_sidecar.h declares (the VR BAG sidecar raster)
+_SIDECAR_SIGNATURES = {
+    "bgnn_sidecar_table_bytes": (C.c_size_t, [C.c_int32]),
+    "bgnn_sidecar_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
+    "bgnn_sidecar_add": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
+    "bgnn_sidecar_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+}
+SIDECAR_MAX_PIXELS = 1 << 28       # BGNN_SIDECAR_MAX_PIXELS
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -133,7 +144,8 @@ class BgnnError(RuntimeError):
 
 
 def load_library(path: Optional[str] = None):
-    """dlopen the HIP library and bind every symbol of include/bgnn.h and include/bgnn_train.h.  Needs no GPU."""
+    """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h and include/bgnn_sidecar.h.  Needs no
+    GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -144,7 +156,7 @@ def load_library(path: Optional[str] = None):
                 f"{p} not found: the HIP library is not built. Run `python __graft_entry__.py` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = C.CDLL(p)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

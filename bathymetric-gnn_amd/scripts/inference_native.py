@@ -405,9 +405,43 @@ class NativeVRProcessor:
         s.ensure(cells, grids, results)
         return s
 
+    def _sidecar_begin(self, sidecar, tab, hw):
+        """Device state of one sidecar run: the placement table (checked and clipped to the raster by ``bgnn_sidecar_table``, which
+        also refuses a raster over the documented bound), the three zeroed uint64 images and the [4, H, W] float planes whose last
+        plane, the valid mask, the chunks write directly."""
+        from types import SimpleNamespace
+        from .. import runtime as rt
+        ctx = self._engine.ctx
+        n = len(tab["cells"])
+        h, w = int(sidecar.shape[0]), int(sidecar.shape[1])
+        place = np.ascontiguousarray(np.stack(sidecar.placement(tab), 1), dtype=np.int64)
+        hw = np.ascontiguousarray(hw, dtype=np.int32)
+        pix_off = np.zeros(n + 1, np.int64)
+        nbytes = int(ctx.lib.bgnn_sidecar_table_bytes(n))
+        table = torch.empty(nbytes, dtype=torch.uint8, device=ctx.device)
+        torch.cuda.synchronize(ctx.device)                   # (allocated on the caller's stream, written on the engine's)
+        rt.check(ctx.lib.bgnn_sidecar_table(ctx.handle, h, w, n, hw.ctypes.data, place.ctypes.data, rt.ptr(table), nbytes,
+                                            pix_off.ctypes.data))
+        images = torch.zeros((3, h, w), dtype=torch.int64, device=ctx.device)
+        planes = torch.empty((4, h, w), dtype=torch.float32, device=ctx.device)
+        planes[3].zero_()
+        torch.cuda.synchronize(ctx.device)                   # (both contexts' streams write into them)
+        return SimpleNamespace(h=h, w=w, table=table, images=images, planes=planes, valid=planes[3], pix_off=pix_off)
+
+    def _sidecar_finish(self, sidecar, sc):
+        """Every chunk has completed: images -> value planes on the first context's stream; the builder takes the device planes."""
+        from .. import runtime as rt
+        ctx = self._engine.ctx
+        with torch.cuda.stream(ctx.stream):
+            rt.check(ctx.lib.bgnn_sidecar_finish(ctx.handle, sc.h, sc.w, rt.ptr(sc.images), sc.h * sc.w, rt.ptr(sc.planes)))
+            ready = torch.cuda.Event()
+            ready.record(ctx.stream)
+        sc.images.record_stream(ctx.stream)                  # (freed here, still read by the kernel just queued)
+        sidecar._adopt_device(sc.planes, ready)
+
     def process_refinements(self, handler, writer=None, min_valid_ratio: float = 0.0,
                             cell_budget: Optional[int] = None, return_results: bool = False, results_sink=None,
-                            auto_correct_threshold: Optional[float] = None):
+                            auto_correct_threshold: Optional[float] = None, sidecar=None):
         """Classify and correct every refinement grid of a VR BAG with the records resident in HBM.
 
         ``varres_refinements`` is already the concatenated-grid layout ``bgnn_infer_tiles`` consumes
@@ -420,13 +454,23 @@ class NativeVRProcessor:
         write-back arithmetic of ``apply_results``) -> D2H of the corrected records, the per-grid valid counts / keep flags
         and the counters (and, when asked for, the three result planes).  Up to ``BAG_SLOTS`` chunks are in flight on two
         contexts; a finished chunk goes into ``writer`` with one slice assignment and, per grid in iteration order, to
-        ``results_sink(grid, classification, confidence, correction)`` (where the sidecar builder is fed).
+        ``results_sink(grid, classification, confidence, correction)``.
+
+        ``sidecar`` (a fresh ``data.SidecarBuilder``, e.g. from ``SidecarBuilder.from_georef``): the sidecar raster is painted ON THE
+        DEVICE from the result planes each chunk leaves in HBM (``bgnn_sidecar_add`` behind ``bgnn_vr_apply`` on the chunk's stream,
+        one ``bgnn_sidecar_finish`` after the last chunk; include/bgnn_sidecar.h).  The per-grid placement is computed once on the
+        host (``SidecarBuilder.placement``); no result plane is copied to the host for it and collection stays where it was.  The
+        raster equals the builder fed grid by grid on the host, bit for bit, however the BAG was chunked.  The builder's host
+        attributes are filled from the device on first access (``planes_device()`` hands out the device tensor).  A builder that
+        has been added to already is refused with ``ValueError``.
 
         Returns the statistics the reference's ``main`` logs (:540-559); with ``return_results`` also per-record
         classification / confidence / correction arrays.  Results equal ``run_refinements(pipelined=False)`` (the
         reference's grid-by-grid loop) bit for bit; ``total_confidence`` is a float64 sum in device order."""
         import ctypes as C
         from .. import runtime as rt
+        if sidecar is not None and not sidecar.fresh:
+            raise ValueError("process_refinements(sidecar=...) needs a fresh SidecarBuilder: this one has been added to already")
         thr = self.auto_correct_threshold if auto_correct_threshold is None else auto_correct_threshold
         self._sync_options()
         tab = handler.refinement_table()
@@ -453,6 +497,7 @@ class NativeVRProcessor:
         hw = np.stack([tab["dims_y"], tab["dims_x"]], 1).astype(np.int32)
         res = np.stack([tab["res_x"], tab["res_y"]], 1).astype(np.float64)
         want_res = return_results or results_sink is not None
+        sc = self._sidecar_begin(sidecar, tab, hw) if sidecar is not None else None
         if cell_budget is None:
             cell_budget = min(max(total // 2 + 1, self.BAG_CHUNK_MIN), self.BAG_CHUNK_MAX)
         nodata = C.c_float(getattr(handler, "NODATA", 1.0e6))
@@ -501,6 +546,11 @@ class NativeVRProcessor:
                 eng.infer_device(hw[g0:g1], res[g0:g1], slot.depth_t[:n], slot.mask_t[:n], unc_t, out=out, defer_end=True, begin=False)
                 rt.check(ctx.lib.bgnn_vr_apply(ctx.handle, rt.ptr(slot.rec_t), n, rt.ptr(slot.mask_t), rt.ptr(out[0]), rt.ptr(out[1]),
                                                rt.ptr(out[2]), C.c_float(thr), rt.ptr(slot.tail_t), rt.ptr(slot.tail_t[24:])))
+                if sc is not None:      # (grid indices, not launch order, decide which grid owns a pixel: no ordering between the streams)
+                    rt.check(ctx.lib.bgnn_sidecar_add(ctx.handle, sc.h, sc.w, rt.ptr(sc.images), rt.ptr(sc.valid), sc.h * sc.w,
+                                                      rt.ptr(sc.table), n_grids, g0, g, int(sc.pix_off[g1] - sc.pix_off[g0]),
+                                                      rt.ptr(out[0]), rt.ptr(out[1]), rt.ptr(out[2]), rt.ptr(slot.mask_t), n,
+                                                      rt.ptr(keep_t)))
                 if writer is not None:
                     slot.out_rec_h[:n].copy_(slot.rec_t[:n], non_blocking=True)
                 slot.tail_h[:32 + 9 * g].copy_(slot.tail_t[:32 + 9 * g], non_blocking=True)
@@ -583,6 +633,8 @@ class NativeVRProcessor:
                     pass
             for slot in slots:
                 slot.done.synchronize()
+        if sc is not None:
+            self._sidecar_finish(sidecar, sc)
         stats["mean_confidence"] = stats["total_confidence"] / stats["cells_processed"] if stats["cells_processed"] else 0
         return (stats, res_all) if return_results else stats
 
@@ -600,14 +652,28 @@ def apply_results(depth: np.ndarray, uncertainty: Optional[np.ndarray], classifi
     return apply
 
 
+def _with_sidecar(sidecar, results_sink):
+    """The per-grid sink of the loop routes: the sidecar builder first (where the reference feeds it), then the user's sink."""
+    if results_sink is None:
+        return sidecar.add_refinement_results
+
+    def sink(grid, classification, confidence, correction):
+        sidecar.add_refinement_results(grid, classification, confidence, correction)
+        results_sink(grid, classification, confidence, correction)
+    return sink
+
+
 def run_refinements(processor: NativeVRProcessor, handler, writer, min_valid_ratio: float = 0.0,
                     auto_correct_threshold: Optional[float] = None, results_sink=None, pipelined: bool = True,
-                    records_resident: Optional[bool] = None):
+                    records_resident: Optional[bool] = None, sidecar=None):
     """The grid-by-grid loop of the reference's ``main`` (:445-538): iterate the refinement grids, queue them
     with ``add_to_batch``, flush when ``batch_ready``, apply each grid's results (``apply_results`` closure,
     :480-503) and write it back with ``update_refinement_batch``.  Kept as the API-level mirror and as the
     statement ``NativeVRProcessor.process_refinements`` (records resident in HBM) is tested against.
-    ``results_sink(grid, classification, confidence, correction)`` stands where the sidecar builder is fed.
+    ``results_sink(grid, classification, confidence, correction)`` stands where the sidecar builder is fed; ``sidecar`` IS a sidecar
+    builder (``data.SidecarBuilder``): on the records-resident route it is painted on the device (``process_refinements(...,
+    sidecar=...)``), on every other route its ``add_refinement_results`` is called per grid where the reference calls it (before
+    the write-back arithmetic, :482-483), ahead of a user ``results_sink`` if both are given.
 
     ``pipelined`` (default): a full batch is SUBMITTED (``submit_batch``) and the loop goes on queueing the next one; the
     results of the batch before it are collected -- and applied, in the same grid order -- while the new one runs on the
@@ -633,9 +699,17 @@ def run_refinements(processor: NativeVRProcessor, handler, writer, min_valid_rat
     if records_resident:
         if not can_route:
             raise ValueError("records_resident=True needs a handler with refinement_table() / varres_refinements and a writer with write_records()")
-        st = processor.process_refinements(handler, writer, min_valid_ratio, results_sink=results_sink, auto_correct_threshold=thr)
+        kw = {}
+        if sidecar is not None:
+            if hasattr(sidecar, "_adopt_device"):
+                kw["sidecar"] = sidecar                     # (passed only when given: processors with the earlier signature keep working)
+            else:                                           # a foreign builder (the reference's own class): fed on the host
+                results_sink = _with_sidecar(sidecar, results_sink)
+        st = processor.process_refinements(handler, writer, min_valid_ratio, results_sink=results_sink, auto_correct_threshold=thr, **kw)
         st.pop("grids_skipped", None)                      # (the loop's statistics, key for key)
         return st
+    if sidecar is not None:
+        results_sink = _with_sidecar(sidecar, results_sink)
     stats = {"grids_processed": 0, "cells_processed": 0, "cells_classified_noise": 0, "cells_corrected": 0,
              "total_confidence": 0.0}
     nodata = getattr(handler, "NODATA", 1.0e6)
