@@ -135,6 +135,42 @@ _SIDECAR_SIGNATURES = {
 }
 SIDECAR_MAX_PIXELS = 1 << 28       # BGNN_SIDECAR_MAX_PIXELS
 
+
+class NoiseParams(C.Structure):
+    """bgnn_noise_params: which noise terms run, and the generator parameters that are not drawn."""
+    _fields_ = [("enable_gaussian", C.c_int32), ("enable_spikes", C.c_int32), ("enable_blobs", C.c_int32),
+                ("enable_systematic", C.c_int32), ("complexity_correlation", C.c_double), ("spike_mag_min", C.c_double),
+                ("spike_mag_max", C.c_double), ("seed", C.c_uint64)]
+
+
+class NoiseBlob(C.Structure):
+    """bgnn_noise_blob: centre (row < 0: the floor(centre_u * n_valid)-th valid cell), size, signed magnitude draw."""
+    _fields_ = [("row", C.c_int32), ("col", C.c_int32), ("size", C.c_int32), ("pad", C.c_int32), ("centre_u", C.c_double),
+                ("magnitude", C.c_double)]
+
+
+class NoisePlan(C.Structure):
+    """bgnn_noise_plan: the scalar draws of one tile and its slice of the blob list."""
+    _fields_ = [("sample", C.c_uint64), ("intensity", C.c_double), ("gaussian_std_factor", C.c_double),
+                ("spike_density", C.c_double), ("amplitude_factor", C.c_double), ("freq_a", C.c_double), ("freq_b", C.c_double),
+                ("phase", C.c_double), ("artifact", C.c_int32), ("blob_first", C.c_int32), ("blob_count", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class NoiseFields(C.Structure):
+    """bgnn_noise_fields: device pointers of supplied per-cell draws (any may be NULL)."""
+    _fields_ = [("gaussian", C.c_void_p), ("uniform", C.c_void_p), ("sign", C.c_void_p), ("magnitude", C.c_void_p)]
+
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_noise.h declares (synthetic training noise)
+_NOISE_SIGNATURES = {
+    "bgnn_noise_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_void_p, C.c_int32]),
+    "bgnn_noise_generate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NoiseParams),
+                                      C.POINTER(NoisePlan), C.POINTER(NoiseBlob), C.c_int32, C.POINTER(NoiseFields), C.c_void_p,
+                                      C.c_size_t] + [C.c_void_p] * 4),
+}
+NOISE_ARTIFACTS = ("none", "stripe_horizontal", "stripe_vertical", "wave", "gradient_x", "gradient_y", "gradient_diagonal")   # BGNN_NOISE_*
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -144,8 +180,8 @@ class BgnnError(RuntimeError):
 
 
 def load_library(path: Optional[str] = None):
-    """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h and include/bgnn_sidecar.h.  Needs no
-    GPU."""
+    """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h and
+    include/bgnn_noise.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -156,7 +192,8 @@ def load_library(path: Optional[str] = None):
                 f"{p} not found: the HIP library is not built. Run `python __graft_entry__.py` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = C.CDLL(p)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
+                list(_NOISE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
