@@ -7,11 +7,11 @@ tile-batch inference loop, behind the reference's own Python API
 kernels for gfx950 reached through the C ABI declared in ``include/bgnn.h``; there is no
 CPU fallback -- importing works anywhere, computing raises without the library + a GPU.
 
-Submodules mirror the reference's layout: ``config``, ``data``, ``models``, ``scripts``.
+Submodules mirror the reference's layout: ``config``, ``data``, ``models``, ``scripts``, ``training`` (the loss side).
 """
 __version__ = "0.1.0"
 
-__all__ = ["config", "data", "models", "scripts", "synthetic", "runtime"]
+__all__ = ["config", "data", "models", "scripts", "training", "synthetic", "runtime"]
 
 
 def __getattr__(name):  # lazy submodules: `import bathymetric_gnn_amd as b; b.data.GraphBuilder`

@@ -171,6 +171,40 @@ _NOISE_SIGNATURES = {
 }
 NOISE_ARTIFACTS = ("none", "stripe_horizontal", "stripe_vertical", "wave", "gradient_x", "gradient_y", "gradient_diagonal")   # BGNN_NOISE_*
 
+
+
+class LossParams(C.Structure):
+    """bgnn_loss_params: what a BathymetricGNNLoss holds (class weights, smoothing, Huber delta, class ids, penalties, term weights)."""
+    _fields_ = [("num_classes", C.c_int32), ("has_class_weights", C.c_int32), ("class_weights", C.c_double * 16),
+                ("label_smoothing", C.c_double), ("delta", C.c_double), ("feature_class", C.c_int32),
+                ("feature_noise_class", C.c_int32), ("seafloor_class", C.c_int32), ("shoal_noise_class", C.c_int32),
+                ("penalty_weight", C.c_double), ("shoal_penalty", C.c_double), ("deep_penalty", C.c_double),
+                ("term_weights", C.c_double * 5)]
+
+
+class LossInputs(C.Structure):
+    """bgnn_loss_inputs: device pointers of the model outputs and targets of one loss call (three may be NULL)."""
+    _fields_ = [("logits", C.c_void_p), ("confidence", C.c_void_p), ("correction", C.c_void_p), ("predicted_class", C.c_void_p),
+                ("labels", C.c_void_p), ("correction_targets", C.c_void_p), ("noise_mask", C.c_void_p)]
+
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_loss.h declares (the multi-task training loss)
+_LOSS_SIGNATURES = {
+    "bgnn_loss_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "bgnn_loss_forward": (C.c_int, [C.c_void_p, C.POINTER(LossParams), C.c_int64, C.POINTER(LossInputs), C.c_void_p, C.c_size_t,
+                                    C.c_void_p, C.c_void_p]),
+    "bgnn_loss_backward": (C.c_int, [C.c_void_p, C.POINTER(LossParams), C.c_int64, C.POINTER(LossInputs)] + [C.c_void_p] * 5),
+}
+# launch geometry and table layout of include/bgnn_loss.h (BGNN_LOSS_*)
+LOSS_MAX_CLASSES = 16
+LOSS_IGNORE_INDEX = -100
+LOSS_ROWS_PER_WG = 1024        # rows behind one partial sum
+LOSS_FINISH_WIDTH = 256        # partials the finish workgroup reads per pass
+LOSS_TERMS = ("classification", "correction", "confidence", "feature_preservation", "shoal_safety", "total")
+LOSS_COUNTS = ("n_masked", "false_positives", "shoal_false_positives", "deep_false_positives", "n_ignored", "n_invalid",
+               "feature_as_noise")
+LOSS_N_SUMS = 4
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -180,8 +214,8 @@ class BgnnError(RuntimeError):
 
 
 def load_library(path: Optional[str] = None):
-    """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h and
-    include/bgnn_noise.h.  Needs no GPU."""
+    """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
+    include/bgnn_noise.h and include/bgnn_loss.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -193,7 +227,7 @@ def load_library(path: Optional[str] = None):
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = C.CDLL(p)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
-                list(_NOISE_SIGNATURES.items()):
+                list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,9 @@
+"""Mirror of the loss side of the reference's ``training`` package: the multi-task loss of ``BathymetricGNN`` (fused HIP kernels
+on float32 device tensors, the same formulas as torch operations elsewhere) and the two helpers that derive its class weights and
+Huber delta from the training data.  The reference's ``Trainer`` and datasets (torch_geometric loaders, GDAL, tqdm) are outside
+the path."""
+from .losses import (BathymetricGNNLoss, ClassificationLoss, ConfidenceCalibrationLoss, CorrectionLoss, FeaturePreservationLoss,
+                     ShoalSafetyLoss, compute_class_weights, compute_correction_delta)
+
+__all__ = ["BathymetricGNNLoss", "ClassificationLoss", "CorrectionLoss", "ConfidenceCalibrationLoss", "FeaturePreservationLoss",
+           "ShoalSafetyLoss", "compute_class_weights", "compute_correction_delta"]

@@ -1,9 +1,11 @@
 """One training step of BathymetricGNN (default shape: GAT, hidden 64, heads 4, 4 layers, edge_dim 3, dropout 0.1; --gnn-type picks
 GraphSAGE or GIN instead) on a batch of 16 synthetic 256 x 256 V0 tiles, timed by phase on the GPU: the taped training forward, backward (bgnn_backward), weight repack +
 optimizer step (the repack timed on its own: host packing and upload of the blob), and the
-untaped training forward for comparison.  Prints one JSON line (milliseconds, medians over --steps) with the tape's bytes per node.
+untaped training forward for comparison.  --loss fused|torch replaces the fixed linear form of the outputs by BathymetricGNNLoss on random
+labels (90 / 2 / 8 % class mix, mask = label 2), through the fused kernels or as separate torch operations (``forward_torch``); its
+forward is timed on its own ("loss") and its backward is part of "backward".  Prints one JSON line (milliseconds, medians over --steps) with the tape's bytes per node.
 
-    python tools/train_step_bench.py [--gnn-type GAT|GraphSAGE|GIN] [--tiles 16] [--size 256] [--steps 10] [--warmup 3]
+    python tools/train_step_bench.py [--gnn-type GAT|GraphSAGE|GIN] [--tiles 16] [--size 256] [--steps 10] [--warmup 3] [--loss fused|torch]
 """
 import argparse
 import json
@@ -25,6 +27,7 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--loss", default=None, choices=["fused", "torch"])
     a = ap.parse_args()
     from bathymetric_gnn_amd import synthetic
     from bathymetric_gnn_amd.data import GraphBuilder
@@ -40,6 +43,14 @@ def main():
     opt = torch.optim.SGD(m.parameters(), lr=1e-6)
     N = g.num_nodes
     w = torch.randn(N, 3, device=dev)
+    if a.loss:
+        from bathymetric_gnn_amd.training import BathymetricGNNLoss, compute_class_weights
+        rng = np.random.default_rng(0)
+        labels = torch.from_numpy(rng.choice(3, size=N, p=(0.90, 0.02, 0.08))).to(dev)
+        targets = {"class_labels": labels, "noise_mask": labels == 2,
+                   "correction_targets": torch.from_numpy(rng.standard_normal(N).astype(np.float32)).to(dev)}
+        crit = BathymetricGNNLoss(class_weights=compute_class_weights(labels), label_smoothing=0.1)
+        loss_fn = crit if a.loss == "fused" else crit.forward_torch
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -49,11 +60,16 @@ def main():
         return r, (time.perf_counter() - t0) * 1e3
 
     rec = {"taped_forward": [], "backward": [], "repack_and_step": [], "untaped_forward": []}
+    if a.loss:
+        rec["loss"] = []
     for it in range(a.warmup + a.steps):
         m.dropout_seed = it
         opt.zero_grad(set_to_none=True)
         out, t_fwd = timed(lambda: m(g))
-        loss = (out["class_logits"] * w).sum() + out["confidence"].sum() + out["correction"].sum()
+        if a.loss:
+            loss, t_loss = timed(lambda: loss_fn(out, targets)["total"])
+        else:
+            loss = (out["class_logits"] * w).sum() + out["confidence"].sum() + out["correction"].sum()
         _, t_bwd = timed(loss.backward)
         _, t_opt = timed(opt.step)
         with torch.no_grad():
@@ -69,8 +85,11 @@ def main():
             rec["backward"].append(t_bwd)
             rec["untaped_forward"].append(t_plain)
             rec["repack_and_step"].append(t_opt + t_pack)
+            if a.loss:
+                rec["loss"].append(t_loss)
     tape_bytes = int(ctx.lib.bgnn_tape_bytes(m.native(ctx, 3), g._handle))
     res = {"metric": "train_step_ms", "gnn_type": a.gnn_type, "nodes": N, "tiles": a.tiles, "size": a.size,
+           **({"loss_path": a.loss} if a.loss else {}),
            **{k: round(float(np.median(v)), 3) for k, v in rec.items()},
            "tape_bytes_per_node": round(tape_bytes / N, 1), "tape_gb": round(tape_bytes / 1e9, 3)}
     print(json.dumps(res))
