@@ -173,10 +173,9 @@ def _accept(group, name, g_gpu, g64, g32, scale=1):
     assert not bad, "\n".join(bad)
 
 
-def _tape_relu_patterns(m, out, n):
-    """The kernels' ReLU patterns of ``out``'s training step, in the order the oracle applies its ReLUs: the extractor's h0, the
-    output of every GAT layer but the last, then each head's hidden units -- every one ``> 0`` over the first ``n`` rows of the
-    tape (bgnn_api.hip tape_layout: a 256-byte header, then [row capacity][width] float32 tables, each 256-byte aligned)."""
+def _tape_tables(m, out):
+    """(tape, row capacity, head units HT, {table: byte offset}) of ``out``'s GAT training step (bgnn_api.hip tape_layout: a
+    256-byte header, then [row capacity][width] float32 tables, each 256-byte aligned)."""
     tape = out["class_logits"].grad_fn.info["tape"]
     hid, nh = m.hidden_channels, 3 if m.predict_correction else 2
     hh = hid // 2
@@ -210,7 +209,16 @@ def _tape_relu_patterns(m, out, n):
         if found:
             break
     assert found, "the tape's size fits no layout of this model"
-    rows, HT, t = found
+    return (tape,) + found
+
+
+def _tape_relu_patterns(m, out, n):
+    """The kernels' ReLU patterns of ``out``'s training step, in the order the oracle applies its ReLUs: the extractor's h0, the
+    output of every GAT layer but the last, then each head's hidden units -- every one ``> 0`` over the first ``n`` rows of the
+    tape."""
+    tape, rows, HT, t = _tape_tables(m, out)
+    hid, nh = m.hidden_channels, 3 if m.predict_correction else 2
+    hh = hid // 2
 
     def table(off, w):
         return tape[off:off + n * w * 4].view(torch.float32).view(n, w).cpu()
