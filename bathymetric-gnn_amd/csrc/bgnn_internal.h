@@ -56,6 +56,20 @@ struct ProfRecord {
   hipEvent_t start, stop;
 };
 
+// Offsets (in floats) of every tensor of the weight blob (bgnn_model_weight_count order) -- of the gradient blob as well; filled by
+// model_pack.hip weight_layout.
+// Layer slots: GAT  W = lin.weight, as / ad / ae = att_src / att_dst / att_edge, We = lin_edge.weight, bias;
+//              GCN  W = lin.weight, bias;  GraphSAGE  W = lin_l.weight, bias = lin_l.bias, W2 = lin_r.weight;
+//              GIN  W = nn.0.weight, b1 = nn.0.bias, W2 = nn.2.weight, bias = nn.2.bias;
+// then every backbone's BatchNorm weight / bias / running_mean / running_var.  Slots a backbone does not have stay 0.
+struct WeightLayout {
+  size_t fe_W0, fe_b0, fe_W1, fe_b1;
+  struct Layer { size_t W, as, ad, ae, We, bias, bn_w, bn_b, bn_mean, bn_var, W2, b1; };
+  std::vector<Layer> layers;
+  size_t hd_W0[3], hd_b0[3], hd_W1[3], hd_b1[3];   // per head: mlp.0 weight / bias, mlp.3 weight / bias
+  size_t total;
+};
+
 }  // namespace bgnn
 
 // Per-tile metadata (device + host copy)
@@ -146,7 +160,7 @@ struct BgnnLayer {
   float *shift;     // [width]  (conv bias - mean) * scale + BN bias
   float *Wsp;       // Wt as a bf16 hi / lo split image for the bf16x3 matrix path (same byte geometry as Wt; see pack_split)
   float *Wsp16;     // the same with float16 parts (fp16x3), of W * 2^S ...
-  float Wsp16_inv = 1.0f;   // ... 2^-S: the kernels' accumulators are multiplied by it (bgnn_api.hip pack_split)
+  float Wsp16_inv = 1.0f;   // ... 2^-S: the kernels' accumulators are multiplied by it (model_pack.hip pack_split)
   float *Wfp;       // Wt with the columns of every row permuted for the fused exact-f32 kernel (gat_layer_fused.hip: WTileGroup)
   float *Wbf;       // Wt as a bf16 (hi only) image for the bf16 storage path: [D/16][NC/32][1 KiB] in MFMA A-fragment lane order
   // non-attention backbones (desc.gnn_type != BGNN_GNN_GAT): Wt = GCN lin^T [hid][hid] | SAGE [lin_l^T ; lin_r^T] [2 hid][hid]
@@ -165,6 +179,7 @@ struct bgnn_model {
   bgnn_model_desc desc;       // the shape the KERNELS run: hidden / heads zero-padded to a supported width (bgnn_model_create)
   int logical_hidden = 0, logical_heads = 0;   // the caller's shape: widths of `hidden` in / out, bgnn_model_weight_count
   bool padded = false;
+  bgnn::WeightLayout weights; // of `desc`: where `raw` (and the gradient blob of bgnn_backward) holds which tensor
   float *blob = nullptr;      // one device allocation holding everything below
   size_t blob_floats = 0;
   float *fe_W0t, *fe_b0, *fe_W1t, *fe_b1;     // [in8][hid], [hid], [hid][hid], [hid]
@@ -269,6 +284,20 @@ namespace bgnn {
 int ctx_workspace(bgnn_ctx *ctx, int slot, size_t bytes, void **out);
 int ctx_upload(bgnn_ctx *ctx, const void *host, size_t bytes, void *dev);
 
+// ---- host helpers shared by bgnn_api.hip, model_pack.hip and train_api.hip ------------------
+int head_count(const bgnn_model_desc *d);                                            // model_pack.hip
+int model_canonical_V(bgnn_model *m, const bgnn_graph *g, const float **out);        // model_pack.hip
+// The pieces the inference forward and the training forward share (bgnn_api.hip).  forward_begin: the input checks, the four
+// workspace tables, the foreign-graph self-loop check of GraphSAGE / GIN; rows = 0 on return: an empty graph, nothing to do
+struct FwdTables {
+  int64_t rows = 0;
+  const int64_t *dm = nullptr;               // the node count on the device
+  float *X = nullptr, *Y = nullptr;          // two [rows][widest layer] tables
+  float *asdX = nullptr, *asdY = nullptr;    // two [rows][2 heads] tables of attention dots
+  float *hidb = nullptr;                     // [rows][head_hidden_total]
+};
+int forward_begin(bgnn_ctx *ctx, const bgnn_model *m, const bgnn_graph *g, FwdTables *t);
+
 // profiling scope: records events around a kernel launch when enabled for that kernel
 struct ProfScope {
   bgnn_ctx *ctx;
@@ -338,6 +367,11 @@ int launch_gat_aggregate(bgnn_ctx *ctx, const bgnn_graph *g, const BgnnLayer &L,
                          const float *asd, float *out, int relu, const DropSpec *attention_drop = nullptr);
 int launch_gat_aggregate_tiled(bgnn_ctx *ctx, const bgnn_graph *g, const BgnnLayer &L, int C, int ED, const float *xw,
                                const float *asd, float *out, int relu);
+// the unfused GAT layer (bgnn_api.hip): the tiled aggregate where it has an instance and no attention dropout is asked for, else the plain one
+int gat_aggregate_unfused(bgnn_ctx *ctx, const bgnn_graph *g, const BgnnLayer &L, int C, int ED, const float *xw, const float *asd,
+                          float *out, int relu, const DropSpec *attention_drop);
+// the `hidden` output (backbone output h [rows][hidden]) and the heads' first layers into t.hidb (bgnn_api.hip); launch_heads_final follows
+int forward_heads_hidden(bgnn_ctx *ctx, const bgnn_model *m, const float *h, const FwdTables &t, const bgnn_outputs *o);
 // fused K4 + next K3 (EPI_NEXT) / K4(last) + K5 + K6 (EPI_HEADS); BGNN_ERR_UNSUPPORTED when no instance fits
 // (V3: the layer's edge vector over the canonical three attributes, [heads][3] -- nullptr: L.V is that already, default list)
 int launch_fused_layer_next(bgnn_ctx *ctx, const bgnn_graph *g, const BgnnLayer &L, const BgnnLayer &Ln, int C, const float *V3,

@@ -85,7 +85,7 @@ struct FusedArgs {
   void *out;              // [rows][NC]  f32, or bf16 with SP = 3
   float *asd_out;         // [rows][2*H2]
   int H2, C2;
-  float w_inv;            // SP = 2: the float16 weight image holds W * 2^S (bgnn_api.hip pack_split); accumulators *= 2^-S before the epilogue
+  float w_inv;            // SP = 2: the float16 weight image holds W * 2^S (model_pack.hip pack_split); accumulators *= 2^-S before the epilogue
   const float *W0af;      // layer 0 "aggregate first" (gat_layer_bf16_2p_kernel, AF): the folded lin_0 weight as per-head 64 x 64 bf16 images
   // EPI_HEADS
   const float *hd_tab;    // [HEADW] b0 [96] | second-layer rows (cls [classes], conf, corr) at 96 + 32 j | their biases at 288
@@ -374,7 +374,7 @@ struct FusedGeom {                                       // halo geometry of one
 // per 32-channel slab: A = X^T read straight from the [row][32 ch] slab image by ds_read_b64_tr_b16 (the hardware transpose), B =
 // the dense alpha rows (one ds_read_b128 per 16 window rows).  The result tile has the cell on the lane and the channels in the
 // 16 registers -- exactly what the next-layer GEMM wants as ITS B operand (k order 8(j>>2) + 4h + (j&3): the W image is packed
-// to match, bgnn_api.hip pack_bf16_image_accop).  Per slab and wave that replaces 17 x 3 LDS reads, 272 unpack and 144 FMA
+// to match, model_pack.hip pack_bf16_image_accop).  Per slab and wave that replaces 17 x 3 LDS reads, 272 unpack and 144 FMA
 // instructions by 16 + 8 LDS reads and 8 MFMAs; 87 % of those MFMAs' products are zeros, on a pipe with 16x the vector rate.
 // alpha is rounded to bf16 for this (the activations it multiplies already are).  Rows without a node hold zeros and 0 x 0 = 0;
 // non-finite activations (which valid, finite depths cannot produce) would spread over the window instead of the stencil.
@@ -1177,7 +1177,7 @@ __global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, 
     }
   }
 
-  if constexpr (SP == 2) {                              // the float16 image holds W * 2^S (bgnn_api.hip pack_split): exact power-of-two rescale
+  if constexpr (SP == 2) {                              // the float16 image holds W * 2^S (model_pack.hip pack_split): exact power-of-two rescale
     const float wi = a.w_inv;
 #pragma unroll
     for (int t = 0; t < NT; ++t)

@@ -252,9 +252,9 @@ __device__ __forceinline__ f32x16 mfma_lp(const f16x8 &a, const f16x8 &b, const 
 // gemm_f32_kernel<2, false> launch it replaces -- bit-identical h1, which never goes to HBM (256 B/node written + read back,
 // and one launch, less).  The result tile holds, on lane (r, h), channels 8s + 4h + i of row r: exactly this kernel's X fragment
 // order on the exact path; on the bf16 path it is the accumulator-as-operand order, for which the W image is packed
-// (bgnn_api.hip pack_bf16_image_accop).
+// (model_pack.hip pack_bf16_image_accop).
 // PM (exact path, attention form with the fused front, NT >= 4): tile-PAIR-major MFMA order over a weight image whose columns
-// interleave the two tiles of a pair (bgnn_api.hip pack_tilegroup_image, TG = 2: one ds_read_b64 = the fragments of both tiles of a
+// interleave the two tiles of a pair (model_pack.hip pack_tilegroup_image, TG = 2: one ds_read_b64 = the fragments of both tiles of a
 // k row), with the epilogue of pair p -- bias, attention dots, transposed patch, row stores -- issued in eight slots BETWEEN the
 // eight MFMA groups of pair p + 1.  In the tile-major form a wave's life is 256 MFMAs, then ~600 epilogue instructions; the two
 // waves of a SIMD share the matrix pipe fairly, so they stay in phase -- both in their MFMAs, then both in their epilogues with
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wres64_kernel(GemmArgs a) {
   float *wl = wres_lds;                              // [64][NC]
   constexpr int PP = 68;                              // patch pitch: two 32-column tiles side by side + 4 pad
   // bf16 output: the attention dots are a NINTH 32-column MFMA tile (AMF).  Its weight columns are W att folded on the host
-  // (bgnn_api.hip pack_alpha_tile): column hd = sum over head hd's columns of W_bf16[k][c] att_src[c] (4 + hd: att_dst), as bf16
+  // (model_pack.hip pack_alpha_tile): column hd = sum over head hd's columns of W_bf16[k][c] att_src[c] (4 + hd: att_dst), as bf16
   // hi parts, columns 8.. / 12.. their bf16 lo parts, so that hi + lo carries 16 mantissa bits; the bias' share is a constant per
   // head behind the image.  Against taking the dots from the accumulators this drops 64 ds_read_b128 of the att vectors, 64
   // v_pk_fma_f32 and 8 scalar stores per 32 rows for 4 MFMAs and one 16-byte store: the launch was bound by exactly that LDS and
@@ -549,7 +549,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wres64_kernel(GemmArgs a) {
             acc[t] = mfma_lp(wh, xh, acc[t]);
           }
         }
-        if constexpr (SP == 2) {                       // the image holds W * 2^S (bgnn_api.hip pack_split): exact power-of-two rescale
+        if constexpr (SP == 2) {                       // the image holds W * 2^S (model_pack.hip pack_split): exact power-of-two rescale
           const float wi = a.w_inv;
 #pragma unroll
           for (int t = 0; t < NT; ++t)

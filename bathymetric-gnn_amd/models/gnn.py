@@ -250,72 +250,46 @@ class BathymetricGNN(nn.Module):
         d.bn_eps = float(self.gnn.norms[0].module.eps)
         return d
 
+    def _blob_slots(self, sd, ed: int):
+        """(state-dict key, numel) of every tensor of the weight blob, in the order ``bgnn_model_weight_count`` documents
+        (include/bgnn.h).  The key is None where the model has no tensor and the blob holds zeros: the edge weights of a model with
+        ``edge_dim=None``, over however many edge features the graph has."""
+        conv = {"GAT": ("lin.weight", "att_src", "att_dst", "att_edge", "lin_edge.weight", "bias"),
+                "GCN": ("lin.weight", "bias"),
+                "GraphSAGE": ("lin_l.weight", "lin_l.bias", "lin_r.weight"),
+                "GIN": ("nn.0.weight", "nn.0.bias", "nn.2.weight", "nn.2.bias")}[self.gnn_type]
+        mlp = ("mlp.0.weight", "mlp.0.bias", "mlp.3.weight", "mlp.3.bias")
+        for k in mlp:
+            yield "feature_extractor." + k, sd["feature_extractor." + k].numel()
+        for l in range(self.num_gnn_layers):
+            c = f"gnn.convs.{l}."
+            for k in conv:
+                if self.edge_dim is None and k in ("att_edge", "lin_edge.weight"):
+                    yield None, sd[c + "att_src"].numel() * (1 if k == "att_edge" else ed)
+                else:
+                    yield c + k, sd[c + k].numel()
+            for k in ("weight", "bias", "running_mean", "running_var"):
+                yield f"gnn.norms.{l}.module.{k}", sd[f"gnn.norms.{l}.module.{k}"].numel()
+        for h in ["classification_head", "confidence_head"] + (["correction_head"] if self.predict_correction else []):
+            for k in mlp:
+                yield f"{h}.{k}", sd[f"{h}.{k}"].numel()
+
     def pack_weights(self, graph_edge_dim: Optional[int] = None) -> np.ndarray:
         """Flat float32 blob in the order ``bgnn_model_weight_count`` documents (include/bgnn.h)."""
-        ed = self._edge_width(graph_edge_dim)
-        sd = {k: v.detach().to("cpu", torch.float32).contiguous().numpy().ravel() for k, v in self.state_dict().items()
-              if v.dtype.is_floating_point}
-        parts = []
-        for p in ("feature_extractor.mlp.0", "feature_extractor.mlp.3"):
-            parts += [sd[p + ".weight"], sd[p + ".bias"]]
-        for l in range(self.num_gnn_layers):
-            c, n = f"gnn.convs.{l}.", f"gnn.norms.{l}.module."
-            if self.gnn_type == "GAT":
-                if self.edge_dim is None:        # no edge term: zero att_edge / lin_edge over however many edge features the graph has
-                    att_e, lin_e = np.zeros_like(sd[c + "att_src"]), np.zeros(sd[c + "att_src"].size * ed, np.float32)
-                else:
-                    att_e, lin_e = sd[c + "att_edge"], sd[c + "lin_edge.weight"]
-                parts += [sd[c + "lin.weight"], sd[c + "att_src"], sd[c + "att_dst"], att_e, lin_e, sd[c + "bias"]]
-            elif self.gnn_type == "GCN":
-                parts += [sd[c + "lin.weight"], sd[c + "bias"]]
-            elif self.gnn_type == "GraphSAGE":
-                parts += [sd[c + "lin_l.weight"], sd[c + "lin_l.bias"], sd[c + "lin_r.weight"]]
-            else:
-                parts += [sd[c + "nn.0.weight"], sd[c + "nn.0.bias"], sd[c + "nn.2.weight"], sd[c + "nn.2.bias"]]
-            parts += [sd[n + "weight"], sd[n + "bias"], sd[n + "running_mean"], sd[n + "running_var"]]
-        heads = ["classification_head", "confidence_head"] + (["correction_head"] if self.predict_correction else [])
-        for h in heads:
-            parts += [sd[h + ".mlp.0.weight"], sd[h + ".mlp.0.bias"], sd[h + ".mlp.3.weight"], sd[h + ".mlp.3.bias"]]
+        sd = self.state_dict()
+        parts = [np.zeros(n, np.float32) if k is None else sd[k].detach().to("cpu", torch.float32).contiguous().numpy().ravel()
+                 for k, n in self._blob_slots(sd, self._edge_width(graph_edge_dim))]
         return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
 
     def grad_slots(self, graph_edge_dim: Optional[int] = None):
         """[(parameter name or None, offset, numel)] covering the blob of ``pack_weights`` -- and the gradient blob of
         ``bgnn_backward`` -- in order.  None marks the slots that are no parameter: BatchNorm running statistics, and the zero edge
         weights a model with ``edge_dim=None`` is packed with."""
-        ed = self._edge_width(graph_edge_dim)
-        sd = {k: v for k, v in self.state_dict().items() if v.dtype.is_floating_point}
         params = dict(self.named_parameters())
         slots, off = [], 0
-
-        def put(name, n=None):
-            nonlocal off
-            n = sd[name].numel() if n is None else n
-            slots.append((name if name in params else None, off, n))
+        for k, n in self._blob_slots(self.state_dict(), self._edge_width(graph_edge_dim)):
+            slots.append((k if k in params else None, off, n))
             off += n
-        for p in ("feature_extractor.mlp.0", "feature_extractor.mlp.3"):
-            put(p + ".weight"); put(p + ".bias")
-        for l in range(self.num_gnn_layers):
-            c, n = f"gnn.convs.{l}.", f"gnn.norms.{l}.module."
-            if self.gnn_type == "GAT":
-                put(c + "lin.weight"); put(c + "att_src"); put(c + "att_dst")
-                if self.edge_dim is None:
-                    hc = sd[c + "att_src"].numel()
-                    slots += [(None, off, hc), (None, off + hc, hc * ed)]
-                    off += hc + hc * ed
-                else:
-                    put(c + "att_edge"); put(c + "lin_edge.weight")
-                put(c + "bias")
-            elif self.gnn_type == "GCN":
-                put(c + "lin.weight"); put(c + "bias")
-            elif self.gnn_type == "GraphSAGE":
-                put(c + "lin_l.weight"); put(c + "lin_l.bias"); put(c + "lin_r.weight")
-            else:
-                put(c + "nn.0.weight"); put(c + "nn.0.bias"); put(c + "nn.2.weight"); put(c + "nn.2.bias")
-            for k in ("weight", "bias", "running_mean", "running_var"):
-                put(n + k)
-        for h in ["classification_head", "confidence_head"] + (["correction_head"] if self.predict_correction else []):
-            for k in (".mlp.0.weight", ".mlp.0.bias", ".mlp.3.weight", ".mlp.3.bias"):
-                put(h + k)
         return slots
 
     def _weights_version(self):

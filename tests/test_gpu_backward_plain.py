@@ -3,7 +3,7 @@ after a training-mode forward fills every parameter's ``.grad``, as it does for 
 
 Reference gradients: the oracle's training-mode forward (``oracle.gat_cpu.sage_conv`` / ``gin_conv``) under torch autograd in
 float64 and float32, with the kernels' dropout masks (``CounterDropout``, same seed) and the kernels' ReLU patterns (read from
-the tape, laid out as bgnn_api.hip ``PlainTapeLayout`` documents; ``test_gpu_backward_training`` explains why).  Acceptance rule
+the tape, laid out as train_api.hip ``TapeLayout`` documents; ``test_gpu_backward_training`` explains why).  Acceptance rule
 as there: per parameter, max |g_gpu - g64| <= BOUND_C * max |g32 - g64| + FLOOR_REL * max |g64|, and a parameter the loss does
 not reach gets exactly 0.
 

@@ -174,7 +174,7 @@ def _accept(group, name, g_gpu, g64, g32, scale=1):
 
 
 def _tape_tables(m, out):
-    """(tape, row capacity, head units HT, {table: byte offset}) of ``out``'s GAT training step (bgnn_api.hip tape_layout: a
+    """(tape, row capacity, head units HT, {table: byte offset}) of ``out``'s GAT training step (train_api.hip tape_layout: a
     256-byte header, then [row capacity][width] float32 tables, each 256-byte aligned)."""
     tape = out["class_logits"].grad_fn.info["tape"]
     hid, nh = m.hidden_channels, 3 if m.predict_correction else 2
