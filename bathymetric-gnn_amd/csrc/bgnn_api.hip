@@ -851,6 +851,7 @@ int bgnn_forward(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_auto, fl
   BGNN_REQUIRE(ctx && m && g && o, "bgnn_forward: NULL argument");
   BGNN_REQUIRE(m->ctx == ctx && g->ctx == ctx, "bgnn_forward: model/graph belong to another context");
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  BGNN_TRY(model_sync(ctx, m));
   return forward_infer(ctx, m, g, thr_auto, thr_review, o, nullptr);
 }
 
@@ -869,6 +870,7 @@ int bgnn_feature_extractor(bgnn_ctx *ctx, bgnn_model *m, const float *x, int64_t
   BGNN_REQUIRE(n_nodes >= 0 && n_nodes < ((int64_t)1 << 30), "bgnn_feature_extractor: n_nodes=%lld out of range", (long long)n_nodes);
   if (n_nodes == 0) return BGNN_OK;
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  BGNN_TRY(model_sync(ctx, m));
   const int hid = m->desc.hidden, in = m->desc.in_channels;
   void *px8, *ph;
   BGNN_TRY(ctx_workspace(ctx, 0, (size_t)n_nodes * 8 * sizeof(float), &px8));
@@ -895,6 +897,7 @@ int bgnn_heads(bgnn_ctx *ctx, bgnn_model *m, const float *hidden, int64_t n_node
   BGNN_REQUIRE(!o->hidden, "bgnn_heads: `hidden` is this call's input");
   if (n_nodes == 0) return BGNN_OK;
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  BGNN_TRY(model_sync(ctx, m));
   const int hid = m->desc.hidden;
   void *phid;
   BGNN_TRY(ctx_workspace(ctx, 3, (size_t)n_nodes * m->head_hidden_total * sizeof(float), &phid));
@@ -916,6 +919,8 @@ int bgnn_infer_tiles(bgnn_ctx *ctx, bgnn_model *m, const bgnn_tiles *tiles, cons
                      float thr_review, float norm_floor, float *classification, float *confidence, float *correction,
                      int64_t *n_nodes_out) {
   BGNN_REQUIRE(ctx && m && tiles && opts, "bgnn_infer_tiles: NULL argument");
+  BGNN_REQUIRE(m->ctx == ctx, "bgnn_infer_tiles: model belongs to another context");
+  BGNN_TRY(model_sync(ctx, m));
   bgnn_graph *g = nullptr;
   float *const grids[3] = {classification, confidence, correction};
   // (the compaction scan writes the node count there itself; a ragged batch's canvas fill zero-fills the result grids on its way)

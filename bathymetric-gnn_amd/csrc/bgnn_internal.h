@@ -12,6 +12,7 @@
 
 #include "../../include/bgnn.h"
 #include "../../include/bgnn_train.h"
+#include "../../include/bgnn_optim.h"
 
 namespace bgnn {
 
@@ -174,6 +175,22 @@ struct BgnnLayer {
   float *tr_Wt;     // SAGE [lin_l^T ; lin_r^T], GIN nn.2^T without the BatchNorm fold (else nullptr)
 };
 
+namespace bgnn {
+// Device tables of bgnn_model_refresh (optimizer.hip), built by model_pack.hip from the host packer's own loops: every packed
+// element that is a plain copy of a weight is one (destination, source) pair.
+struct RefreshTables {
+  int32_t *dev = nullptr;        // ONE device allocation holding the three tables below
+  int32_t *d_copy = nullptr;     // [n_copy][2]: blob[dst] = weights[src]
+  int32_t *d_relay = nullptr;    // [n_relay][2]: blob[dst] = blob[src] (re-layouts of the folded layer-0 weight; after the fold)
+  int32_t *d_vjob = nullptr;     // [n_vjob][4]: blob[dst] = sum_c weights[ae + c] * weights[we + c * edge_dim]  (dst, ae, we, 0)
+  int32_t n_copy = 0, n_relay = 0, n_vjob = 0;
+  // the extractor's second Linear folded into lin of layer 0 (GAT): blob[l0f_Wt + i HC0 + o] = sum_k fe_W1[k][i] * W0[o][k]
+  int32_t fold_cols = 0;         // HC0 (0: no fold, not a GAT model)
+  int32_t fe_W1 = 0, fe_b1 = 0, W0 = 0;   // offsets in the weight blob
+  int32_t l0f_Wt = 0, l0f_b = 0;          // offsets in the packed blob
+};
+}  // namespace bgnn
+
 struct bgnn_model {
   bgnn_ctx *ctx;
   bgnn_model_desc desc;       // the shape the KERNELS run: hidden / heads zero-padded to a supported width (bgnn_model_create)
@@ -206,6 +223,10 @@ struct bgnn_model {
   // that hold attribute id.  One small device table [layers][heads][3] per list, made on first use (model_canonical_V).
   std::vector<float> h_V;                             // host copy of every layer's V: [layers][heads_l][edge_dim]
   std::vector<std::pair<uint32_t, float *>> v3_tables;   // (packed list, device table [layers][max heads][3])
+  // bgnn_model_refresh (include/bgnn_optim.h): the training images were rewritten on the device from a new weight blob ...
+  bool eval_stale = false;    // ... the eval-only images, h_V and v3_tables were not: model_sync repacks / drops them before an
+                              // eval entry point reads the model (the training entry points read none of them)
+  bgnn::RefreshTables *refresh = nullptr;
 };
 
 struct bgnn_graph {
@@ -287,6 +308,12 @@ int ctx_upload(bgnn_ctx *ctx, const void *host, size_t bytes, void *dev);
 // ---- host helpers shared by bgnn_api.hip, model_pack.hip and train_api.hip ------------------
 int head_count(const bgnn_model_desc *d);                                            // model_pack.hip
 int model_canonical_V(bgnn_model *m, const bgnn_graph *g, const float **out);        // model_pack.hip
+// The single choke point of stale eval images: every public entry point that reads a model outside the training path calls it
+// first.  Not stale (a model that was never refreshed): one branch.  Stale: waits for the stream, downloads `raw`, runs the host
+// packer and uploads into the same allocation.
+int model_sync_slow(bgnn_ctx *ctx, bgnn_model *m);                                   // model_pack.hip
+inline int model_sync(bgnn_ctx *ctx, bgnn_model *m) { return m->eval_stale ? model_sync_slow(ctx, m) : BGNN_OK; }
+int model_refresh_tables(bgnn_ctx *ctx, bgnn_model *m);                              // model_pack.hip: builds m->refresh (idempotent)
 // The pieces the inference forward and the training forward share (bgnn_api.hip).  forward_begin: the input checks, the four
 // workspace tables, the foreign-graph self-loop check of GraphSAGE / GIN; rows = 0 on return: an empty graph, nothing to do
 struct FwdTables {

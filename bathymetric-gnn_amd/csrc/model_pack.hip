@@ -239,38 +239,41 @@ static void pad_model_weights(const bgnn_model_desc *d, const WeightLayout &a, c
   }
 }
 
-static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLayout &&wl, const float *w, bgnn_model **out) {
-  // (the generic kernels take 32 / 64 / 128 as long as a layer stays within 256 columns -- the heads' hidden/2 has to be a multiple of
-  //  16 and their three first layers side by side a multiple of 32; the fused kernels exist for hidden 64 only, the reference's
-  //  default: config/config.py:41)
-  BGNN_REQUIRE(d->hidden == 32 || d->hidden == 64 || d->hidden == 128, "hidden_channels=%d unsupported (32, 64 or 128)", d->hidden);
-  BGNN_REQUIRE(d->in_channels >= 1 && d->in_channels <= 8, "in_channels=%d unsupported (1..8)", d->in_channels);
-  BGNN_REQUIRE(d->num_layers >= 1 && d->num_layers <= 64, "num_gnn_layers=%d unsupported", d->num_layers);
-  BGNN_REQUIRE(d->gnn_type >= BGNN_GNN_GAT && d->gnn_type <= BGNN_GNN_GIN, "gnn_type=%d unknown", d->gnn_type);
+// Every image of a packed model as ONE host vector, and where each lies in it.  pack() is the host packer: bgnn_model_create
+// uploads its result, model_sync runs it again over the weights a refreshed model holds (the same allocation takes the result),
+// and bgnn_model_refresh's gather tables come from a run over an index-valued blob (model_refresh_tables).
+struct Packed {
+  struct LOff { size_t Wt, as, ad, V, sc, sh, b1, Wt2, b2, tr_bias, tr_bw, tr_bb, tr_Wt; };   // tr_*: unfolded, for bgnn_forward_train
+  std::vector<float> pk;
+  int HT = 0;
+  bool htab_ok = false, f16_ok = true;                 // f16_ok: every weight fits float16: else BGNN_SPLIT_F16 falls back to the bf16 split
+  size_t o_fe_W0t = 0, o_fe_b0 = 0, o_fe_W1t = 0, o_fe_b1 = 0, o_ones = 0, o_raw = 0;
+  size_t o_hW0 = 0, o_hW0t = 0, o_hb0 = 0, o_hW1 = 0, o_hb1 = 0, o_htab = 0, o_l0f_Wt = 0, o_l0f_b = 0;
+  size_t o_hW0sp = 0, o_l0fsp = 0, o_hW0sp16 = 0, o_l0fsp16 = 0, o_hW0bf = 0, o_l0fbf = 0, o_hW0fp = 0, o_l0fpm = 0;
+  size_t o_l0af_W = 0, o_l0af_sh = 0, o_l0f_blk = 0;
+  std::vector<LOff> lo;
+  std::vector<size_t> o_wsp, o_wsp16, o_wbf, o_wfp, o_plainfp, o_wblk;
+  std::vector<float> inv16;                            // 2^-S of each float16 image (pack_split)
+  float inv16_hd = 1.0f, inv16_l0f = 1.0f;
+  void pack(const bgnn_model_desc *d, const WeightLayout &wl, const float *w);
+  void assign(bgnn_model *m) const;                    // the model's pointers into m->blob (which holds pk)
+};
+
+void Packed::pack(const bgnn_model_desc *d, const WeightLayout &wl, const float *w) {
   const bool gat = d->gnn_type == BGNN_GNN_GAT;
-  // (`heads` only shapes a GAT backbone: models/gnn.py:125-143)
-  // (up to 256 columns a layer is one launch per kernel; 512 columns -- 8 heads of 64, 4 of 128 -- run the generic kernels in two
-  //  256-column blocks: Wt_blk)
-  BGNN_REQUIRE(!gat || (d->heads >= 1 && d->heads * d->hidden <= 512 && (d->heads & (d->heads - 1)) == 0),
-               "heads=%d unsupported (power of two, heads*hidden <= 512)", d->heads);
-  BGNN_REQUIRE(!gat || (d->edge_dim >= 1 && d->edge_dim <= 4), "edge_dim=%d unsupported (1..4)", d->edge_dim);
-  BGNN_REQUIRE(d->num_classes >= 1 && d->num_classes <= 16, "num_classes=%d unsupported", d->num_classes);
-  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
   const int hid = d->hidden, in = d->in_channels, hh = hid / 2, L = d->num_layers, ED = d->edge_dim;
   const int nh = head_count(d);
-  const int HT = ((nh * hh + 31) / 32) * 32;
-
-  std::vector<float> pk;
+  HT = ((nh * hh + 31) / 32) * 32;
+  pk.clear();
   auto reserve = [&](size_t n) { size_t o = pk.size(); pk.resize(o + ((n + 3) & ~(size_t)3), 0.0f); return o; };
   // feature extractor
-  size_t o_fe_W0t = reserve((size_t)8 * hid), o_fe_b0 = reserve(hid);
+  o_fe_W0t = reserve((size_t)8 * hid), o_fe_b0 = reserve(hid);
   for (int o = 0; o < hid; ++o) for (int i = 0; i < in; ++i) pk[o_fe_W0t + (size_t)i * hid + o] = w[wl.fe_W0 + (size_t)o * in + i];
   std::copy(w + wl.fe_b0, w + wl.fe_b0 + hid, pk.begin() + o_fe_b0);
-  size_t o_fe_W1t = reserve((size_t)hid * hid), o_fe_b1 = reserve(hid);
+  o_fe_W1t = reserve((size_t)hid * hid), o_fe_b1 = reserve(hid);
   for (int o = 0; o < hid; ++o) for (int i = 0; i < hid; ++i) pk[o_fe_W1t + (size_t)i * hid + o] = w[wl.fe_W1 + (size_t)o * hid + i];
   std::copy(w + wl.fe_b1, w + wl.fe_b1 + hid, pk.begin() + o_fe_b1);
-  struct LOff { size_t Wt, as, ad, V, sc, sh, b1, Wt2, b2, tr_bias, tr_bw, tr_bb, tr_Wt; };   // tr_*: unfolded, for bgnn_forward_train
-  std::vector<LOff> lo(L);
+  lo.assign(L, LOff{});
   // BatchNorm (eval) as y = x * s + t
   auto bn_fold = [&](const float *bw, const float *bb, const float *rm, const float *rv, int c, double &sc, double &sh) {
     sc = (double)bw[c] / std::sqrt((double)rv[c] + (double)d->bn_eps);
@@ -358,14 +361,14 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
     std::copy(bias, bias + W, pk.begin() + lo[l].tr_bias);
     std::copy(bw, bw + W, pk.begin() + lo[l].tr_bw); std::copy(bb, bb + W, pk.begin() + lo[l].tr_bb);
   }
-  const size_t o_ones = reserve(512);                     // (as wide as the widest layer: heads * hidden <= 512)
+  o_ones = reserve(512);                     // (as wide as the widest layer: heads * hidden <= 512)
   std::fill(pk.begin() + o_ones, pk.begin() + o_ones + 512, 1.0f);
   // heads: first layers concatenated column-wise, second layers packed
-  const size_t o_raw = reserve(wl.total);                // the blob as given: the backward's untransposed weights
+  o_raw = reserve(wl.total);                // the blob as given: the backward's untransposed weights
   std::copy(w, w + wl.total, pk.begin() + o_raw);
-  size_t o_hW0 = reserve((size_t)HT * hid);
-  size_t o_hW0t = reserve((size_t)hid * HT), o_hb0 = reserve(HT);
-  size_t o_hW1 = reserve((size_t)d->num_classes * hh + 2 * hh), o_hb1 = reserve(d->num_classes + 2);
+  o_hW0 = reserve((size_t)HT * hid);
+  o_hW0t = reserve((size_t)hid * HT), o_hb0 = reserve(HT);
+  o_hW1 = reserve((size_t)d->num_classes * hh + 2 * hh), o_hb1 = reserve(d->num_classes + 2);
   for (int k = 0; k < nh; ++k) {
     const float *W0 = w + wl.hd_W0[k], *b0 = w + wl.hd_b0[k], *W1 = w + wl.hd_W1[k], *b1 = w + wl.hd_b1[k];
     for (int o = 0; o < hh; ++o) for (int i = 0; i < hid; ++i) pk[o_hW0t + (size_t)i * HT + k * hh + o] = W0[(size_t)o * hid + i];
@@ -379,9 +382,9 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
   }
   // the fused heads kernel takes all of the above as ONE LDS image (a single DMA piece per workgroup): first-layer biases at 0,
   // second-layer row j at 96 + 32 j, second-layer biases at 288 (gat_layer_fused.hip, FusedLds::HEADW)
-  const size_t o_htab = reserve(296);
+  o_htab = reserve(296);
   const int n_rows1 = d->num_classes + nh - 1;
-  const bool htab_ok = HT <= 96 && hh == 32 && n_rows1 <= 6;
+  htab_ok = HT <= 96 && hh == 32 && n_rows1 <= 6;
   if (htab_ok) {
     std::copy(pk.begin() + o_hb0, pk.begin() + o_hb0 + HT, pk.begin() + o_htab);
     std::copy(pk.begin() + o_hW1, pk.begin() + o_hW1 + (size_t)n_rows1 * hh, pk.begin() + o_htab + 96);
@@ -391,7 +394,7 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
   // LocalFeatureExtractor ends in a Linear without activation (gnn.py:52-68) and GATConv's lin follows directly:
   // y = z W1^T + b1, xw = y W0^T  ==>  xw = z (W1^T W0^T) + b1 W0^T.  Folded in float64, one GEMM less per forward.
   const int HC0 = (L > 1 ? d->heads : 1) * hid;
-  size_t o_l0f_Wt = reserve((size_t)hid * HC0), o_l0f_b = reserve(HC0);
+  o_l0f_Wt = reserve((size_t)hid * HC0), o_l0f_b = reserve(HC0);
   for (int o = 0; o < HC0 && gat; ++o) {
     for (int i = 0; i < hid; ++i) {
       double s = 0.0;
@@ -405,11 +408,11 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
 
   // bf16 and float16 hi / lo images of the fused kernels' next-stage weights (layers 1.., the heads' first layers) and
   // of the folded layer-0 weight
-  std::vector<size_t> o_wsp(L, 0), o_wsp16(L, 0), o_wbf(L, 0), o_wfp(L, 0);
-  size_t o_hW0sp = 0, o_l0fsp = 0, o_hW0sp16 = 0, o_l0fsp16 = 0, o_hW0bf = 0, o_l0fbf = 0, o_hW0fp = 0, o_l0fpm = 0;
-  bool f16_ok = true;                  // every weight fits float16: else BGNN_SPLIT_F16 falls back to the bf16 split
-  std::vector<float> inv16(L, 1.0f);   // 2^-S of each float16 image (pack_split)
-  float inv16_hd = 1.0f, inv16_l0f = 1.0f;
+  o_wsp.assign(L, 0); o_wsp16.assign(L, 0); o_wbf.assign(L, 0); o_wfp.assign(L, 0);
+  o_hW0sp = 0, o_l0fsp = 0, o_hW0sp16 = 0, o_l0fsp16 = 0, o_hW0bf = 0, o_l0fbf = 0, o_hW0fp = 0, o_l0fpm = 0;
+  f16_ok = true;                  // every weight fits float16: else BGNN_SPLIT_F16 falls back to the bf16 split
+  inv16.assign(L, 1.0f);          // 2^-S of each float16 image (pack_split)
+  inv16_hd = 1.0f, inv16_l0f = 1.0f;
   if (gat) {
     for (int l = 1; l < L; ++l) {
       const int H = l == L - 1 ? 1 : d->heads, D = hid * d->heads, HC = H * hid;
@@ -448,7 +451,7 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
   // layer 0 "aggregate first" (bf16 path, default shape): the folded lin_0 weight as four per-head [64 k][64 columns] bf16 images
   // ([head][k-step][tile] KiB, accumulator-operand k order), and layer 0's folded shift with the folded lin_0 bias carried through the
   // BatchNorm scale (the attention coefficients of a node sum to 1: sum_j alpha_ij (W h_j + b) = W sum_j alpha_ij h_j + b)
-  size_t o_l0af_W = 0, o_l0af_sh = 0;
+  o_l0af_W = 0, o_l0af_sh = 0;
   if (gat && hid == 64 && L > 1 && d->heads == 4) {
     o_l0af_W = reserve((size_t)4 * 2048); o_l0af_sh = reserve(HC0);
     for (int hd = 0; hd < 4; ++hd) {
@@ -462,7 +465,7 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
   }
 
   // plain backbones (hidden 64): the layer weight in the fused layer kernel's column-permuted image (launch_fused_plain_layer)
-  std::vector<size_t> o_plainfp(L, 0);
+  o_plainfp.assign(L, 0);
   if (!gat && hid == 64) {
     for (int l = 0; l < L; ++l) o_plainfp[l] = reserve((size_t)(d->gnn_type == BGNN_GNN_SAGE ? 2 : 1) * hid * hid);
     for (int l = 0; l < L; ++l) {                          // (reserve may reallocate pk: sources taken afterwards)
@@ -473,8 +476,8 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
   }
 
   // layers wider than 256 columns: blocked images for the generic GEMM (layer 0: the folded and the unfolded weight)
-  std::vector<size_t> o_wblk(L, 0);
-  size_t o_l0f_blk = 0;
+  o_wblk.assign(L, 0);
+  o_l0f_blk = 0;
   if (gat && d->heads * hid > 256) {
     for (int l = 0; l + 1 < L; ++l) o_wblk[l] = reserve((size_t)(l == 0 ? hid : hid * d->heads) * d->heads * hid);
     if (L > 1) o_l0f_blk = reserve((size_t)hid * HC0);
@@ -489,12 +492,12 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
     }
   }
 
-  bgnn_model *m = new bgnn_model();
-  m->ctx = ctx; m->desc = *d; m->weights = std::move(wl); m->blob_floats = pk.size();
-  hipError_t e = hipMalloc((void **)&m->blob, pk.size() * sizeof(float));
-  if (e != hipSuccess) { delete m; set_error("hipMalloc(model) failed: %s", hipGetErrorString(e)); return BGNN_ERR_NOMEM; }
-  e = hipMemcpy(m->blob, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(m->blob); delete m; set_error("hipMemcpy(model) failed: %s", hipGetErrorString(e)); return BGNN_ERR_HIP; }
+}
+
+void Packed::assign(bgnn_model *m) const {
+  const bgnn_model_desc *d = &m->desc;
+  const bool gat = d->gnn_type == BGNN_GNN_GAT;
+  const int hid = d->hidden, L = d->num_layers, ED = d->edge_dim;
   m->fe_W0t = m->blob + o_fe_W0t; m->fe_b0 = m->blob + o_fe_b0; m->fe_W1t = m->blob + o_fe_W1t; m->fe_b1 = m->blob + o_fe_b1;
   m->l0f_Wt = m->blob + o_l0f_Wt; m->l0f_b = m->blob + o_l0f_b;
   m->l0f_Wsp = gat ? m->blob + o_l0fsp : nullptr;
@@ -508,6 +511,7 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
   m->l0af_W = o_l0af_W ? m->blob + o_l0af_W : nullptr;
   m->l0af_shift = o_l0af_sh ? m->blob + o_l0af_sh : nullptr;
   m->layers.resize(L);
+  m->h_V.clear();
   for (int l = 0; l < L && !gat; ++l) {
     BgnnLayer &Ly = m->layers[l];
     Ly = BgnnLayer{};
@@ -546,6 +550,35 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
   m->hd_W0t = m->blob + o_hW0t; m->hd_b0 = m->blob + o_hb0; m->hd_W1 = m->blob + o_hW1; m->hd_b1 = m->blob + o_hb1;
   m->hd_tab = htab_ok ? m->blob + o_htab : nullptr;
   m->raw = m->blob + o_raw; m->hd_W0 = m->blob + o_hW0;
+}
+
+static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLayout &&wl, const float *w, bgnn_model **out) {
+  // (the generic kernels take 32 / 64 / 128 as long as a layer stays within 256 columns -- the heads' hidden/2 has to be a multiple of
+  //  16 and their three first layers side by side a multiple of 32; the fused kernels exist for hidden 64 only, the reference's
+  //  default: config/config.py:41)
+  BGNN_REQUIRE(d->hidden == 32 || d->hidden == 64 || d->hidden == 128, "hidden_channels=%d unsupported (32, 64 or 128)", d->hidden);
+  BGNN_REQUIRE(d->in_channels >= 1 && d->in_channels <= 8, "in_channels=%d unsupported (1..8)", d->in_channels);
+  BGNN_REQUIRE(d->num_layers >= 1 && d->num_layers <= 64, "num_gnn_layers=%d unsupported", d->num_layers);
+  BGNN_REQUIRE(d->gnn_type >= BGNN_GNN_GAT && d->gnn_type <= BGNN_GNN_GIN, "gnn_type=%d unknown", d->gnn_type);
+  const bool gat = d->gnn_type == BGNN_GNN_GAT;
+  // (`heads` only shapes a GAT backbone: models/gnn.py:125-143)
+  // (up to 256 columns a layer is one launch per kernel; 512 columns -- 8 heads of 64, 4 of 128 -- run the generic kernels in two
+  //  256-column blocks: Wt_blk)
+  BGNN_REQUIRE(!gat || (d->heads >= 1 && d->heads * d->hidden <= 512 && (d->heads & (d->heads - 1)) == 0),
+               "heads=%d unsupported (power of two, heads*hidden <= 512)", d->heads);
+  BGNN_REQUIRE(!gat || (d->edge_dim >= 1 && d->edge_dim <= 4), "edge_dim=%d unsupported (1..4)", d->edge_dim);
+  BGNN_REQUIRE(d->num_classes >= 1 && d->num_classes <= 16, "num_classes=%d unsupported", d->num_classes);
+  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  Packed P;
+  P.pack(d, wl, w);
+  const std::vector<float> &pk = P.pk;
+  bgnn_model *m = new bgnn_model();
+  m->ctx = ctx; m->desc = *d; m->weights = std::move(wl); m->blob_floats = pk.size();
+  hipError_t e = hipMalloc((void **)&m->blob, pk.size() * sizeof(float));
+  if (e != hipSuccess) { delete m; set_error("hipMalloc(model) failed: %s", hipGetErrorString(e)); return BGNN_ERR_NOMEM; }
+  e = hipMemcpy(m->blob, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(m->blob); delete m; set_error("hipMemcpy(model) failed: %s", hipGetErrorString(e)); return BGNN_ERR_HIP; }
+  P.assign(m);
   *out = m;
   return BGNN_OK;
 }
@@ -580,6 +613,114 @@ int model_canonical_V(bgnn_model *m, const bgnn_graph *g, const float **out) {
   }
   m->v3_tables.emplace_back(key, d);
   *out = d;
+  return BGNN_OK;
+}
+
+// Stale eval images (bgnn_model_refresh rewrote only what training reads): the host packer over the weights the model holds, into
+// the allocation it has.  Waits for the stream twice (download, upload from pageable memory).
+int model_sync_slow(bgnn_ctx *ctx, bgnn_model *m) {
+  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  std::vector<float> w(m->weights.total);
+  BGNN_HIP_CHECK(hipMemcpyAsync(w.data(), m->raw, w.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  BGNN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  Packed P;
+  P.pack(&m->desc, m->weights, w.data());
+  BGNN_REQUIRE(P.pk.size() == m->blob_floats, "model_sync: the repacked model has %zu floats, the live one %zu", P.pk.size(), m->blob_floats);
+  BGNN_HIP_CHECK(hipMemcpyAsync(m->blob, P.pk.data(), P.pk.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  BGNN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  P.assign(m);                                         // (the float16 images may have come or gone with the weights' range; h_V)
+  for (auto &kv : m->v3_tables) (void)hipFree(kv.second);   // (the stream is idle: nothing reads them; remade on demand)
+  m->v3_tables.clear();
+  m->eval_stale = false;
+  return BGNN_OK;
+}
+
+// The gather tables of bgnn_model_refresh.  The host packer runs over a blob whose element i holds i + 1 (exact in float32 below
+// 2^24): wherever an image is a plain copy of a weight -- transposes, concatenations, stacked heads, column blocks -- the packed
+// value names its source, and a 0 is padding that stays 0.  Only the images the training path reads are taken (the others hold
+// products of indices); the re-layouts of the folded layer-0 weight come from the same packers over an index-valued l0f_Wt.
+int model_refresh_tables(bgnn_ctx *ctx, bgnn_model *m) {
+  if (m->refresh) return BGNN_OK;
+  const bgnn_model_desc *d = &m->desc;
+  const WeightLayout &wl = m->weights;
+  const size_t total = wl.total;
+  if (total >= ((size_t)1 << 24) || m->blob_floats >= ((size_t)1 << 31)) {
+    set_error("bgnn_model_refresh: a model of %zu weights is beyond the gather tables (2^24)", total);
+    return BGNN_ERR_UNSUPPORTED;
+  }
+  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  const bool gat = d->gnn_type == BGNN_GNN_GAT;
+  const int hid = d->hidden, L = d->num_layers, ED = d->edge_dim, hh = hid / 2;
+  std::vector<float> probe(total);
+  for (size_t i = 0; i < total; ++i) probe[i] = (float)(i + 1);
+  Packed P;
+  P.pack(d, wl, probe.data());
+  BGNN_REQUIRE(P.pk.size() == m->blob_floats, "bgnn_model_refresh: the probe pack has %zu floats, the live model %zu", P.pk.size(), m->blob_floats);
+  std::vector<int32_t> copy, relay, vjob;
+  bool ok = true;
+  auto take = [&](size_t off, size_t n) {
+    for (size_t i = off; i < off + n; ++i) {
+      const float v = P.pk[i];
+      if (v == 0.0f) continue;
+      if (!(v >= 1.0f && v <= (float)total && v == std::floor(v))) { ok = false; continue; }
+      copy.push_back((int32_t)i); copy.push_back((int32_t)v - 1);
+    }
+  };
+  const size_t HT = (size_t)P.HT;
+  take(P.o_fe_W0t, (size_t)8 * hid); take(P.o_fe_b0, hid); take(P.o_fe_W1t, (size_t)hid * hid); take(P.o_fe_b1, hid);
+  for (int l = 0; l < L; ++l) {
+    const Packed::LOff &O = P.lo[l];
+    const BgnnLayer &Ly = m->layers[l];
+    const size_t W = (size_t)Ly.width;
+    take(O.tr_bias, W); take(O.tr_bw, W); take(O.tr_bb, W);
+    if (gat) {
+      const size_t HC = (size_t)Ly.heads * hid;
+      take(O.Wt, (size_t)Ly.d_in * HC); take(O.as, HC); take(O.ad, HC);
+      if (P.o_wblk[l]) take(P.o_wblk[l], (size_t)Ly.d_in * HC);
+      for (int h = 0; h < Ly.heads; ++h)
+        for (int f = 0; f < ED; ++f) {
+          vjob.push_back((int32_t)(O.V + (size_t)h * ED + f));
+          vjob.push_back((int32_t)(wl.layers[l].ae + (size_t)h * hid));
+          vjob.push_back((int32_t)(wl.layers[l].We + (size_t)h * hid * ED + f));
+          vjob.push_back(0);
+        }
+    } else if (d->gnn_type == BGNN_GNN_GCN) {
+      take(O.Wt, (size_t)hid * hid);
+    } else if (d->gnn_type == BGNN_GNN_SAGE) {
+      take(O.tr_Wt, (size_t)2 * hid * hid);
+    } else {
+      take(O.Wt, (size_t)hid * hid); take(O.b1, hid); take(O.tr_Wt, (size_t)hid * hid);
+    }
+  }
+  take(P.o_hW0, HT * hid); take(P.o_hW0t, (size_t)hid * HT); take(P.o_hb0, HT);
+  take(P.o_hW1, (size_t)d->num_classes * hh + 2 * hh); take(P.o_hb1, (size_t)d->num_classes + 2);
+  BGNN_REQUIRE(ok, "bgnn_model_refresh: an image taken for a plain copy of the weights is none (internal)");
+  RefreshTables *T = new RefreshTables();
+  if (gat) {
+    const int HC0 = m->layers[0].heads * hid;
+    const size_t n0 = (size_t)hid * HC0;
+    T->fold_cols = HC0; T->fe_W1 = (int32_t)wl.fe_W1; T->fe_b1 = (int32_t)wl.fe_b1; T->W0 = (int32_t)wl.layers[0].W;
+    T->l0f_Wt = (int32_t)P.o_l0f_Wt; T->l0f_b = (int32_t)P.o_l0f_b;
+    std::vector<float> idx(n0), img(n0);
+    for (size_t i = 0; i < n0; ++i) idx[i] = (float)(i + 1);
+    auto relay_of = [&](size_t dst) {
+      for (size_t i = 0; i < n0; ++i) { relay.push_back((int32_t)(dst + i)); relay.push_back((int32_t)(P.o_l0f_Wt + (size_t)img[i] - 1)); }
+    };
+    if (P.o_l0fpm) { pack_tilegroup_image(idx.data(), hid, HC0, img.data(), 2); relay_of(P.o_l0fpm); }
+    if (P.o_l0f_blk) { pack_col_blocks(idx.data(), hid, HC0, img.data()); relay_of(P.o_l0f_blk); }
+  }
+  T->n_copy = (int32_t)(copy.size() / 2); T->n_relay = (int32_t)(relay.size() / 2); T->n_vjob = (int32_t)(vjob.size() / 4);
+  std::vector<int32_t> all;
+  all.insert(all.end(), copy.begin(), copy.end());
+  all.insert(all.end(), relay.begin(), relay.end());
+  all.insert(all.end(), vjob.begin(), vjob.end());
+  all.push_back(0);                                    // (never an empty allocation)
+  hipError_t e = hipMalloc((void **)&T->dev, all.size() * sizeof(int32_t));
+  if (e != hipSuccess) { delete T; set_error("hipMalloc(refresh tables) failed: %s", hipGetErrorString(e)); return BGNN_ERR_NOMEM; }
+  e = hipMemcpy(T->dev, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(T->dev); delete T; set_error("hipMemcpy(refresh tables) failed: %s", hipGetErrorString(e)); return BGNN_ERR_HIP; }
+  T->d_copy = T->dev; T->d_relay = T->d_copy + copy.size(); T->d_vjob = T->d_relay + relay.size();
+  m->refresh = T;
   return BGNN_OK;
 }
 
@@ -629,6 +770,7 @@ int bgnn_model_destroy(bgnn_model *m) {
   (void)hipStreamSynchronize(m->ctx->stream);
   (void)hipFree(m->blob);
   for (auto &kv : m->v3_tables) (void)hipFree(kv.second);
+  if (m->refresh) { (void)hipFree(m->refresh->dev); delete m->refresh; }
   delete m;
   return BGNN_OK;
 }

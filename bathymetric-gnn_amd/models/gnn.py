@@ -227,6 +227,7 @@ class BathymetricGNN(nn.Module):
         self.correction_head = CorrectionHead(hidden_channels, hidden_channels // 2, dropout) if predict_correction else None
         self._native = {}            # id(ctx) -> (weakref to ctx, handle): a model does not keep extra contexts alive
         self._native_key = None
+        self.__dict__["_flat"] = None    # set by training.FusedAdamW: the flat device master the parameters are views of (_flatten)
         for sub in (self.feature_extractor, self.classification_head, self.confidence_head, self.correction_head):
             if sub is not None:
                 object.__setattr__(sub, "_owner", weakref.ref(self))
@@ -325,6 +326,72 @@ class BathymetricGNN(nn.Module):
         self.__dict__.pop("_wv_struct", None)
         self._drop_native()
 
+    # ---- flat device master (training.FusedAdamW) ------------------------------------------------
+    def _flatten(self, ed: int):
+        """Give the model ONE flat float32 device tensor in ``pack_weights`` order (for edge width ``ed``) and make every parameter
+        and BatchNorm buffer of the blob a view into it.  Slots without a tensor (the edge weights of an ``edge_dim=None`` model)
+        are zeros nobody can reach.  The packed model is then kept up to date from the master on the device
+        (``bgnn_model_refresh``) instead of through ``pack_weights``; see ``_flat_ok`` for what ends that."""
+        named = dict(self.named_parameters())
+        named.update(dict(self.named_buffers()))
+        slots, off = [], 0
+        for k, n in self._blob_slots(named, ed):
+            slots.append((k, off, n))
+            off += n
+        ts = [named[k] for k, _, _ in slots if k is not None]
+        dev = ts[0].device
+        for k, _, _ in slots:
+            t = named.get(k) if k is not None else None
+            if t is not None and (t.dtype != torch.float32 or t.device.type != "cuda" or t.device != dev):
+                raise ValueError(f"{k}: {t.dtype} on {t.device}; the flat master holds float32 tensors of one GPU")
+        master = torch.zeros(off, dtype=torch.float32, device=dev)
+        views = []
+        with torch.no_grad():
+            for k, o, n in slots:
+                if k is None:
+                    continue
+                t = named[k]
+                v = master[o:o + n]
+                v.copy_(t.detach().reshape(-1))
+                t.data = v.view(t.shape)
+                views.append((t, o, n))
+        self._weights_version()
+        self.__dict__["_flat"] = {"master": master, "ed": int(ed), "n": off, "views": views, "struct": self.__dict__["_wv_struct"]}
+        return self.__dict__["_flat"]
+
+    def _flat_ok(self):
+        """The flat state while it still describes the model, else None (and it is dropped: the host repack takes over until
+        ``FusedAdamW.step`` flattens again).  It holds as long as the module tree is the one that was flattened -- ``.to()``,
+        ``load_state_dict``, ``invalidate_native`` and assigning a parameter or sub-module all rebuild the cached tensor list --
+        and every tensor still starts where its slot of the master does (``data_ptr``; ``p.data = other`` moves it)."""
+        fl = self.__dict__.get("_flat")
+        if fl is None:
+            return None
+        self._weights_version()                                  # (rebuilds the cached list if a slot of the tree changed)
+        if fl["struct"] is self.__dict__.get("_wv_struct"):
+            base = fl["master"].data_ptr()
+            if all(t.data_ptr() == base + 4 * o for t, o, _ in fl["views"]):
+                return fl
+        self.__dict__["_flat"] = None
+        return None
+
+    def _refresh_native(self, what: int):
+        """``bgnn_model_refresh`` from the flat master on every packed copy of its layout; copies of another edge width go."""
+        fl = self.__dict__["_flat"]
+        for cid, (wctx, h) in list((self._native or {}).items()):
+            ctx = wctx()
+            if ctx is None or ctx.handle is None or cid[1] != fl["ed"] or ctx.device != fl["master"].device:
+                try:
+                    if ctx is not None and ctx.handle is not None:
+                        ctx.lib.bgnn_model_destroy(h)
+                except Exception:
+                    pass
+                del self._native[cid]
+                continue
+            ctx.begin()
+            rt.check(ctx.lib.bgnn_model_refresh(ctx.handle, h, rt.ptr(fl["master"]), fl["n"], what))
+            ctx.end()
+
     def _apply(self, fn, *a, **k):
         self.__dict__.pop("_wv_struct", None)
         return super()._apply(fn, *a, **k)
@@ -357,13 +424,22 @@ class BathymetricGNN(nn.Module):
         """The packed model on ``ctx`` (one per library context -- and, for ``edge_dim=None`` models, per edge_attr width of the
         graphs they meet; rebuilt when a weight changes)."""
         key = self._weights_version()
+        fl = None
         if self._native is None or self._native_key != key:
-            self._drop_native()
+            fl = self._flat_ok() if self.__dict__.get("_flat") is not None else None
+            if fl is not None and self._native:
+                # a flattened model: something wrote through the views (or they were just made); the master holds the weights
+                self._refresh_native(rt.REFRESH_ALL)
+            else:
+                self._drop_native()
             self._native_key = key
         ed = self._edge_width(graph_edge_dim)
         ent = self._native.get((id(ctx), ed))
         if ent is None:
-            blob = self.pack_weights(ed)
+            if fl is None and self.__dict__.get("_flat") is not None:
+                fl = self._flat_ok()
+            flat = fl is not None and fl["ed"] == ed and fl["master"].device == ctx.device
+            blob = fl["master"].cpu().numpy() if flat else self.pack_weights(ed)
             desc = self._desc(ed)
             n = ctx.lib.bgnn_model_weight_count(C.byref(desc))
             if n != blob.size:
@@ -372,6 +448,8 @@ class BathymetricGNN(nn.Module):
             rt.check(ctx.lib.bgnn_model_create(ctx.handle, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
                                                blob.size, C.byref(h)))
             ent = self._native[(id(ctx), ed)] = (weakref.ref(ctx), h)
+            if flat:                                     # (the gather tables: their one allocation happens here, not in a step)
+                rt.check(ctx.lib.bgnn_model_refresh_prepare(ctx.handle, h))
             me, cid = weakref.ref(self), id(ctx)
             ctx.on_close(lambda: me() is not None and me()._drop_native(cid))
         return ent[1]
@@ -482,6 +560,11 @@ class BathymetricGNN(nn.Module):
                         bn.running_mean.mul_(1.0 - f).add_(mean[off:off + w].to(bn.running_mean.device), alpha=f)
                         bn.running_var.mul_(1.0 - f).add_(var[off:off + w].to(bn.running_var.device), alpha=f)
                     off += w
+            if self.__dict__.get("_flat") is not None and self._flat_ok() is not None:
+                # a flattened model: the statistics went through the views into the master.  Nothing a training step reads
+                # depends on them: the packed copies take the blob and mark their eval images stale -- no repack
+                self._refresh_native(rt.REFRESH_STATS)
+                self._native_key = self._weights_version()
         elif N > 0:
             ctx.begin()
             rt.check(ctx.lib.bgnn_forward(ctx.handle, model_h, g._handle, C.c_float(thr_auto), C.c_float(thr_review),

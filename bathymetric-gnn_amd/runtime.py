@@ -205,6 +205,29 @@ LOSS_COUNTS = ("n_masked", "false_positives", "shoal_false_positives", "deep_fal
                "feature_as_noise")
 LOSS_N_SUMS = 4
 
+
+
+class AdamWSlot(C.Structure):
+    """bgnn_adamw_slot: one updated tensor of the blob and the number of steps it has taken, this one included."""
+    _fields_ = [("offset", C.c_uint64), ("count", C.c_uint64), ("step", C.c_int64)]
+
+
+class AdamWParams(C.Structure):
+    """bgnn_adamw_params: the per-call scalars of bgnn_adamw_step (max_norm <= 0 or inf: no clipping)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("max_norm", C.c_double)]
+
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_optim.h declares (fused clip + AdamW, in-place model refresh)
+_OPTIM_SIGNATURES = {
+    "bgnn_adamw_step": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.POINTER(AdamWSlot), C.c_int32,
+                                  C.POINTER(AdamWParams), C.c_void_p]),
+    "bgnn_model_refresh_prepare": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bgnn_model_refresh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
+}
+ADAMW_CHUNK = 2048                 # BGNN_ADAMW_CHUNK
+REFRESH_ALL, REFRESH_STATS = 0, 1  # BGNN_REFRESH_*
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -215,7 +238,7 @@ class BgnnError(RuntimeError):
 
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
-    include/bgnn_noise.h and include/bgnn_loss.h.  Needs no GPU."""
+    include/bgnn_noise.h, include/bgnn_loss.h and include/bgnn_optim.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -227,7 +250,7 @@ def load_library(path: Optional[str] = None):
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = C.CDLL(p)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
-                list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()):
+                list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -4,8 +4,13 @@ optimizer step (the repack timed on its own: host packing and upload of the blob
 untaped training forward for comparison.  --loss fused|torch replaces the fixed linear form of the outputs by BathymetricGNNLoss on random
 labels (90 / 2 / 8 % class mix, mask = label 2), through the fused kernels or as separate torch operations (``forward_torch``); its
 forward is timed on its own ("loss") and its backward is part of "backward".  Prints one JSON line (milliseconds, medians over --steps) with the tape's bytes per node.
+--optimizer fused runs training.FusedAdamW (clip_grad_norm_ 1.0 + AdamW + the in-place refresh of the packed model) instead of torch's
+SGD and the host repack: "step" is the optimizer step with its refresh, "step_and_forward_share" adds what the following training forward
+pays because the weights changed (its time minus that of the same forward run once more), "pack_weights_calls" counts the host repacks
+of the timed iterations (0: the step never went through the host).
 
     python tools/train_step_bench.py [--gnn-type GAT|GraphSAGE|GIN] [--tiles 16] [--size 256] [--steps 10] [--warmup 3] [--loss fused|torch]
+                                     [--optimizer torch|fused]
 """
 import argparse
 import json
@@ -28,6 +33,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--loss", default=None, choices=["fused", "torch"])
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "fused"])
     a = ap.parse_args()
     from bathymetric_gnn_amd import synthetic
     from bathymetric_gnn_amd.data import GraphBuilder
@@ -40,7 +46,15 @@ def main():
     m = BathymetricGNN(in_channels=7, edge_dim=3, dropout=0.1, gnn_type=a.gnn_type)
     m.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
     m.to(dev).train()
-    opt = torch.optim.SGD(m.parameters(), lr=1e-6)
+    fused = a.optimizer == "fused"
+    if fused:
+        from bathymetric_gnn_amd.training import FusedAdamW
+        opt = FusedAdamW(m, lr=1e-6, max_grad_norm=1.0)
+        packs = []
+        real_pack = BathymetricGNN.pack_weights
+        BathymetricGNN.pack_weights = lambda self, *x, **k: (packs.append(1), real_pack(self, *x, **k))[1]
+    else:
+        opt = torch.optim.SGD(m.parameters(), lr=1e-6)
     N = g.num_nodes
     w = torch.randn(N, 3, device=dev)
     if a.loss:
@@ -60,6 +74,8 @@ def main():
         return r, (time.perf_counter() - t0) * 1e3
 
     rec = {"taped_forward": [], "backward": [], "repack_and_step": [], "untaped_forward": []}
+    if fused:
+        rec = {"taped_forward": [], "backward": [], "step": [], "step_and_forward_share": [], "untaped_forward": []}
     if a.loss:
         rec["loss"] = []
     for it in range(a.warmup + a.steps):
@@ -75,21 +91,32 @@ def main():
         with torch.no_grad():
             _, t_plain = timed(lambda: m(g))           # untaped training forward (repacks like every training forward)
         ctx = rt.get_context(dev)
-        t0 = time.perf_counter()
-        m.invalidate_native()                          # the repack on its own: host packing + upload of the blob
-        m.native(ctx, 3)
-        torch.cuda.synchronize()
-        t_pack = (time.perf_counter() - t0) * 1e3
+        if fused:
+            with torch.no_grad():
+                _, t_again = timed(lambda: m(g))       # the same forward once more: nothing changed but the running statistics
+            if it + 1 == a.warmup:
+                del packs[:]
+            if it >= a.warmup:
+                rec["step"].append(t_opt)
+                rec["step_and_forward_share"].append(t_opt + max(0.0, t_plain - t_again))
+        else:
+            t0 = time.perf_counter()
+            m.invalidate_native()                      # the repack on its own: host packing + upload of the blob
+            m.native(ctx, 3)
+            torch.cuda.synchronize()
+            t_pack = (time.perf_counter() - t0) * 1e3
+            if it >= a.warmup:
+                rec["repack_and_step"].append(t_opt + t_pack)
         if it >= a.warmup:
             rec["taped_forward"].append(t_fwd)
             rec["backward"].append(t_bwd)
             rec["untaped_forward"].append(t_plain)
-            rec["repack_and_step"].append(t_opt + t_pack)
             if a.loss:
                 rec["loss"].append(t_loss)
     tape_bytes = int(ctx.lib.bgnn_tape_bytes(m.native(ctx, 3), g._handle))
     res = {"metric": "train_step_ms", "gnn_type": a.gnn_type, "nodes": N, "tiles": a.tiles, "size": a.size,
            **({"loss_path": a.loss} if a.loss else {}),
+           **({"optimizer": "fused", "pack_weights_calls": len(packs)} if fused else {}),
            **{k: round(float(np.median(v)), 3) for k, v in rec.items()},
            "tape_bytes_per_node": round(tape_bytes / N, 1), "tape_gb": round(tape_bytes / 1e9, 3)}
     print(json.dumps(res))
