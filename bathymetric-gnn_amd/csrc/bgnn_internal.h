@@ -13,6 +13,7 @@
 #include "../../include/bgnn.h"
 #include "../../include/bgnn_train.h"
 #include "../../include/bgnn_optim.h"
+#include "model_images.h"   // WeightLayout, ImageMap: the weight blob's and the packed model's layouts (host only)
 
 namespace bgnn {
 
@@ -55,20 +56,6 @@ struct DevPool {
 struct ProfRecord {
   int kernel;
   hipEvent_t start, stop;
-};
-
-// Offsets (in floats) of every tensor of the weight blob (bgnn_model_weight_count order) -- of the gradient blob as well; filled by
-// model_pack.hip weight_layout.
-// Layer slots: GAT  W = lin.weight, as / ad / ae = att_src / att_dst / att_edge, We = lin_edge.weight, bias;
-//              GCN  W = lin.weight, bias;  GraphSAGE  W = lin_l.weight, bias = lin_l.bias, W2 = lin_r.weight;
-//              GIN  W = nn.0.weight, b1 = nn.0.bias, W2 = nn.2.weight, bias = nn.2.bias;
-// then every backbone's BatchNorm weight / bias / running_mean / running_var.  Slots a backbone does not have stay 0.
-struct WeightLayout {
-  size_t fe_W0, fe_b0, fe_W1, fe_b1;
-  struct Layer { size_t W, as, ad, ae, We, bias, bn_w, bn_b, bn_mean, bn_var, W2, b1; };
-  std::vector<Layer> layers;
-  size_t hd_W0[3], hd_b0[3], hd_W1[3], hd_b1[3];   // per head: mlp.0 weight / bias, mlp.3 weight / bias
-  size_t total;
 };
 
 }  // namespace bgnn
@@ -161,7 +148,7 @@ struct BgnnLayer {
   float *shift;     // [width]  (conv bias - mean) * scale + BN bias
   float *Wsp;       // Wt as a bf16 hi / lo split image for the bf16x3 matrix path (same byte geometry as Wt; see pack_split)
   float *Wsp16;     // the same with float16 parts (fp16x3), of W * 2^S ...
-  float Wsp16_inv = 1.0f;   // ... 2^-S: the kernels' accumulators are multiplied by it (model_pack.hip pack_split)
+  float Wsp16_inv = 1.0f;   // ... 2^-S: the kernels' accumulators are multiplied by it (model_images.h pack_split)
   float *Wfp;       // Wt with the columns of every row permuted for the fused exact-f32 kernel (gat_layer_fused.hip: WTileGroup)
   float *Wbf;       // Wt as a bf16 (hi only) image for the bf16 storage path: [D/16][NC/32][1 KiB] in MFMA A-fragment lane order
   // non-attention backbones (desc.gnn_type != BGNN_GNN_GAT): Wt = GCN lin^T [hid][hid] | SAGE [lin_l^T ; lin_r^T] [2 hid][hid]
@@ -176,7 +163,7 @@ struct BgnnLayer {
 };
 
 namespace bgnn {
-// Device tables of bgnn_model_refresh (optimizer.hip), built by model_pack.hip from the host packer's own loops: every packed
+// Device tables of bgnn_model_refresh (optimizer.hip): model_images.h refresh_plan, uploaded by model_pack.hip.  Every packed
 // element that is a plain copy of a weight is one (destination, source) pair.
 struct RefreshTables {
   int32_t *dev = nullptr;        // ONE device allocation holding the three tables below
@@ -197,8 +184,8 @@ struct bgnn_model {
   int logical_hidden = 0, logical_heads = 0;   // the caller's shape: widths of `hidden` in / out, bgnn_model_weight_count
   bool padded = false;
   bgnn::WeightLayout weights; // of `desc`: where `raw` (and the gradient blob of bgnn_backward) holds which tensor
-  float *blob = nullptr;      // one device allocation holding everything below
-  size_t blob_floats = 0;
+  bgnn::ImageMap images;      // of `desc`: where `blob` holds which image (fixed at creation: a refresh or a sync moves nothing)
+  float *blob = nullptr;      // one device allocation holding everything below, images.total floats
   float *fe_W0t, *fe_b0, *fe_W1t, *fe_b1;     // [in8][hid], [hid], [hid][hid], [hid]
   float *l0f_Wt, *l0f_b;      // [hid][HC0], [HC0]: second extractor layer folded into lin of layer 0 (no activation between)
   float *l0f_Wsp = nullptr, *l0f_Wsp16 = nullptr;   // l0f_Wt as bf16 / float16 hi / lo split images
@@ -306,7 +293,6 @@ int ctx_workspace(bgnn_ctx *ctx, int slot, size_t bytes, void **out);
 int ctx_upload(bgnn_ctx *ctx, const void *host, size_t bytes, void *dev);
 
 // ---- host helpers shared by bgnn_api.hip, model_pack.hip and train_api.hip ------------------
-int head_count(const bgnn_model_desc *d);                                            // model_pack.hip
 int model_canonical_V(bgnn_model *m, const bgnn_graph *g, const float **out);        // model_pack.hip
 // The single choke point of stale eval images: every public entry point that reads a model outside the training path calls it
 // first.  Not stale (a model that was never refreshed): one branch.  Stale: waits for the stream, downloads `raw`, runs the host

@@ -1,7 +1,7 @@
 // The optimizer part of the C ABI (include/bgnn_optim.h): gradient clipping + AdamW over the flat weight blob, and the refresh of a
 // live packed model from that blob.  Latency-bound kernels over <= 1 M elements: plain, one element per thread.
-// Compiled with -ffp-contract=off: the refresh's float64 dot products restate the host packer's (model_pack.hip) operation by
-// operation, and the step's sums have one fixed order.
+// Compiled with -ffp-contract=off: the refresh's float64 dot products restate the host packer's (model_images.h fill_images)
+// operation by operation, and the step's sums have one fixed order.
 #include <algorithm>
 #include <cmath>
 
