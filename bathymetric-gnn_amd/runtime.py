@@ -228,6 +228,17 @@ _OPTIM_SIGNATURES = {
 ADAMW_CHUNK = 2048                 # BGNN_ADAMW_CHUNK
 REFRESH_ALL, REFRESH_STATS = 0, 1  # BGNN_REFRESH_*
 
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_trainer.h declares (per-node training targets, epoch bookkeeping)
+_TRAINER_SIGNATURES = {
+    "bgnn_training_targets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7),
+    "bgnn_epoch_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "bgnn_epoch_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+TARGETS_SYNTHETIC, TARGETS_GROUND_TRUTH = 0, 1     # BGNN_TARGETS_*
+EPOCH_MAX_CLASSES = 16                             # BGNN_EPOCH_MAX_CLASSES
+EPOCH_ACC_BYTES = 72 + 8 * EPOCH_MAX_CLASSES * EPOCH_MAX_CLASSES   # BGNN_EPOCH_ACC_BYTES: double [6] | int64 nodes, correct, steps | int64 [16 * 16]
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -238,7 +249,7 @@ class BgnnError(RuntimeError):
 
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
-    include/bgnn_noise.h, include/bgnn_loss.h and include/bgnn_optim.h.  Needs no GPU."""
+    include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h and include/bgnn_trainer.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -250,7 +261,7 @@ def load_library(path: Optional[str] = None):
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = C.CDLL(p)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
-                list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()):
+                list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,614 @@
+"""``Trainer`` -- the reference's ``training/trainer.py`` on this package's device path: tiles resident in HBM (``TileStore``),
+per-node targets gathered by one kernel (``bgnn_training_targets``), the step's bookkeeping added up on the device
+(``EpochMetrics`` over ``bgnn_epoch_accumulate``), and the reference's epoch loop with validation, scheduler, early stopping
+(``StopRule``) and checkpoints around the taped forward, ``BathymetricGNNLoss`` and ``FusedAdamW``.
+
+What stays out: GDAL / survey file reading, torch_geometric loaders (``num_workers``, ``pin_memory``), progress bars, the unused
+``augment_rotations`` / ``augment_flips`` flags, wandb, multi-GPU training, and the models the backward refuses (GCN, zero-padded
+shapes, layers wider than 256 columns: ``Trainer`` raises at construction).
+
+Determinism.  An epoch draws from two places only: ``Trainer.step_plan(epoch)`` (the shuffle and the dropout seed of every step)
+and the noise of a synthetic store, a function of ``(seed, epoch, tile)``.  Two runs with equal seeds give equal bits, whatever
+ran before, and a resumed run continues the run it was saved from bit for bit."""
+from __future__ import annotations
+
+import dataclasses
+import logging
+from pathlib import Path
+from types import SimpleNamespace
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from torch.optim.lr_scheduler import CosineAnnealingWarmRestarts, ReduceLROnPlateau
+
+from .. import runtime as rt
+from ..config.constants import CORRECTION_NORM_CAP, CORRECTION_NORM_FLOOR
+from .losses import BathymetricGNNLoss, compute_class_weights, compute_correction_delta
+from .optim import FusedAdamW
+
+logger = logging.getLogger(__name__)
+
+# the reference's TrainingConfig (config/config.py:53-81): what an empty ``Config.training`` dict stands for
+TRAINING_DEFAULTS: Dict[str, Any] = {
+    "learning_rate": 1e-3, "weight_decay": 1e-4, "batch_size": 4, "epochs": 100, "scheduler": "cosine", "warmup_epochs": 5,
+    "patience": 15, "min_delta": 1e-4, "classification_weight": 1.0, "correction_weight": 0.5, "confidence_weight": 0.2,
+    "class_weights": None, "augment_rotations": True, "augment_flips": True, "augment_noise_intensity": True,
+}
+
+
+def training_settings(training: Any = None) -> SimpleNamespace:
+    """The training settings as attributes, with the reference's defaults filled in.  ``training``: the plain dict this package's
+    ``Config.training`` carries, an object with attributes (the reference's ``TrainingConfig``), a ``Config`` of either kind
+    (its ``training`` member is taken), or None.  Keys the reference does not know are ignored."""
+    if training is not None and not isinstance(training, dict) and hasattr(training, "training"):
+        training = training.training
+    out = dict(TRAINING_DEFAULTS)
+    for k in TRAINING_DEFAULTS:
+        if isinstance(training, dict):
+            if k in training:
+                out[k] = training[k]
+        elif training is not None and hasattr(training, k):
+            out[k] = getattr(training, k)
+    return SimpleNamespace(**out)
+
+
+def plan_ground_truth_tiles(labels: np.ndarray, tile_size: int = 512, overlap: int = 64,
+                            min_valid_ratio: float = 0.1) -> Tuple[List[Tuple[int, int, int, int]], Dict[int, int]]:
+    """The reference's scan of a ground-truth label band (``GroundTruthDataset._scan_ground_truth``, trainer.py:133-171), host
+    only: ``(row_start, col_start, row_end, col_end)`` of every full tile on the stride grid whose share of labelled cells
+    (``label >= 0``) reaches ``min_valid_ratio``, then the scan's single far-corner edge tile when the raster is larger than a tile
+    both ways and either extent is no multiple of the stride, and the class counts 0 / 1 / 2 over the labelled cells of the
+    tiles that were kept (overlaps counted as often as they are cut)."""
+    labels = np.asarray(labels)
+    if labels.ndim != 2:
+        raise ValueError(f"labels must be a 2-D grid, got shape {labels.shape}")
+    height, width = labels.shape
+    stride = tile_size - overlap
+    if stride <= 0:
+        raise ValueError("Tile size must be larger than overlap")
+    boxes: List[Tuple[int, int, int, int]] = []
+    counts = {0: 0, 1: 0, 2: 0}
+
+    def consider(r0, c0, r1, c1):
+        t = labels[r0:r1, c0:c1]
+        valid = t >= 0
+        if np.sum(valid) / valid.size >= min_valid_ratio:
+            boxes.append((r0, c0, r1, c1))
+            for c in (0, 1, 2):
+                counts[c] += int(np.sum(t[valid] == c))
+
+    for r0 in range(0, height - tile_size + 1, stride):
+        for c0 in range(0, width - tile_size + 1, stride):
+            consider(r0, c0, r0 + tile_size, c0 + tile_size)
+    if height > tile_size and width > tile_size and (height % stride != 0 or width % stride != 0):
+        consider(height - tile_size, width - tile_size, height, width)
+    return boxes, counts
+
+
+def dropout_seed(seed: int, global_step: int) -> int:
+    """The dropout seed of training step ``global_step`` (epoch * steps per epoch + step) of a run seeded ``seed``:
+    ``(seed mod 2^31) * 2^32 + (global_step mod 2^32)``."""
+    return ((int(seed) % (1 << 31)) << 32) | (int(global_step) % (1 << 32))
+
+
+class TileStore:
+    """The tiles of a training set, flat in HBM with the ``hw`` / ``res`` tables ``GraphBuilder.build_from_device`` takes: the
+    device-resident form of the reference's ``BathymetricGraphDataset(cache_tiles=True)`` (clean tiles, noise added per sample)
+    and of its ``GroundTruthDataset`` (label / difference / noisy-depth planes).  ``batch`` turns a list of tile indices into the
+    batch's graph and the target dict of ``BathymetricGNNLoss``, without leaving the device."""
+
+    def __init__(self, kind: str, hw, res, depth, mask, unc=None, labels=None, difference=None, class_counts=None,
+                 graph_builder=None, noise_generator=None, augment: bool = True, seed: int = 0, device=None):
+        from ..data import GraphBuilder, NoiseAugmentor, SyntheticNoiseGenerator
+        assert kind in ("synthetic", "ground_truth")
+        self.kind = kind
+        self.device = rt.resolve_device(device)
+        self.hw = np.ascontiguousarray(hw, np.int32).reshape(-1, 2)
+        self.res = np.ascontiguousarray(res, np.float64).reshape(-1, 2)
+        cells = self.hw[:, 0].astype(np.int64) * self.hw[:, 1]
+        self.offsets = np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
+        self.depth, self.mask, self.unc, self.labels, self.difference = depth, mask, unc, labels, difference
+        for t in (depth, mask, unc, labels, difference):
+            if t is not None and t.numel() != int(self.offsets[-1]):
+                raise ValueError("tile table and planes disagree on the number of cells")
+        self.uniform = len(self.hw) > 0 and bool((self.hw == self.hw[0]).all())
+        self.seed = int(seed)
+        self.graph_builder = graph_builder if graph_builder is not None else GraphBuilder(device=self.device)
+        self.augment = bool(augment)
+        self.noise_generator = self.noise_augmentor = None
+        if kind == "synthetic":
+            self.noise_generator = noise_generator if noise_generator is not None else SyntheticNoiseGenerator(seed=self.seed)
+            self.noise_generator.device = self.device
+            self.noise_augmentor = NoiseAugmentor(self.noise_generator, seed=self.seed) if augment else None
+        else:
+            self._class_counts = dict(class_counts or {0: 0, 1: 0, 2: 0})
+
+    # ---- constructors --------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_tiles(cls, depths, valid_masks=None, uncertainties=None, resolutions=None, device=None, **kw) -> "TileStore":
+        """Clean tiles (host arrays) for synthetic noise.  ``valid_masks[i]`` None: ``isfinite(depth)``; ``uncertainties``: for
+        every tile or for none; ``resolutions``: one ``(x, y)`` per tile (default 1.0).  Keywords: ``graph_builder``,
+        ``noise_generator``, ``augment`` (True: ``NoiseAugmentor`` with a drawn intensity per sample), ``seed``."""
+        from ..data import GraphBuilder
+        device = rt.resolve_device(device)
+        gb = kw.get("graph_builder") or GraphBuilder(device=device)
+        kw["graph_builder"] = gb
+        n = len(depths)
+        if n == 0:
+            raise ValueError("a TileStore needs at least one tile")
+        resolutions = [(1.0, 1.0)] * n if resolutions is None else list(resolutions)
+        hw, res, d, m, u = gb.upload_tiles(list(depths), None if valid_masks is None else list(valid_masks), uncertainties, resolutions)
+        return cls("synthetic", hw, res, d.to(device), m.to(device), None if u is None else u.to(device), device=device, **kw)
+
+    @classmethod
+    def from_grid(cls, grid, tile_manager, device=None, **kw) -> "TileStore":
+        """The tiles ``tile_manager.iterate_tiles(grid, skip_empty=True)`` yields (trainer.py:351), at the grid's resolution."""
+        tiles = list(tile_manager.iterate_tiles(grid, skip_empty=True))
+        unc = [t.uncertainty for t in tiles] if tiles and tiles[0].uncertainty is not None else None
+        return cls.from_tiles([t.data for t in tiles], [t.valid_mask for t in tiles], unc, [grid.resolution] * len(tiles),
+                              device=device, **kw)
+
+    @classmethod
+    def from_ground_truth(cls, labels, difference, noisy_depth, uncertainty=None, resolution=(1.0, 1.0), tile_size: int = 512,
+                          overlap: int = 64, min_valid_ratio: float = 0.1, device=None, **kw) -> "TileStore":
+        """A ground-truth raster as its bands hold it: 1 labels (0 seafloor, 2 noise, -1 nodata), 2 difference (noisy - clean),
+        3 noisy depth, 5 uncertainty (optional).  Cut with ``plan_ground_truth_tiles``; a cell is valid where its label is
+        >= 0."""
+        device = rt.resolve_device(device)
+        labels = np.asarray(labels).astype(np.int32)
+        boxes, counts = plan_ground_truth_tiles(labels, tile_size, overlap, min_valid_ratio)
+        if not boxes:
+            raise ValueError("the ground-truth raster yields no tile")
+        planes = {"labels": (labels, np.int32), "difference": (difference, np.float32), "depth": (noisy_depth, np.float32)}
+        if uncertainty is not None:
+            planes["unc"] = (uncertainty, np.float32)
+        flat = {}
+        for k, (arr, dt) in planes.items():
+            arr = np.asarray(arr)
+            if arr.shape != labels.shape:
+                raise ValueError(f"{k} has shape {arr.shape}, labels {labels.shape}")
+            flat[k] = torch.from_numpy(np.concatenate([np.ascontiguousarray(arr[r0:r1, c0:c1], dt).ravel()
+                                                       for r0, c0, r1, c1 in boxes])).to(device)
+        hw = np.array([(r1 - r0, c1 - c0) for r0, c0, r1, c1 in boxes], np.int32)
+        res = np.array([(float(resolution[0]), float(resolution[1]))] * len(boxes), np.float64)
+        store = cls("ground_truth", hw, res, flat["depth"], (flat["labels"] >= 0).view(torch.uint8), flat.get("unc"),
+                    labels=flat["labels"], difference=flat["difference"], class_counts=counts, device=device, **kw)
+        store.boxes = boxes
+        return store
+
+    # ---- access ----------------------------------------------------------------------------------------------------------
+    def __len__(self) -> int:
+        return int(self.hw.shape[0])
+
+    @property
+    def in_channels(self) -> int:
+        return self.graph_builder.n_node_columns(self.unc is not None)
+
+    def _gather(self, idx: np.ndarray):
+        """hw, res and the planes of the tiles ``idx``, concatenated in that order (one index-copy per plane)."""
+        planes = {"depth": self.depth, "mask": self.mask, "unc": self.unc, "labels": self.labels, "difference": self.difference}
+        if self.uniform:
+            cells = int(self.hw[0, 0]) * int(self.hw[0, 1])
+            sel = torch.as_tensor(idx, dtype=torch.int64).to(self.device)
+            out = {k: None if p is None else p.view(len(self), cells).index_select(0, sel).reshape(-1) for k, p in planes.items()}
+        else:
+            cell_idx = np.concatenate([np.arange(self.offsets[i], self.offsets[i + 1], dtype=np.int64) for i in idx])
+            sel = torch.from_numpy(cell_idx).to(self.device)
+            out = {k: None if p is None else p.index_select(0, sel) for k, p in planes.items()}
+        return np.ascontiguousarray(self.hw[idx]), np.ascontiguousarray(self.res[idx]), out
+
+    def batch(self, indices: Sequence[int], epoch: int = 0, noise=None):
+        """``(graph, targets)`` of the tiles ``indices`` in epoch ``epoch``.  A synthetic store adds noise first
+        (``NoiseAugmentor.augment_batch``, or ``generate_batch`` with ``augment=False``; ``noise``: another augmentor or
+        generator for this call) with the sample index ``epoch * len(store) + i`` for tile ``i``, so the noise is a function of
+        (seed, epoch, tile) alone; the graph is built from the noisy depth.  ``targets``: ``class_labels`` (int64),
+        ``correction_targets`` (float32), ``noise_mask`` (bool), one row per node."""
+        idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
+        if idx.size == 0 or idx.min() < 0 or idx.max() >= len(self):
+            raise IndexError(f"tile indices {idx.tolist()} outside a store of {len(self)} tiles")
+        ctx = rt.get_context(self.device)
+        hw, res, p = self._gather(idx)
+        if self.kind == "synthetic":
+            source = noise if noise is not None else (self.noise_augmentor if self.noise_augmentor is not None else self.noise_generator)
+            samples = [int(epoch) * len(self) + int(i) for i in idx]
+            if hasattr(source, "augment_batch"):
+                nb = source.augment_batch(hw, p["depth"], p["mask"], sample_indices=samples, ctx=ctx)
+            else:
+                nb = source.generate_batch(hw, p["depth"], p["mask"], sample_indices=samples, ctx=ctx)
+            depth, mode = nb.noisy_depth, rt.TARGETS_SYNTHETIC
+            a, b, labels, nmask = nb.noisy_depth, p["depth"], nb.classification, nb.noise_mask.view(torch.uint8)
+        else:
+            depth, mode = p["depth"], rt.TARGETS_GROUND_TRUTH
+            a, b, labels, nmask = p["difference"], None, p["labels"], None
+        graph = self.graph_builder.build_from_device(hw, res, depth, p["mask"], p["unc"], ctx=ctx)
+        targets = training_targets_fused(graph, mode, a, b, labels, nmask)
+        return graph, targets
+
+
+def training_targets_fused(graph, mode: int, a: torch.Tensor, b: Optional[torch.Tensor], labels: torch.Tensor,
+                           noise_mask: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """``bgnn_training_targets`` on a graph from ``build_from_device`` and the flat per-cell planes of its batch (mode 0: noisy,
+    clean, int64 classification, uint8 / bool noise mask -- what ``data.training_targets`` takes; mode 1: difference, None, int32
+    labels, None).  Returns the loss's target dict."""
+    ctx = graph._ctx
+    dev = ctx.device
+    cells = int((graph._hw[:, 0].astype(np.int64) * graph._hw[:, 1]).sum())
+    want = {"a": torch.float32, "b": torch.float32, "labels": torch.int64 if mode == rt.TARGETS_SYNTHETIC else torch.int32}
+    planes = {"a": a, "b": b, "labels": labels, "noise_mask": noise_mask}
+    for k, t in list(planes.items()):
+        if t is None:
+            continue
+        if k == "noise_mask":
+            if t.dtype not in (torch.uint8, torch.bool):
+                raise TypeError(f"noise_mask must be uint8 or bool, got {t.dtype}")
+            t = t.view(torch.uint8) if t.dtype == torch.bool else t
+        elif t.dtype != want[k]:
+            raise TypeError(f"{k} must be {want[k]}, got {t.dtype}")
+        if t.numel() != cells or t.device != dev:
+            raise ValueError(f"{k} must hold one entry per cell of the graph's batch ({cells}) on {dev}")
+        planes[k] = t.contiguous().view(-1)
+    if mode == rt.TARGETS_SYNTHETIC and (planes["b"] is None or planes["noise_mask"] is None):
+        raise ValueError("mode 0 takes the clean plane and the noise mask")
+    n = graph.num_nodes
+    y = torch.empty(n, dtype=torch.int64, device=dev)
+    target = torch.empty(n, dtype=torch.float32, device=dev)
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n > 0:
+        ctx.begin()
+        rt.check(ctx.lib.bgnn_training_targets(ctx.handle, graph._handle, int(mode), rt.ptr(planes["a"]), rt.ptr(planes["b"]),
+                                               rt.ptr(planes["labels"]), rt.ptr(planes["noise_mask"]), rt.ptr(y), rt.ptr(target),
+                                               rt.ptr(mask)))
+        ctx.end()
+    return {"class_labels": y, "correction_targets": target, "noise_mask": mask.view(torch.bool)}
+
+
+class EpochMetrics:
+    """One accumulator block of ``bgnn_epoch_accumulate`` (include/bgnn_trainer.h) and its single read-back."""
+
+    def __init__(self, device=None):
+        self.device = rt.resolve_device(device)
+        self._ctx = rt.get_context(self.device)
+        self._acc = torch.zeros(rt.EPOCH_ACC_BYTES // 8, dtype=torch.int64, device=self.device)
+        self._idle = None            # zero terms / counts for a step that has no loss statistics (an empty batch)
+        self.num_classes = None
+
+    def reset(self):
+        ctx = self._ctx
+        ctx.begin()
+        rt.check(ctx.lib.bgnn_epoch_reset(ctx.handle, rt.ptr(self._acc)))
+        ctx.end()
+
+    def accumulate(self, graph, terms: torch.Tensor, counts: torch.Tensor, num_classes: int):
+        """The raw entry point: ``terms`` float32 [6], ``counts`` int64 [C * C + 7] on the device; n comes from ``graph``."""
+        if terms.dtype != torch.float32 or terms.numel() < 6 or counts.dtype != torch.int64 or \
+                counts.numel() < num_classes * num_classes + len(rt.LOSS_COUNTS) or not terms.is_contiguous() or not counts.is_contiguous():
+            raise ValueError("terms must be float32 [6] and counts int64 [C * C + 7], contiguous")
+        ctx = self._ctx
+        self.num_classes = int(num_classes)
+        ctx.begin()
+        rt.check(ctx.lib.bgnn_epoch_accumulate(ctx.handle, graph._handle, rt.ptr(terms), rt.ptr(counts), int(num_classes),
+                                               rt.ptr(self._acc)))
+        ctx.end()
+
+    def update(self, graph, losses: Dict[str, torch.Tensor], criterion: BathymetricGNNLoss):
+        """Add one step: ``losses`` as ``criterion`` returned them for ``graph``'s batch, ``criterion.last_stats`` from that call.
+        No host wait."""
+        stats = criterion.last_stats
+        if stats is None:
+            # the loss took its torch path: an empty batch (nothing to add; the kernel sees n = 0 and reads nothing)
+            if graph.num_nodes != 0:
+                raise rt.BgnnError("EpochMetrics.update: the loss call left no device statistics (BathymetricGNNLoss ran its torch path)")
+            if self._idle is None:
+                c = rt.EPOCH_MAX_CLASSES
+                self._idle = (torch.zeros(6, dtype=torch.float32, device=self.device),
+                              torch.zeros(c * c + len(rt.LOSS_COUNTS), dtype=torch.int64, device=self.device))
+            known = self.num_classes
+            self.accumulate(graph, self._idle[0], self._idle[1], known or 2)
+            self.num_classes = known
+            return
+        conf = stats["confusion"]
+        c = int(conf.shape[0])
+        if stats["n_masked"].data_ptr() != conf.data_ptr() + 8 * c * c:       # not the loss pass's own block: assemble one
+            counts = torch.cat([conf.reshape(-1)] + [stats[k].reshape(1) for k in rt.LOSS_COUNTS])
+        else:
+            counts = torch.as_strided(conf, (c * c + len(rt.LOSS_COUNTS),), (1,))
+        first = losses[rt.LOSS_TERMS[0]]
+        if all(losses[k].data_ptr() == first.data_ptr() + 4 * i and losses[k].dtype == torch.float32
+               for i, k in enumerate(rt.LOSS_TERMS)):
+            terms = torch.as_strided(first.detach(), (6,), (1,))
+        else:
+            terms = torch.stack([losses[k].detach().to(torch.float32) for k in rt.LOSS_TERMS])
+        self.accumulate(graph, terms, counts, c)
+
+    def result(self) -> Dict[str, Any]:
+        """The epoch's single device-to-host copy: ``loss`` (sum of total * n over the nodes, 0 when empty), ``accuracy``, the
+        five term means, ``confusion`` [C, C], ``nodes``, ``steps``."""
+        host = self._acc.cpu().numpy()
+        sums = host[:6].view(np.float64)
+        nodes, correct, steps = (int(v) for v in host[6:9])
+        c = self.num_classes or 0
+        out = {"loss": float(sums[5]) / nodes if nodes > 0 else 0, "accuracy": correct / nodes if nodes > 0 else 0}
+        for i, k in enumerate(rt.LOSS_TERMS[:5]):
+            out[k] = float(sums[i]) / nodes if nodes > 0 else 0
+        out["confusion"] = host[9:9 + c * c].reshape(c, c).copy()
+        out["nodes"], out["steps"] = nodes, steps
+        return out
+
+
+class StopRule:
+    """Early stopping as the reference's loop does it (trainer.py:698-706): an epoch improves when its validation loss is below
+    the best so far by more than ``min_delta``; ``patience`` epochs in a row without improvement stop the run."""
+
+    def __init__(self, patience: int, min_delta: float):
+        self.patience, self.min_delta = patience, min_delta
+        self.best = float("inf")
+        self.counter = 0
+
+    def update(self, val_loss: float) -> Tuple[bool, bool]:
+        """``(improved, stop)``."""
+        if val_loss < self.best - self.min_delta:
+            self.best = val_loss
+            self.counter = 0
+            return True, False
+        self.counter += 1
+        return False, self.counter >= self.patience
+
+
+class Trainer:
+    """Training manager for bathymetric GNN (the reference's ``Trainer``), over ``TileStore`` s.
+
+    ``config``: a ``Config`` of this package (``training`` a plain dict) or of the reference; the training settings are read
+    through ``training_settings``.  The model is moved to the store's GPU.  A model the backward pass refuses (GCN, a
+    zero-padded shape, layers wider than 256 columns) raises here, with the backward's message."""
+
+    def __init__(self, config, model, train_store: TileStore, val_store: Optional[TileStore] = None, output_dir=None,
+                 seed: int = 0):
+        self.config = config
+        self.model = model
+        self.train_dataset = self.train_store = train_store
+        self.val_dataset = self.val_store = val_store
+        self.output_dir = Path(output_dir) if output_dir else Path("./outputs")
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+        self.seed = int(seed)
+        self.settings = training_settings(config)
+        self.device = train_store.device
+        self.model.to(self.device)
+        self._refuse_untrainable()
+
+        self.optimizer = FusedAdamW(model, lr=self.settings.learning_rate, weight_decay=self.settings.weight_decay,
+                                    max_grad_norm=1.0)
+        if self.settings.scheduler == "cosine":
+            self.scheduler = CosineAnnealingWarmRestarts(self.optimizer, T_0=10, T_mult=2)
+        elif self.settings.scheduler == "plateau":
+            self.scheduler = ReduceLROnPlateau(self.optimizer, mode="min", factor=0.5, patience=5)
+        else:
+            self.scheduler = None
+
+        class_weights, correction_delta = self._compute_training_stats()
+        if class_weights is not None:
+            class_weights = class_weights.to(self.device)
+            logger.info(f"Class weights: {class_weights.tolist()}")
+        logger.info(f"Correction Huber delta: {correction_delta:.3f}")
+        self.criterion = BathymetricGNNLoss(
+            class_weights=class_weights,
+            classification_weight=self.settings.classification_weight,
+            correction_weight=self.settings.correction_weight,
+            confidence_weight=self.settings.confidence_weight,
+            correction_delta=correction_delta,
+        )
+
+        self.current_epoch = 0
+        self.stop_rule = StopRule(self.settings.patience, self.settings.min_delta)
+        self.history: Dict[str, List[float]] = {"train_loss": [], "val_loss": [], "train_acc": [], "val_acc": []}
+        self._next_epoch = 0
+        self.train_metrics = EpochMetrics(self.device)
+        self.val_metrics = EpochMetrics(self.device)
+        logger.info(f"Trainer initialized, device: {self.device}")
+
+    # (the reference keeps these two as plain members; here they live in the stop rule)
+    best_val_loss = property(lambda self: self.stop_rule.best, lambda self, v: setattr(self.stop_rule, "best", v))
+    patience_counter = property(lambda self: self.stop_rule.counter, lambda self, v: setattr(self.stop_rule, "counter", v))
+
+    def _refuse_untrainable(self):
+        """Ask the library whether this model has a backward pass (``bgnn_tape_bytes`` on a 4 x 4 graph)."""
+        from ..data import GraphBuilder
+        ctx = rt.get_context(self.device)
+        gb = self.train_store.graph_builder
+        probe = GraphBuilder(connectivity=gb.connectivity, include_self_loops=gb.include_self_loops, node_features=gb.node_features,
+                             edge_features=gb.edge_features, device=self.device)
+        g = probe.build_graphs([np.zeros((4, 4), np.float32)], None, None, [(1.0, 1.0)])
+        handle = self.model.native(ctx, g.edge_dim)
+        if int(ctx.lib.bgnn_tape_bytes(handle, g._handle)) == 0:
+            raise NotImplementedError(ctx.lib.bgnn_last_error().decode(errors="replace"))
+
+    # ---- statistics of the training set ----------------------------------------------------------------------------------
+    def _compute_training_stats(self) -> Tuple[Optional[torch.Tensor], float]:
+        """Class weights and the Huber delta from the training store (trainer.py:549-660): a synthetic store's first
+        ``min(len, 50)`` samples (epoch 0) give the class counts and the normalised corrections of their noise cells; a
+        ground-truth store brings its scanned class counts and ``linspace`` of ``min(len, 100)`` samples give the corrections.
+        Counting and selection run on the device; the selected magnitudes come to the host once."""
+        num_classes = int(self.config.model.num_classes) if hasattr(self.config, "model") else int(self.model.num_classes)
+        try:
+            store = self.train_store
+            counts = torch.zeros(num_classes, dtype=torch.long, device=self.device)
+            selected = []
+            scanned = hasattr(store, "_class_counts")
+            if scanned:
+                counts = torch.tensor([int(store._class_counts.get(c, 0)) for c in range(num_classes)], dtype=torch.long,
+                                      device=self.device)
+                num_samples = min(len(store), 100)
+                logger.info(f"Sampling {num_samples} tiles for correction statistics...")
+                sample_indices = [int(i) for i in np.linspace(0, len(store) - 1, num_samples, dtype=int)]
+            else:
+                sample_indices = list(range(min(len(store), 50)))
+            bs = max(1, int(self.settings.batch_size))
+            for k in range(0, len(sample_indices), bs):
+                _, t = store.batch(sample_indices[k:k + bs], epoch=0)
+                y, mask, target = t["class_labels"], t["noise_mask"], t["correction_targets"]
+                if not scanned and y.numel() > 0:
+                    ok = (y >= 0) & (y < num_classes)
+                    counts += torch.bincount(y[ok], minlength=num_classes)
+                norm = target[mask]
+                selected.append(norm[torch.isfinite(norm)])
+            counts = counts.cpu()
+            class_weights = None
+            if counts.sum() > 0:
+                logger.info(f"Class distribution: {dict(enumerate(counts.tolist()))}")
+                # (on the host, as the reference computes them: the weights are then the same bits as a host replay's)
+                class_weights = compute_class_weights(torch.arange(num_classes).repeat_interleave(counts.clamp(min=1)),
+                                                      num_classes=num_classes, smoothing=0.1)
+            else:
+                logger.warning("No valid labels found, skipping class weights")
+            combined = torch.cat(selected).cpu().numpy() if selected else np.zeros(0, np.float32)
+            if combined.size > 0:
+                capped = np.clip(combined, -CORRECTION_NORM_CAP, CORRECTION_NORM_CAP)
+                correction_delta = compute_correction_delta(capped, percentile=95.0, min_delta=1.0)
+                logger.info(f"Correction stats (normalized by local_std): mean |correction|={np.mean(np.abs(combined)):.3f}, "
+                            f"max |correction|={np.max(np.abs(combined)):.3f}, "
+                            f"95th percentile={np.percentile(np.abs(combined), 95):.3f}")
+            else:
+                correction_delta = 1.0
+                logger.warning("No noise corrections found, using default delta=1.0")
+            return class_weights, correction_delta
+        except Exception as e:
+            logger.warning(f"Failed to compute training stats: {e}")
+            return None, 1.0
+
+    # ---- the plan of an epoch --------------------------------------------------------------------------------------------
+    def step_plan(self, epoch: int, validation: bool = False) -> List[Tuple[np.ndarray, Optional[int]]]:
+        """``(tile indices, dropout seed)`` of every step of epoch ``epoch``.  Training: the tiles in the order
+        ``np.random.default_rng([seed, epoch]).permutation(len(train_store))``, cut into pieces of ``batch_size``; the dropout
+        seed of step ``k`` is ``dropout_seed(seed, epoch * steps_per_epoch + k)`` and is written to ``model.dropout_seed``
+        before the step's forward.  ``validation=True``: the validation store in its own order, seed None (no dropout in
+        ``eval()``).  This method, with the stores' noise (a function of (seed, epoch, tile)), is the whole source of randomness
+        of an epoch."""
+        store = self.val_store if validation else self.train_store
+        bs = max(1, int(self.settings.batch_size))
+        n = len(store)
+        order = np.arange(n, dtype=np.int64) if validation else \
+            np.random.default_rng([self.seed, int(epoch)]).permutation(n).astype(np.int64)
+        pieces = [order[k:k + bs] for k in range(0, n, bs)]
+        if validation:
+            return [(p, None) for p in pieces]
+        return [(p, dropout_seed(self.seed, int(epoch) * len(pieces) + k)) for k, p in enumerate(pieces)]
+
+    # ---- epochs ------------------------------------------------------------------------------------------------------------
+    def _train_epoch(self) -> Dict[str, float]:
+        """Run one training epoch."""
+        self.model.train()
+        metrics = self.train_metrics
+        metrics.reset()
+        for indices, drop_seed in self.step_plan(self.current_epoch):
+            graph, targets = self.train_store.batch(indices, self.current_epoch)
+            self.model.dropout_seed = drop_seed
+            self.optimizer.zero_grad()
+            outputs = self.model(graph)
+            losses = self.criterion(outputs, targets)
+            losses["total"].backward()
+            self.optimizer.step()
+            metrics.update(graph, losses, self.criterion)
+        return metrics.result()
+
+    def _validate_epoch(self) -> Dict[str, float]:
+        """Run one validation epoch."""
+        self.model.eval()
+        metrics = self.val_metrics
+        metrics.reset()
+        with torch.no_grad():
+            for indices, _ in self.step_plan(self.current_epoch, validation=True):
+                graph, targets = self.val_store.batch(indices, self.current_epoch)
+                outputs = self.model(graph)
+                losses = self.criterion(outputs, targets)
+                metrics.update(graph, losses, self.criterion)
+        return metrics.result()
+
+    def train(self) -> Dict[str, List[float]]:
+        """Run the full training loop (trainer.py:662-728; after ``resume`` it continues at the epoch after the checkpoint's).
+        Returns the history: ``train_loss``, ``val_loss``, ``train_acc``, ``val_acc``."""
+        history = self.history
+        epochs = int(self.settings.epochs)
+        for epoch in range(self._next_epoch, epochs):
+            self.current_epoch = epoch
+            train_metrics = self._train_epoch()
+            history["train_loss"].append(train_metrics["loss"])
+            history["train_acc"].append(train_metrics["accuracy"])
+            if self.val_store is not None:
+                val_metrics = self._validate_epoch()
+                history["val_loss"].append(val_metrics["loss"])
+                history["val_acc"].append(val_metrics["accuracy"])
+                if self.scheduler is not None:
+                    if isinstance(self.scheduler, ReduceLROnPlateau):
+                        self.scheduler.step(val_metrics["loss"])
+                    else:
+                        self.scheduler.step()
+                improved, stop = self.stop_rule.update(val_metrics["loss"])
+                if improved:
+                    self._save_checkpoint("best_model.pt")
+                elif stop:
+                    logger.info(f"Early stopping at epoch {epoch}")
+                    break
+                logger.info(f"Epoch {epoch+1}/{epochs} - Train Loss: {train_metrics['loss']:.4f}, "
+                            f"Val Loss: {val_metrics['loss']:.4f}, Val Acc: {val_metrics['accuracy']:.4f}")
+            else:
+                logger.info(f"Epoch {epoch+1}/{epochs} - Train Loss: {train_metrics['loss']:.4f}, "
+                            f"Train Acc: {train_metrics['accuracy']:.4f}")
+            if (epoch + 1) % 10 == 0:
+                self._save_checkpoint(f"checkpoint_epoch_{epoch+1}.pt")
+        self._next_epoch = self.current_epoch + 1
+        self._save_checkpoint("final_model.pt")
+        return history
+
+    # ---- checkpoints -------------------------------------------------------------------------------------------------------
+    def _config_dict(self):
+        cfg = self.config
+        if dataclasses.is_dataclass(cfg) and not isinstance(cfg, type):
+            return dataclasses.asdict(cfg)
+        return dict(cfg) if isinstance(cfg, dict) else {"training": dict(vars(self.settings))}
+
+    def _save_checkpoint(self, filename: str):
+        """The reference's checkpoint (trainer.py:811-825) from plain containers and tensors only, so that
+        ``torch.load(weights_only=True)`` and ``BathymetricPipeline.load_model`` read it: ``config`` is a nested dict,
+        ``model_config`` holds the model's own shape, ``edge_dim`` is the model's; ``patience_counter``, ``history`` and ``seed``
+        let ``resume`` continue the run."""
+        m = self.model
+        checkpoint = {
+            "epoch": int(self.current_epoch),
+            "model_state_dict": {k: v.detach().clone() for k, v in m.state_dict().items()},
+            "optimizer_state_dict": self.optimizer.state_dict(),
+            "best_val_loss": float(self.best_val_loss),
+            "config": self._config_dict(),
+            "in_channels": int(m.feature_extractor.mlp[0].in_features),
+            "edge_dim": m.edge_dim,
+            "correction_norm_floor": CORRECTION_NORM_FLOOR,
+            "correction_norm_cap": CORRECTION_NORM_CAP,
+            "model_config": {"gnn_type": m.gnn_type, "gnn_hidden_channels": int(m.hidden_channels),
+                             "gnn_num_layers": int(m.num_gnn_layers), "gnn_heads": int(m.heads),
+                             "gnn_dropout": float(m.gnn.dropout), "num_classes": int(m.num_classes),
+                             "predict_correction": bool(m.predict_correction)},
+            "patience_counter": int(self.patience_counter),
+            "history": {k: [float(v) for v in vs] for k, vs in self.history.items()},
+            "seed": int(self.seed),
+        }
+        if self.scheduler is not None:
+            checkpoint["scheduler_state_dict"] = self.scheduler.state_dict()
+        path = self.output_dir / filename
+        torch.save(checkpoint, path)
+        logger.info(f"Saved checkpoint: {path}")
+
+    def resume(self, path):
+        """Restore model, optimizer, scheduler, epoch, best loss, patience counter and history from a checkpoint of this
+        class; the next ``train()`` continues at the following epoch."""
+        ckpt = torch.load(Path(path), map_location="cpu", weights_only=True)
+        self.model.load_state_dict(ckpt["model_state_dict"])
+        self.model.to(self.device)
+        self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+        if self.scheduler is not None and "scheduler_state_dict" in ckpt:
+            self.scheduler.load_state_dict(ckpt["scheduler_state_dict"])
+        self.current_epoch = int(ckpt["epoch"])
+        self._next_epoch = self.current_epoch + 1
+        self.best_val_loss = float(ckpt["best_val_loss"])
+        self.patience_counter = int(ckpt.get("patience_counter", 0))
+        hist = ckpt.get("history") or {}
+        self.history = {k: [float(v) for v in hist.get(k, [])] for k in ("train_loss", "val_loss", "train_acc", "val_acc")}
+        return ckpt

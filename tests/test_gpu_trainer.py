@@ -1,0 +1,463 @@
+"""The Trainer on the GPU (training/trainer.py over include/bgnn_trainer.h): the fused per-node targets against
+``data.training_targets`` bit for bit, the epoch accumulator against a replay in Python floats, ``Trainer.train()`` against a loop
+written here from its own plan, resume, the checkpoint through ``BathymetricPipeline.load_model``, early stopping, the training
+statistics, a short run that learns, and the refusals that stay."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from test_gpu_backward_training import _masked, _tile
+
+pytestmark = pytest.mark.gpu
+RES = (0.5, 0.5)
+KEYS = ("epoch", "model_state_dict", "optimizer_state_dict", "best_val_loss", "config", "in_channels", "edge_dim",
+        "correction_norm_floor", "correction_norm_cap")
+
+
+def _consts():
+    from bathymetric_gnn_amd.config.constants import CORRECTION_NORM_CAP, CORRECTION_NORM_FLOOR
+    return CORRECTION_NORM_FLOOR, CORRECTION_NORM_CAP
+
+
+# ---- 1 / 2. the targets kernel -----------------------------------------------------------------------------------------------
+
+def _target_tiles():
+    """37 x 45 V1 (holes), 24 x 48 V1, 16 x 16 without a valid cell.  In the first two a 7 x 7 patch of the depth the graph is built
+    from is made constant and valid (local_std 0 at its centre: below the floor)."""
+    tiles = [list(_tile(37, 45, 91)), list(_tile(24, 48, 92)), list(_masked(16, 16, np.zeros((16, 16), bool)))]
+    for d, m, _ in tiles[:2]:
+        d[4:11, 6:13] = np.float32(-21.5)
+        m[4:11, 6:13] = True
+    return tiles
+
+
+def _flat(arrs, dtype):
+    return torch.from_numpy(np.concatenate([np.ascontiguousarray(a, dtype).ravel() for a in arrs])).cuda()
+
+
+def _cell_index(g):
+    """The cell of every node, as ``data.training_targets`` computes it from the exported rows / columns / batch."""
+    hw = np.asarray(g._hw, np.int64)
+    off = torch.as_tensor(np.concatenate([[0], np.cumsum(hw[:, 0] * hw[:, 1])[:-1]]), device=g.device)
+    width = torch.as_tensor(hw[:, 1].copy(), device=g.device)
+    b = g.batch
+    return off[b] + g.valid_rows * width[b] + g.valid_cols
+
+
+def _mode0_planes(tiles, nan_in_clean):
+    """noisy = the tiles' depth; clean = noisy - raw with raw ~ N(0, 0.3), and +-1 m on the flat patches (quotients of +-100 at the
+    0.01 floor: beyond the cap both ways); labels 2 / mask 1 where |raw| > 0.3."""
+    rng = np.random.default_rng(7)
+    noisy, clean, labels, nmask = [], [], [], []
+    for k, (d, m, _) in enumerate(tiles):
+        raw = rng.normal(0.0, 0.3, d.shape).astype(np.float32)
+        if k < 2:
+            raw[6:9, 8:11] = np.float32(1.0)
+            raw[6:9, 9] = np.float32(-1.0)
+        c = (d - raw).astype(np.float32)
+        if nan_in_clean and k == 0:
+            r, cc = np.argwhere(m)[5]
+            c[r, cc] = np.nan
+        noisy.append(d); clean.append(c)
+        labels.append(np.where(np.abs(raw) > 0.3, 2, 0)); nmask.append(np.abs(raw) > 0.3)
+    return _flat(noisy, np.float32), _flat(clean, np.float32), _flat(labels, np.int64), _flat(nmask, np.uint8)
+
+
+@pytest.mark.parametrize("nan_in_clean", [False, True], ids=["finite", "nan in clean"])
+@pytest.mark.parametrize("conn", ["8-connected", "16-dilated"])
+def test_targets_mode0_equal_training_targets(conn, nan_in_clean, gpu_device):
+    from bathymetric_gnn_amd import data
+    from bathymetric_gnn_amd.training.trainer import training_targets_fused
+    floor, cap = _consts()
+    tiles = _target_tiles()
+    gb = data.GraphBuilder(connectivity=conn)
+    hw, res, d, m, u = gb.upload_tiles([t[0] for t in tiles], [t[1] for t in tiles], None, [RES] * 3)
+    g = gb.build_from_device(hw, res, d, m, u)
+    noisy, clean, labels, nmask = _mode0_planes(tiles, nan_in_clean)
+    assert torch.equal(noisy, d)
+    cells = int((hw[:, 0].astype(np.int64) * hw[:, 1]).sum())
+    assert 0 < g.num_nodes < cells - 256                              # holes and an empty tile: row capacity above the node count
+    got = training_targets_fused(g, 0, noisy, clean, labels, nmask.view(torch.bool))
+    y, target, mask = data.training_targets(g, clean, noisy, labels, nmask.view(torch.bool))
+    # the set-up reaches the floor and both caps
+    idx = _cell_index(g)
+    q = (noisy[idx] - clean[idx]) / torch.clamp(g.local_std, min=floor)
+    assert bool((g.local_std < floor).any()) and bool((q > cap).any()) and bool((q < -cap).any())
+    assert bool((target == cap).any()) and bool((target == -cap).any())
+    assert got["class_labels"].dtype == torch.int64 and got["noise_mask"].dtype == torch.bool
+    assert torch.equal(got["class_labels"], y)
+    assert torch.equal(got["noise_mask"], mask)
+    if nan_in_clean:
+        # (torch.equal is False on NaN: the NaN rows must be the same rows, every other row the same bits)
+        assert int(torch.isnan(target).sum()) == 1
+        assert torch.equal(torch.isnan(got["correction_targets"]), torch.isnan(target))
+        keep = ~torch.isnan(target)
+        assert torch.equal(got["correction_targets"][keep].view(torch.int32), target[keep].view(torch.int32))
+    else:
+        assert torch.equal(got["correction_targets"], target)
+        assert torch.equal(got["correction_targets"].view(torch.int32), target.view(torch.int32))
+
+
+@pytest.mark.parametrize("conn", ["8-connected", "16-dilated"])
+def test_targets_mode1_ground_truth(conn, gpu_device):
+    """int32 labels with -1 / 0 / 1 / 2 (valid = label >= 0) and a difference plane, against the torch indexing of the
+    reference's GroundTruthDataset.__getitem__."""
+    from bathymetric_gnn_amd import data
+    from bathymetric_gnn_amd.training.trainer import training_targets_fused
+    floor, cap = _consts()
+    tiles = _target_tiles()
+    rng = np.random.default_rng(11)
+    labels, diff = [], []
+    for k, (d, m, _) in enumerate(tiles):
+        lab = rng.choice(np.array([0, 1, 2], np.int32), size=d.shape, p=(0.7, 0.1, 0.2)).astype(np.int32)
+        lab[~m] = -1
+        raw = rng.normal(0.0, 0.3, d.shape).astype(np.float32)
+        if k < 2:
+            raw[6:9, 8:11] = np.float32(1.0)
+            raw[6:9, 9] = np.float32(-1.0)
+        labels.append(lab); diff.append(raw)
+    assert (labels[2] == -1).all() and all((labels[0] == v).any() for v in (-1, 0, 1, 2))
+    gb = data.GraphBuilder(connectivity=conn)
+    hw, res, d, m, u = gb.upload_tiles([t[0] for t in tiles], [lab >= 0 for lab in labels], None, [RES] * 3)
+    g = gb.build_from_device(hw, res, d, m, u)
+    lab_t, diff_t = _flat(labels, np.int32), _flat(diff, np.float32)
+    got = training_targets_fused(g, 1, diff_t, None, lab_t, None)
+    idx = _cell_index(g)
+    node_labels = lab_t[idx]
+    want_y = node_labels.long()
+    want_t = torch.clamp(diff_t[idx].float() / torch.clamp(g.local_std, min=floor), min=-cap, max=cap)
+    assert bool((g.local_std < floor).any()) and bool((want_t == cap).any()) and bool((want_t == -cap).any())
+    assert int(want_y.min()) == 0 and int(want_y.max()) == 2
+    assert torch.equal(got["class_labels"], want_y)
+    assert torch.equal(got["correction_targets"].view(torch.int32), want_t.view(torch.int32))
+    assert torch.equal(got["noise_mask"], node_labels == 2)
+
+
+def test_targets_refuse_bad_arguments(gpu_device):
+    from bathymetric_gnn_amd import data
+    from bathymetric_gnn_amd.training.trainer import training_targets_fused
+    d, m, _ = _tile(12, 12, 3, "V0")
+    g = data.GraphBuilder().build_graphs([d], [m], None, [RES])
+    a = torch.zeros(144, device="cuda")
+    lab = torch.zeros(144, dtype=torch.int64, device="cuda")
+    nm = torch.zeros(144, dtype=torch.uint8, device="cuda")
+    with pytest.raises(ValueError):
+        training_targets_fused(g, 0, a, None, lab, nm)                # mode 0 without the clean plane
+    with pytest.raises(ValueError):
+        training_targets_fused(g, 0, a[:100], a, lab, nm)             # a plane that is not the batch's size
+    with pytest.raises(TypeError):
+        training_targets_fused(g, 1, a, None, lab, None)              # mode 1 takes int32 labels
+    with pytest.raises(ValueError, match="mode"):
+        training_targets_fused(g, 2, a, a, lab.int(), nm)                  # refused by the library
+
+
+# ---- 3. the accumulator ---------------------------------------------------------------------------------------------------
+
+def _model(kind="GAT", seed=1, **kw):
+    from bathymetric_gnn_amd import synthetic
+    from bathymetric_gnn_amd.models import BathymetricGNN
+    sd = synthetic.synthetic_state_dict(in_channels=7, num_layers=2, seed=seed, gnn_type=kind, **kw)
+    m = BathymetricGNN(in_channels=7, hidden_channels=64, num_gnn_layers=2, gnn_type=kind, heads=4, dropout=0.1, edge_dim=3, **kw)
+    m.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
+    return m.cuda()
+
+
+@pytest.mark.parametrize("num_classes,correction", [(3, True), (2, False)], ids=["C3 correction", "C2 no correction"])
+def test_epoch_accumulator_equals_python_replay(num_classes, correction, gpu_device):
+    from bathymetric_gnn_amd.training import BathymetricGNNLoss, EpochMetrics, TileStore
+    C = num_classes
+    tiles = [_tile(20, 24, 31), _tile(33, 17, 32), _masked(16, 16, np.zeros((16, 16), bool)), _tile(16, 40, 33), _tile(28, 28, 34)]
+    store = TileStore.from_tiles([t[0] for t in tiles], [t[1] for t in tiles], None, [RES] * len(tiles), seed=3)
+    m = _model(num_classes=C, predict_correction=correction).eval()
+    crit = BathymetricGNNLoss()
+    metrics = EpochMetrics()
+    metrics.reset()
+    sums, nodes, correct, steps, conf, seen_n = [0.0] * 6, 0, 0, 0, np.zeros((C, C), np.int64), []
+    last = None
+    for i in range(len(tiles)):
+        g, t = store.batch([i], epoch=0)
+        y = t["class_labels"]
+        if C == 2:                                            # labels 0 / 2 -> 0 / 1, every 7th row ignored (never equals a prediction)
+            y = (y == 2).long()
+            y[::7] = -100
+            t = {"class_labels": y, "correction_targets": t["correction_targets"], "noise_mask": t["noise_mask"]}
+        with torch.no_grad():
+            out = m(g)
+            losses = crit(out, t)
+        n = g.num_nodes
+        seen_n.append(n)
+        if n == 0:
+            assert crit.last_stats is None
+            metrics.update(g, losses, crit)                   # the loss's torch path: the kernel sees n = 0
+            metrics.accumulate(g, last[0], last[1], C)        # ... and with live terms and counts behind an empty graph
+            continue
+        metrics.update(g, losses, crit)
+        last = (torch.stack([losses[k].detach() for k in ("classification", "correction", "confidence", "feature_preservation",
+                                                          "shoal_safety", "total")]).contiguous(),
+                torch.cat([crit.last_stats["confusion"].reshape(-1)] +
+                          [crit.last_stats[k].reshape(1) for k in ("n_masked", "false_positives", "shoal_false_positives",
+                                                                   "deep_false_positives", "n_ignored", "n_invalid",
+                                                                   "feature_as_noise")]).contiguous())
+        for k, name in enumerate(("classification", "correction", "confidence", "feature_preservation", "shoal_safety", "total")):
+            sums[k] += float(losses[name]) * n
+        pred = out["predicted_class"]
+        correct += int((pred == y).sum())
+        nodes += n
+        steps += 1
+        ok = (y >= 0) & (y < C)
+        conf += np.bincount((y[ok] * C + pred[ok]).cpu().numpy(), minlength=C * C).reshape(C, C)
+    assert len(set(seen_n)) == len(seen_n) and 0 in seen_n
+    r = metrics.result()
+    print(f"C={C}: nodes {nodes}, steps {steps}, loss {r['loss']!r}, accuracy {r['accuracy']!r}")
+    assert all(np.isfinite(s) for s in sums)
+    assert (r["nodes"], r["steps"]) == (nodes, steps) and steps == 4
+    assert r["loss"] == sums[5] / nodes
+    for k, name in enumerate(("classification", "correction", "confidence", "feature_preservation", "shoal_safety")):
+        assert r[name] == sums[k] / nodes, name
+    assert r["accuracy"] == correct / nodes
+    assert np.array_equal(r["confusion"], conf) and int(np.trace(conf)) == correct
+    if C == 2:
+        assert conf.sum() < nodes                             # the ignored rows are in no cell of the matrix
+        assert r["correction"] == 0
+    else:
+        assert conf.sum() == nodes
+    metrics.reset()
+    z = metrics.result()
+    assert (z["loss"], z["accuracy"], z["nodes"], z["steps"]) == (0, 0, 0, 0) and not z["confusion"].any()
+
+
+# ---- 4 - 9. the Trainer ---------------------------------------------------------------------------------------------------
+
+def _stores(seed=0):
+    from bathymetric_gnn_amd.training import TileStore
+    tr = [_tile(32, 40, 40 + i) for i in range(6)]
+    va = [_tile(32, 40, 50 + i) for i in range(2)]
+    return (TileStore.from_tiles([t[0] for t in tr], [t[1] for t in tr], None, [RES] * 6, seed=seed),
+            TileStore.from_tiles([t[0] for t in va], [t[1] for t in va], None, [RES] * 2, seed=seed + 1))
+
+
+def _config(**training):
+    from bathymetric_gnn_amd.config import Config
+    cfg = Config()
+    cfg.training = dict({"batch_size": 2, "epochs": 2, "scheduler": "cosine"}, **training)
+    return cfg
+
+
+def _replay(trainer, epochs):
+    """The epochs of ``Trainer.train()`` written out: the plan, the store, the model, the criterion and the optimizer, with the
+    reference's host bookkeeping in Python floats."""
+    from bathymetric_gnn_amd.training import FusedAdamW
+    model, crit, opt = trainer.model, trainer.criterion, trainer.optimizer
+    assert isinstance(opt, FusedAdamW)
+    hist = {"train_loss": [], "val_loss": [], "train_acc": [], "val_acc": []}
+
+    def run(store, plan, epoch, train):
+        total, correct, nodes = 0.0, 0, 0
+        for idx, seed in plan:
+            g, t = store.batch(idx, epoch)
+            if train:
+                model.dropout_seed = seed
+                opt.zero_grad()
+            out = model(g)
+            losses = crit(out, t)
+            if train:
+                losses["total"].backward()
+                opt.step()
+            total += losses["total"].item() * g.num_nodes
+            correct += (out["predicted_class"] == t["class_labels"]).sum().item()
+            nodes += g.num_nodes
+        return total / nodes, correct / nodes
+
+    for epoch in range(epochs):
+        model.train()
+        loss, acc = run(trainer.train_store, trainer.step_plan(epoch), epoch, True)
+        hist["train_loss"].append(loss); hist["train_acc"].append(acc)
+        model.eval()
+        with torch.no_grad():
+            loss, acc = run(trainer.val_store, trainer.step_plan(epoch, validation=True), epoch, False)
+        hist["val_loss"].append(loss); hist["val_acc"].append(acc)
+        trainer.scheduler.step()
+    return hist
+
+
+@pytest.fixture(scope="module")
+def trained_gat(tmp_path_factory, gpu_device):
+    """Test 4's GAT run, shared with the checkpoint test: (trainer, history, output directory)."""
+    from bathymetric_gnn_amd.training import Trainer
+    out = tmp_path_factory.mktemp("trainer_gat")
+    train, val = _stores()
+    t = Trainer(_config(), _model("GAT"), train, val, output_dir=out, seed=4)
+    return t, copy.deepcopy(t.train()), out
+
+
+def _same_run(kind, trainer, history):
+    from bathymetric_gnn_amd.training import Trainer
+    train, val = _stores()
+    other = Trainer(_config(), _model(kind), train, val, output_dir=trainer.output_dir / "replay", seed=4)
+    hist = _replay(other, 2)
+    print(f"{kind}: history {history}")
+    assert history == hist
+    assert all(len(v) == 2 and all(np.isfinite(v)) for v in history.values())
+    a, b = trainer.model.state_dict(), other.model.state_dict()
+    assert list(a) == list(b)
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+    assert trainer.optimizer.param_groups[0]["lr"] == other.optimizer.param_groups[0]["lr"] != 1e-3     # the scheduler stepped
+
+
+def test_trainer_equals_its_plan_gat(gpu_device, trained_gat):
+    trainer, history, _ = trained_gat
+    _same_run("GAT", trainer, history)
+
+
+def test_trainer_equals_its_plan_graphsage(tmp_path, gpu_device):
+    from bathymetric_gnn_amd.training import Trainer
+    train, val = _stores()
+    t = Trainer(_config(), _model("GraphSAGE"), train, val, output_dir=tmp_path, seed=4)
+    _same_run("GraphSAGE", t, copy.deepcopy(t.train()))
+
+
+def test_resume_continues_bit_for_bit(tmp_path, gpu_device):
+    from bathymetric_gnn_amd.training import Trainer
+    straight = Trainer(_config(epochs=4, scheduler="plateau"), _model("GAT"), *_stores(), output_dir=tmp_path / "a", seed=6)
+    h4 = copy.deepcopy(straight.train())
+    first = Trainer(_config(epochs=2, scheduler="plateau"), _model("GAT"), *_stores(), output_dir=tmp_path / "b", seed=6)
+    h2 = copy.deepcopy(first.train())
+    assert h2 == {k: v[:2] for k, v in h4.items()}
+    second = Trainer(_config(epochs=4, scheduler="plateau"), _model("GAT", seed=99), *_stores(), output_dir=tmp_path / "c", seed=6)
+    second.resume(tmp_path / "b" / "final_model.pt")
+    assert second.current_epoch == 1 and second.history == h2
+    assert second.best_val_loss == first.best_val_loss and second.patience_counter == first.patience_counter
+    assert second.scheduler.state_dict() == first.scheduler.state_dict()
+    h = second.train()
+    assert h == h4 and len(h["train_loss"]) == 4
+    a, b = straight.model.state_dict(), second.model.state_dict()
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+    sa, sb = straight.optimizer.state_dict(), second.optimizer.state_dict()
+    assert sa["param_groups"] == sb["param_groups"]
+    for i in sa["state"]:
+        for k in ("step", "exp_avg", "exp_avg_sq"):
+            assert torch.equal(sa["state"][i][k], sb["state"][i][k]), (i, k)
+
+
+def test_checkpoint_loads_into_the_pipeline(gpu_device, trained_gat):
+    from bathymetric_gnn_amd.config import Config
+    from bathymetric_gnn_amd.data import GraphBuilder
+    from bathymetric_gnn_amd.models.pipeline import BathymetricPipeline
+    trainer, history, out = trained_gat
+    assert (out / "best_model.pt").exists() and (out / "final_model.pt").exists()
+    for name in ("best_model.pt", "final_model.pt"):
+        ck = torch.load(out / name, map_location="cpu", weights_only=True)
+        assert set(KEYS) <= set(ck) and "scheduler_state_dict" in ck and isinstance(ck["config"], dict)
+        assert ck["config"]["training"]["batch_size"] == 2 and ck["in_channels"] == 7 and ck["edge_dim"] == 3
+        assert ck["model_config"]["gnn_num_layers"] == 2 and ck["seed"] == 4 and set(ck["history"]) == set(history)
+    ck = torch.load(out / "final_model.pt", map_location="cpu", weights_only=True)
+    assert ck["epoch"] == 1 and ck["history"] == history and ck["best_val_loss"] == trainer.best_val_loss
+    pipe = BathymetricPipeline(Config())
+    pipe.load_model(out / "final_model.pt")
+    d, m, _ = _tile(32, 40, 77)
+    g = GraphBuilder().build_graphs([d], [m], None, [RES])
+    with torch.no_grad():
+        want = trainer.model.eval()(g)["class_logits"]
+        got = pipe.model.eval()(g)["class_logits"]
+    assert torch.equal(got, want) and bool(torch.isfinite(got).all())
+
+
+def test_early_stopping_and_best_model(tmp_path, gpu_device):
+    from bathymetric_gnn_amd.training import Trainer
+    t = Trainer(_config(epochs=5, patience=1, min_delta=1e9), _model("GAT"), *_stores(), output_dir=tmp_path / "stop", seed=2)
+    h = t.train()
+    assert [len(h[k]) for k in ("train_loss", "val_loss", "train_acc", "val_acc")] == [2, 2, 2, 2]
+    assert t.current_epoch == 1 and t.patience_counter == 1 and t.best_val_loss == h["val_loss"][0]
+    best = torch.load(tmp_path / "stop" / "best_model.pt", map_location="cpu", weights_only=True)
+    assert best["epoch"] == 0 and best["history"]["val_loss"] == h["val_loss"][:1]
+    assert torch.load(tmp_path / "stop" / "final_model.pt", map_location="cpu", weights_only=True)["epoch"] == 1
+    # no validation store: the scheduler never steps (the reference's quirk) and no best model is written
+    train, _ = _stores()
+    t = Trainer(_config(epochs=2), _model("GAT"), train, None, output_dir=tmp_path / "noval", seed=2)
+    h = t.train()
+    assert len(h["train_loss"]) == 2 and h["val_loss"] == [] and h["val_acc"] == []
+    assert t.optimizer.param_groups[0]["lr"] == 1e-3
+    assert not (tmp_path / "noval" / "best_model.pt").exists() and (tmp_path / "noval" / "final_model.pt").exists()
+
+
+def test_training_statistics(tmp_path, gpu_device):
+    from bathymetric_gnn_amd.data import SyntheticNoiseGenerator
+    from bathymetric_gnn_amd.training import TileStore, Trainer, compute_class_weights, compute_correction_delta
+    _, cap = _consts()
+    train, _ = _stores()
+    t = Trainer(_config(), _model("GAT"), train, None, output_dir=tmp_path, seed=0)
+    weights, delta = t._compute_training_stats()
+    ys, sel = [], []
+    for i in range(len(train)):
+        _, tg = train.batch([i], epoch=0)
+        ys.append(tg["class_labels"].cpu().numpy())
+        v = tg["correction_targets"][tg["noise_mask"]].cpu().numpy()
+        sel.append(v[np.isfinite(v)])
+    counts = torch.from_numpy(np.bincount(np.concatenate(ys), minlength=3)[:3])
+    want_w = compute_class_weights(torch.arange(3).repeat_interleave(counts.clamp(min=1)), num_classes=3, smoothing=0.1)
+    want_d = compute_correction_delta(np.clip(np.concatenate(sel), -cap, cap), percentile=95.0, min_delta=1.0)
+    print(f"counts {counts.tolist()}, weights {weights.tolist()}, delta {delta!r}")
+    assert counts[0] > 0 and counts[2] > 0 and np.concatenate(sel).size > 0
+    assert torch.equal(weights.cpu(), want_w) and delta == want_d
+    assert torch.equal(t.criterion.classification_loss.class_weights.cpu(), want_w) and t.criterion.correction_loss.delta == want_d
+    # a store whose samples carry no noise: no selected correction, delta 1.0
+    tiles = [_tile(32, 40, 40 + i) for i in range(2)]
+    quiet = TileStore.from_tiles([x[0] for x in tiles], [x[1] for x in tiles], None, [RES] * 2, augment=False, seed=0,
+                                 noise_generator=SyntheticNoiseGenerator(enable_gaussian=False, enable_spikes=False,
+                                                                         enable_blobs=False, enable_systematic=False, seed=0))
+    _, tg = quiet.batch([0, 1], epoch=0)
+    assert not bool(tg["noise_mask"].any()) and not bool(tg["class_labels"].any())
+    t = Trainer(_config(), _model("GAT"), quiet, None, output_dir=tmp_path, seed=0)
+    weights, delta = t._compute_training_stats()
+    assert delta == 1.0 and weights is not None and float(weights[0]) < float(weights[1]) == float(weights[2])
+
+
+def test_it_learns(tmp_path, gpu_device):
+    """Three epochs at lr 1e-3 on the six training tiles: the dropout-free training-mode loss over those tiles (epoch 0's noise)
+    is lower after than before."""
+    from test_gpu_backward import _set_dropout
+    from bathymetric_gnn_amd.training import Trainer
+    train, val = _stores()
+    t = Trainer(_config(epochs=3, learning_rate=1e-3), _model("GAT"), train, val, output_dir=tmp_path, seed=0)
+
+    def dropout_free_loss():
+        saved = copy.deepcopy(t.model.state_dict())               # (a training-mode forward moves the running statistics)
+        _set_dropout(t.model, 0.0)
+        t.model.train()
+        total, nodes = 0.0, 0
+        with torch.no_grad():
+            for idx, _ in t.step_plan(0):
+                g, tg = train.batch(idx, 0)
+                total += float(t.criterion(t.model(g), tg)["total"]) * g.num_nodes
+                nodes += g.num_nodes
+        _set_dropout(t.model, 0.1)
+        t.model.load_state_dict(saved)
+        return total / nodes
+
+    start = dropout_free_loss()
+    h = t.train()
+    end = dropout_free_loss()
+    print(f"history {h}; dropout-free loss {start:.5f} -> {end:.5f}")
+    assert all(bool(torch.isfinite(p).all()) for p in t.model.parameters())
+    assert end < start
+
+
+# ---- 10. refusals ---------------------------------------------------------------------------------------------------------
+
+def test_refusals_at_construction(tmp_path, gpu_device):
+    from bathymetric_gnn_amd.models import BathymetricGNN
+    from bathymetric_gnn_amd.training import Trainer
+    train, _ = _stores()
+    gcn = BathymetricGNN(in_channels=7, num_gnn_layers=2, gnn_type="GCN", edge_dim=3)
+    with pytest.raises((NotImplementedError, ValueError), match="GCN"):
+        Trainer(_config(), gcn, train, None, output_dir=tmp_path)
+    padded = BathymetricGNN(in_channels=7, hidden_channels=100, num_gnn_layers=2, edge_dim=3)
+    with pytest.raises((NotImplementedError, ValueError), match="hidden_channels=100"):
+        Trainer(_config(), padded, train, None, output_dir=tmp_path)
+    wide = BathymetricGNN(in_channels=7, hidden_channels=128, heads=4, num_gnn_layers=2, edge_dim=3)
+    with pytest.raises((NotImplementedError, ValueError), match="256 columns"):
+        Trainer(_config(), wide, train, None, output_dir=tmp_path)

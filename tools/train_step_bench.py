@@ -8,9 +8,16 @@ forward is timed on its own ("loss") and its backward is part of "backward".  Pr
 SGD and the host repack: "step" is the optimizer step with its refresh, "step_and_forward_share" adds what the following training forward
 pays because the weights changed (its time minus that of the same forward run once more), "pack_weights_calls" counts the host repacks
 of the timed iterations (0: the step never went through the host).
+--targets torch|fused adds the per-node training targets of the batch to the step (synthetic noise generated once, outside the timed
+loop): ``data.training_targets`` (about ten torch launches over the graph's exported batch / valid_rows / valid_cols / local_std) or
+the one launch of ``bgnn_training_targets``.  "targets" is that call per step; for torch, "targets_fresh_export" is the same call with
+the graph's exported tensors dropped first, which is what a training loop pays (every step builds a new graph), and for fused
+"targets_kernel_us" / "targets_gb_per_s" are 50 back-to-back launches between two device events (launch overhead included) over the
+bytes the kernel moves.  --bookkeeping item|device (with --loss fused) adds the step's bookkeeping: the reference's two ``.item()``
+round trips, or ``EpochMetrics.update`` (``bgnn_epoch_accumulate``; no host wait, the figure ends in a device synchronise).
 
     python tools/train_step_bench.py [--gnn-type GAT|GraphSAGE|GIN] [--tiles 16] [--size 256] [--steps 10] [--warmup 3] [--loss fused|torch]
-                                     [--optimizer torch|fused]
+                                     [--optimizer torch|fused] [--targets torch|fused] [--bookkeeping item|device]
 """
 import argparse
 import json
@@ -34,7 +41,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--loss", default=None, choices=["fused", "torch"])
     ap.add_argument("--optimizer", default="torch", choices=["torch", "fused"])
+    ap.add_argument("--targets", default=None, choices=["torch", "fused"])
+    ap.add_argument("--bookkeeping", default=None, choices=["item", "device"])
     a = ap.parse_args()
+    if a.bookkeeping and a.loss != "fused":
+        ap.error("--bookkeeping needs --loss fused (the device form reads the fused loss pass's terms and counts)")
     from bathymetric_gnn_amd import synthetic
     from bathymetric_gnn_amd.data import GraphBuilder
     from bathymetric_gnn_amd.models import BathymetricGNN
@@ -78,16 +89,52 @@ def main():
         rec = {"taped_forward": [], "backward": [], "step": [], "step_and_forward_share": [], "untaped_forward": []}
     if a.loss:
         rec["loss"] = []
+    if a.targets:
+        from bathymetric_gnn_amd.data import SyntheticNoiseGenerator, training_targets
+        from bathymetric_gnn_amd.training.trainer import training_targets_fused
+        gb = GraphBuilder()
+        hw, res_, clean_t, mask_t, _ = gb.upload_tiles([t[0] for t in tiles], [t[1] for t in tiles], None, [(0.5, 0.5)] * a.tiles)
+        nb = SyntheticNoiseGenerator(seed=0).generate_batch(hw, clean_t, mask_t, sample_indices=list(range(a.tiles)))
+        g = gb.build_from_device(hw, res_, nb.noisy_depth, mask_t, None)        # the step's graph: built from the noisy depth
+        N = g.num_nodes
+        w = torch.randn(N, 3, device=dev)
+        rec["targets"] = []
+        if a.targets == "torch":
+            rec["targets_fresh_export"] = []
+            make_targets = lambda: training_targets(g, clean_t, nb.noisy_depth, nb.classification, nb.noise_mask)
+        else:
+            make_targets = lambda: training_targets_fused(g, 0, nb.noisy_depth, clean_t, nb.classification, nb.noise_mask)
+    if a.bookkeeping:
+        from bathymetric_gnn_amd.training import EpochMetrics
+        rec["bookkeeping"] = []
+        metrics = EpochMetrics(dev)
+        metrics.reset()
+        book = {"loss": 0.0, "correct": 0, "nodes": 0}
     for it in range(a.warmup + a.steps):
         m.dropout_seed = it
         opt.zero_grad(set_to_none=True)
         out, t_fwd = timed(lambda: m(g))
+        if a.targets:
+            _, t_tgt = timed(make_targets)
+            if a.targets == "torch":
+                for k in ("batch", "valid_rows", "valid_cols", "local_std"):
+                    g._cache.pop(k, None)
+                _, t_tgt_fresh = timed(make_targets)
         if a.loss:
-            loss, t_loss = timed(lambda: loss_fn(out, targets)["total"])
+            losses, t_loss = timed(lambda: loss_fn(out, targets))
+            loss = losses["total"]
         else:
             loss = (out["class_logits"] * w).sum() + out["confidence"].sum() + out["correction"].sum()
         _, t_bwd = timed(loss.backward)
         _, t_opt = timed(opt.step)
+        if a.bookkeeping == "item":
+            def host_bookkeeping():                    # training/trainer.py:764-767 of the reference
+                book["loss"] += losses["total"].item() * N
+                book["correct"] += (out["predicted_class"] == targets["class_labels"]).sum().item()
+                book["nodes"] += N
+            _, t_book = timed(host_bookkeeping)
+        elif a.bookkeeping == "device":
+            _, t_book = timed(lambda: metrics.update(g, losses, crit))
         with torch.no_grad():
             _, t_plain = timed(lambda: m(g))           # untaped training forward (repacks like every training forward)
         ctx = rt.get_context(dev)
@@ -113,10 +160,35 @@ def main():
             rec["untaped_forward"].append(t_plain)
             if a.loss:
                 rec["loss"].append(t_loss)
+            if a.targets:
+                rec["targets"].append(t_tgt)
+                if a.targets == "torch":
+                    rec["targets_fresh_export"].append(t_tgt_fresh)
+            if a.bookkeeping:
+                rec["bookkeeping"].append(t_book)
+    extra = {}
+    if a.targets == "fused":
+        reps = 50
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        ev0.record()
+        for _ in range(reps):
+            make_targets()
+        ev1.record()
+        torch.cuda.synchronize()
+        us = ev0.elapsed_time(ev1) * 1e3 / reps
+        cells = int(nb.noisy_depth.numel())
+        moved = 4 * cells + N * (4 + 4 + 8 + 1 + 4) + N * (8 + 4 + 1)      # node ids; noisy, clean, label, mask, local_std; y, target, mask
+        extra = {"targets_kernel_us": round(us, 2), "targets_bytes": moved, "targets_gb_per_s": round(moved / us / 1e3, 1)}
+    if a.bookkeeping == "device":
+        r = metrics.result()
+        extra["bookkeeping_steps"] = r["steps"]
     tape_bytes = int(ctx.lib.bgnn_tape_bytes(m.native(ctx, 3), g._handle))
     res = {"metric": "train_step_ms", "gnn_type": a.gnn_type, "nodes": N, "tiles": a.tiles, "size": a.size,
            **({"loss_path": a.loss} if a.loss else {}),
            **({"optimizer": "fused", "pack_weights_calls": len(packs)} if fused else {}),
+           **({"targets_path": a.targets} if a.targets else {}), **({"bookkeeping_path": a.bookkeeping} if a.bookkeeping else {}),
+           **extra,
            **{k: round(float(np.median(v)), 3) for k, v in rec.items()},
            "tape_bytes_per_node": round(tape_bytes / N, 1), "tape_gb": round(tape_bytes / 1e9, 3)}
     print(json.dumps(res))
