@@ -239,6 +239,27 @@ TARGETS_SYNTHETIC, TARGETS_GROUND_TRUTH = 0, 1     # BGNN_TARGETS_*
 EPOCH_MAX_CLASSES = 16                             # BGNN_EPOCH_MAX_CLASSES
 EPOCH_ACC_BYTES = 72 + 8 * EPOCH_MAX_CLASSES * EPOCH_MAX_CLASSES   # BGNN_EPOCH_ACC_BYTES: double [6] | int64 nodes, correct, steps | int64 [16 * 16]
 
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_eval.h declares (ground truth from a survey pair, model evaluation)
+_EVAL_SIGNATURES = {
+    "bgnn_ground_truth_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "bgnn_ground_truth_build": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_size_t] +
+                                [C.c_void_p] * 4),
+    "bgnn_eval_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "bgnn_eval_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bgnn_eval_accumulate": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+# BGNN_GT_STATS_*: int64 valid, noise, seafloor | float64 noise_abs_sum, seafloor_sum | float32 offset, noise_abs_max
+GT_STATS_BYTES = 48
+GT_STATS_DTYPE = [("valid", "<i8"), ("noise", "<i8"), ("seafloor", "<i8"), ("noise_abs_sum", "<f8"), ("seafloor_sum", "<f8"),
+                  ("offset", "<f4"), ("noise_abs_max", "<f4")]
+# BGNN_EVAL_ACC_*: the accumulator block of an evaluation
+EVAL_THRESHOLDS = (0.5, 0.6, 0.7, 0.8, 0.9)
+EVAL_ACC_BYTES = 264
+EVAL_ACC_DTYPE = [("total", "<i8"), ("correct", "<i8"), ("confusion", "<i8", (4, 4)), ("covered", "<i8", (5,)),
+                  ("covered_correct", "<i8", (5,)), ("conf_sum", "<f8"), ("conf_sq", "<f8"), ("conf_correct_sum", "<f8"),
+                  ("conf_incorrect_sum", "<f8"), ("conf_cells", "<i8")]
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -249,7 +270,7 @@ class BgnnError(RuntimeError):
 
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
-    include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h and include/bgnn_trainer.h.  Needs no GPU."""
+    include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h and include/bgnn_eval.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -261,7 +282,8 @@ def load_library(path: Optional[str] = None):
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = C.CDLL(p)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
-                list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()):
+                list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
+                list(_EVAL_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -154,22 +154,36 @@ class TileStore:
                           overlap: int = 64, min_valid_ratio: float = 0.1, device=None, **kw) -> "TileStore":
         """A ground-truth raster as its bands hold it: 1 labels (0 seafloor, 2 noise, -1 nodata), 2 difference (noisy - clean),
         3 noisy depth, 5 uncertainty (optional).  Cut with ``plan_ground_truth_tiles``; a cell is valid where its label is
-        >= 0."""
+        >= 0.  The planes are host arrays, or device tensors (``GroundTruth.training_planes()``): then only the label plane is
+        copied to the host, to plan the tiles, and the tiles are cut on the device; the store is the same bit for bit."""
         device = rt.resolve_device(device)
-        labels = np.asarray(labels).astype(np.int32)
+        on_device = isinstance(labels, torch.Tensor)
+        if on_device:
+            if any(p is not None and not isinstance(p, torch.Tensor) for p in (difference, noisy_depth, uncertainty)):
+                raise TypeError("labels is a tensor: the other planes must be tensors too")
+            labels_dev = labels.to(device=device, dtype=torch.int32)
+            labels = labels_dev.cpu().numpy()
+        else:
+            labels = np.asarray(labels).astype(np.int32)
         boxes, counts = plan_ground_truth_tiles(labels, tile_size, overlap, min_valid_ratio)
         if not boxes:
             raise ValueError("the ground-truth raster yields no tile")
-        planes = {"labels": (labels, np.int32), "difference": (difference, np.float32), "depth": (noisy_depth, np.float32)}
+        planes = {"labels": (labels_dev if on_device else labels, np.int32), "difference": (difference, np.float32),
+                  "depth": (noisy_depth, np.float32)}
         if uncertainty is not None:
             planes["unc"] = (uncertainty, np.float32)
         flat = {}
         for k, (arr, dt) in planes.items():
-            arr = np.asarray(arr)
-            if arr.shape != labels.shape:
-                raise ValueError(f"{k} has shape {arr.shape}, labels {labels.shape}")
-            flat[k] = torch.from_numpy(np.concatenate([np.ascontiguousarray(arr[r0:r1, c0:c1], dt).ravel()
-                                                       for r0, c0, r1, c1 in boxes])).to(device)
+            if not on_device:
+                arr = np.asarray(arr)
+            if tuple(arr.shape) != tuple(labels.shape):
+                raise ValueError(f"{k} has shape {tuple(arr.shape)}, labels {labels.shape}")
+            if on_device:
+                arr = arr.to(device=device, dtype=torch.int32 if dt is np.int32 else torch.float32)
+                flat[k] = torch.cat([arr[r0:r1, c0:c1].reshape(-1) for r0, c0, r1, c1 in boxes])
+            else:
+                flat[k] = torch.from_numpy(np.concatenate([np.ascontiguousarray(arr[r0:r1, c0:c1], dt).ravel()
+                                                           for r0, c0, r1, c1 in boxes])).to(device)
         hw = np.array([(r1 - r0, c1 - c0) for r0, c0, r1, c1 in boxes], np.int32)
         res = np.array([(float(resolution[0]), float(resolution[1]))] * len(boxes), np.float64)
         store = cls("ground_truth", hw, res, flat["depth"], (flat["labels"] >= 0).view(torch.uint8), flat.get("unc"),
