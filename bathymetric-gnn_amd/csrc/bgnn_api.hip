@@ -1,5 +1,6 @@
-// C ABI of libbgnn_hip.so (declared in include/bgnn.h): contexts, graph handles and the forward / fused-inference orchestration
-// (models: model_pack.hip; training forward and backward: train_api.hip).  Host code only; kernels live in the other TUs.
+// C ABI of libbgnn_hip.so (declared in include/bgnn.h): contexts, the pool and the forward / fused-inference orchestration
+// (graph handles: graph_api.hip; models: model_pack.hip; training forward and backward: train_api.hip).  Host code only; kernels
+// live in the other TUs.
 #include <stdarg.h>
 #include <string.h>
 #include <stdlib.h>
@@ -311,8 +312,6 @@ int bgnn_debug_stamps(bgnn_ctx *ctx, unsigned long long *out32) {
   return BGNN_OK;
 }
 
-static void graph_free(bgnn_graph *g);
-
 int bgnn_ctx_destroy(bgnn_ctx *ctx) {
   if (!ctx) return BGNN_OK;
   (void)hipSetDevice(ctx->device);
@@ -359,348 +358,6 @@ int bgnn_ctx_profile_read(bgnn_ctx *ctx, double *ms, int64_t *launches) {
   }
   ctx->prof_records.clear();
   return BGNN_OK;
-}
-
-// ---- graph ------------------------------------------------------------------------------------
-static void graph_free(bgnn_graph *g) {
-  DevPool &P = g->ctx->pool;
-  g->ctx->live_graphs.erase(g);
-  if (g->d_tables) P.release(g->d_tables);       // ragged batch: tiles / items / items2 / items3 / canvas tables live in this block
-  else if (!g->tables_cached) { P.release(g->d_tiles); P.release(g->d_items); }
-  else
-    for (auto &e : g->ctx->table_cache)          // drop this graph's reference on its cache entry (evictable at 0)
-      if (e.id == g->table_cache_id) { if (e.refs > 0) --e.refs; break; }
-  P.release(g->d_node_id); P.release(g->d_cell_of_node);
-  P.release(g->d_counts); P.release(g->d_x8); P.release(g->d_local_std); P.release(g->d_nbr);
-  P.release(g->d_eattr); P.release(g->d_rowptr); P.release(g->d_edge_perm);
-  P.release(g->d_slope); P.release(g->d_node_depth); P.release(g->d_tile_dist); P.release(g->d_atlas_tile_of);
-  P.release(g->d_atlas);
-  P.release(g->d_tr_ptr); P.release(g->d_tr_slot); P.release(g->d_tr_dst);
-  delete g;
-}
-
-static int validate_opts(const bgnn_graph_opts *o) {
-  BGNN_REQUIRE(o->connectivity == 4 || o->connectivity == 8 || o->connectivity == 16,
-               "Unknown connectivity: %d", o->connectivity);
-  BGNN_REQUIRE(o->n_node_features >= 0 && o->n_node_features <= 8, "n_node_features=%d out of range", o->n_node_features);
-  BGNN_REQUIRE(o->n_edge_features >= 1 && o->n_edge_features <= 4, "n_edge_features=%d out of range (1..4)", o->n_edge_features);
-  for (int i = 0; i < o->n_node_features; ++i)
-    BGNN_REQUIRE(o->node_features[i] >= 0 && o->node_features[i] <= 7, "bad node feature id %d", o->node_features[i]);
-  for (int i = 0; i < o->n_edge_features; ++i)
-    BGNN_REQUIRE(o->edge_features[i] >= 0 && o->edge_features[i] <= 3, "bad edge feature id %d", o->edge_features[i]);
-  return BGNN_OK;
-}
-
-static int graph_build_impl(bgnn_ctx *ctx, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, bgnn_graph **out, int64_t *n_nodes_copy,
-                            float *const *clear_grids = nullptr);
-
-int bgnn_graph_build(bgnn_ctx *ctx, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, bgnn_graph **out) {
-  return graph_build_impl(ctx, tiles, opts, out, nullptr);
-}
-
-static int graph_build_impl(bgnn_ctx *ctx, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, bgnn_graph **out, int64_t *n_nodes_copy,
-                            float *const *clear_grids) {
-  BGNN_REQUIRE(ctx && tiles && opts && out, "bgnn_graph_build: NULL argument");
-  BGNN_REQUIRE(tiles->n_tiles >= 1, "bgnn_graph_build: n_tiles=%d", tiles->n_tiles);
-  // (the per-grid kernels index grids by gridDim.y: 65 535 at most -- say so instead of failing the launch)
-  BGNN_REQUIRE(tiles->n_tiles <= 60000, "bgnn_graph_build: %d grids in one batch, at most 60000 (split the batch)", tiles->n_tiles);
-  BGNN_REQUIRE(tiles->hw && tiles->resolution && tiles->depth && tiles->mask, "bgnn_graph_build: NULL tile array");
-  BGNN_TRY(validate_opts(opts));
-  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
-  bgnn_graph *g = new bgnn_graph();
-  g->ctx = ctx; g->kind = 0; g->n_tiles = tiles->n_tiles; g->d_n_nodes_copy = n_nodes_copy;
-  if (clear_grids) for (int i = 0; i < 3; ++i) g->clear_grids[i] = clear_grids[i];
-  g->K = opts->connectivity; g->ED = opts->n_edge_features; g->include_self_loops = opts->include_self_loops ? 1 : 0;
-  g->has_unc = tiles->uncertainty ? 1 : 0;
-  // feature count (see launch_graph_build for the column rule)
-  {
-    int nf = 0; bool listed = false;
-    for (int i = 0; i < opts->n_node_features; ++i) {
-      if (opts->node_features[i] == BGNN_NF_UNCERTAINTY) { listed = true; if (!tiles->uncertainty) continue; }
-      ++nf;
-    }
-    if (tiles->uncertainty && !listed) ++nf;
-    if (nf > 8 || nf < 1) { delete g; set_error("node feature count %d out of range (1..8)", nf); return BGNN_ERR_INVALID; }
-    g->F = nf;
-  }
-  int64_t cells = 0;
-  int64_t cells_est = 0;
-  for (int t = 0; t < tiles->n_tiles; ++t) cells_est += (int64_t)tiles->hw[2 * t] * tiles->hw[2 * t + 1];
-  const int item_cells = (int)std::min<int64_t>(2048, std::max<int64_t>(256, cells_est / (4 * ctx->num_cus)));
-  std::vector<BgnnWorkItem> items, items2, items3;
-  bool uniform = true;
-  g->h_tiles.resize(tiles->n_tiles);
-  for (int t = 0; t < tiles->n_tiles; ++t) {
-    const int h = tiles->hw[2 * t], w = tiles->hw[2 * t + 1];
-    if (h < 2 || w < 2) {
-      // np.gradient needs >= 2 samples per axis: the reference raises ValueError here too
-      delete g;
-      set_error("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements are "
-                "required. (tile %d is %dx%d)", t, h, w);
-      return BGNN_ERR_INVALID;
-    }
-    BgnnTileMeta &m = g->h_tiles[t];
-    m.h = h; m.w = w; m.cell_off = (int32_t)cells; m.pad = 0;
-    m.rx = tiles->resolution[2 * t]; m.ry = tiles->resolution[2 * t + 1];
-    cells += (int64_t)h * w;
-    if (cells >= ((int64_t)1 << 30)) { delete g; set_error("batch too large: 2^30 cells or more; split it"); return BGNN_ERR_INVALID; }
-    // row bands of the feature kernel: ~2048 cells each for big batches, down to one 256-thread pass (256 cells) when the
-    // batch is small, so that a single tile still spreads over the whole chip
-    int rows_per = std::max(1, item_cells / w);
-    for (int r0 = 0; r0 < h; r0 += rows_per) items.push_back({t, r0, std::min(rows_per, h - r0), 0});
-    if (h != tiles->hw[0] || w != tiles->hw[1]) uniform = false;
-    if (w > g->max_w) g->max_w = w;
-  }
-  if (uniform) {
-    g->uni_h = tiles->hw[0]; g->uni_w = tiles->hw[1];
-    g->bh2 = (g->uni_h + 15) / 16; g->bw2 = (g->uni_w + 15) / 16;
-    g->n_blocks2 = g->n_tiles * g->bh2 * g->bw2;
-    g->bh3 = (g->uni_h + 7) / 8; g->bw3 = g->bw2;
-    g->n_blocks3 = g->n_tiles * g->bh3 * g->bw3;
-  } else {
-    for (int t = 0; t < tiles->n_tiles; ++t)
-      for (int r0 = 0; r0 < g->h_tiles[t].h; r0 += 16)
-        for (int c0 = 0; c0 < g->h_tiles[t].w; c0 += 16) items2.push_back({t, r0, c0, 0});
-    g->n_blocks2 = (int32_t)items2.size();
-    for (int t = 0; t < tiles->n_tiles; ++t)
-      for (int r0 = 0; r0 < g->h_tiles[t].h; r0 += 8)
-        for (int c0 = 0; c0 < g->h_tiles[t].w; c0 += 16) items3.push_back({t, r0, c0, 0});
-    g->n_blocks3 = (int32_t)items3.size();
-  }
-  // ragged batch: shelf-pack the grids (tallest first) onto a canvas for the fused layer kernels
-  std::vector<int32_t> atlas_pos;
-  BgnnTileMeta atlas_meta{};
-  if (!uniform && tiles->n_tiles >= 2 && ctx->opts.ragged_atlas) {
-    const int G = g->K == 16 ? 2 : 1;                                   // gutter = reach of the stencil
-    // First-fit shelves, grids by decreasing height (wider first among equals): a grid goes into the first shelf that is tall enough
-    // and has room, else it opens a new shelf.  A few canvas widths around sqrt(cells) are tried and the one with the fewest 8 x 16
-    // blocks wins -- a 50 000-node batch of refinement grids then needs ~480 blocks instead of ~525 (one width, next-fit), i.e. ONE
-    // round of workgroups on 512 slots instead of one and a bit.  (~10 us of host work per batch.)
-    std::vector<int> order(tiles->n_tiles);
-    for (int t = 0; t < tiles->n_tiles; ++t) order[t] = t;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-      return g->h_tiles[a].h != g->h_tiles[b].h ? g->h_tiles[a].h > g->h_tiles[b].h : g->h_tiles[a].w > g->h_tiles[b].w;
-    });
-    struct Shelf { int y, h, x; };
-    std::vector<Shelf> shelves;
-    auto pack = [&](int aw, int32_t *pos) -> int {                      // -> canvas height (before rounding to whole blocks)
-      shelves.clear();
-      int y = 0;
-      for (int t : order) {
-        const int h = g->h_tiles[t].h, w = g->h_tiles[t].w;
-        bool placed = false;
-        for (auto &sh : shelves)
-          if (sh.x + w <= aw && h <= sh.h) {
-            if (pos) { pos[2 * t] = sh.y; pos[2 * t + 1] = sh.x; }
-            sh.x += w + G; placed = true;
-            break;
-          }
-        if (!placed) {
-          if (pos) { pos[2 * t] = y; pos[2 * t + 1] = 0; }
-          shelves.push_back({y, h, w + G});
-          y += h + G;
-        }
-      }
-      return y - G;
-    };
-    const int aw_min = ((g->max_w + G + 15) / 16) * 16;
-    const int side = (int)std::sqrt((double)cells);
-    int aw = 0, ah = 0;
-    int64_t best = -1;
-    // <= 9 candidates between 0.9 and 1.5 sqrt(cells) (<= 4 for batches of many hundred grids: there the host time counts and a round more or less does not)
-    const int step = std::max(16, (side * 6 / 10 / (tiles->n_tiles > 400 ? 3 : 8) + 15) / 16 * 16);
-    for (int cand = std::max(aw_min, (side * 9 / 10 + 15) / 16 * 16);; cand += step) {
-      const int hc = ((pack(cand, nullptr) + 7) / 8) * 8;
-      const int64_t blocks = (int64_t)(hc / 8) * (cand / 16);
-      if (best < 0 || blocks < best) { best = blocks; aw = cand; ah = hc; }
-      if (cand >= side * 3 / 2 || cand + step > 8192) break;            // (always at least one candidate)
-    }
-    atlas_pos.assign((size_t)tiles->n_tiles * 2, 0);
-    (void)pack(aw, atlas_pos.data());
-    // worth it only if the canvas has fewer blocks than the grids have on their own (refinement grids: yes; two big tiles of
-    // different size: no -- they fill their own blocks already and would leave half a canvas empty)
-    if ((int64_t)(ah / 8) * (aw / 16) < (int64_t)items3.size()) {
-      g->atlas_w = aw; g->atlas_h = ah;
-      atlas_meta.h = g->atlas_h; atlas_meta.w = g->atlas_w; atlas_meta.cell_off = 0; atlas_meta.rx = 1.0; atlas_meta.ry = 1.0;
-    }
-  }
-  g->total_cells = (int32_t)cells; g->row_capacity = (int32_t)cells; g->n_items = (int32_t)items.size();
-  DevPool &P = ctx->pool;
-  int rc = BGNN_OK;
-#define GALLOC(ptr, type, count) if (rc == BGNN_OK) { void *_p = nullptr; rc = P.alloc((size_t)(count) * sizeof(type), &_p); ptr = (type *)_p; }
-  // uniform batches at one resolution: the two tables come from (or go into) the context's cache
-  bgnn_ctx::TableCache *hit = nullptr;
-  bool cacheable = uniform;
-  for (int t = 1; t < tiles->n_tiles && cacheable; ++t)
-    cacheable = tiles->resolution[2 * t] == tiles->resolution[0] && tiles->resolution[2 * t + 1] == tiles->resolution[1];
-  if (cacheable)
-    for (auto &e : ctx->table_cache)
-      if (e.n_tiles == g->n_tiles && e.h == g->uni_h && e.w == g->uni_w && e.item_cells == item_cells &&
-          e.rx == tiles->resolution[0] && e.ry == tiles->resolution[1]) { hit = &e; break; }
-  if (hit) {
-    g->d_tiles = hit->d_tiles; g->d_items = hit->d_items; g->tables_cached = true; g->table_cache_id = hit->id;
-    ++hit->refs;
-    hit->stamp = ++ctx->table_stamp;
-  } else if (cacheable) {
-    if (ctx->table_cache.size() >= 8) {                    // evict the least recently used entry NO LIVE GRAPH points into
-      size_t lru = ctx->table_cache.size();                // (nothing in flight reads it after a stream sync)
-      for (size_t i = 0; i < ctx->table_cache.size(); ++i)
-        if (ctx->table_cache[i].refs == 0 && (lru == ctx->table_cache.size() || ctx->table_cache[i].stamp < ctx->table_cache[lru].stamp)) lru = i;
-      if (lru == ctx->table_cache.size()) cacheable = false;          // every entry is pinned: this graph keeps private tables
-      else {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(ctx->table_cache[lru].d_tiles); (void)hipFree(ctx->table_cache[lru].d_items);
-        ctx->table_cache.erase(ctx->table_cache.begin() + lru);
-      }
-    }
-    if (cacheable) {
-      bgnn_ctx::TableCache e{g->n_tiles, g->uni_h, g->uni_w, item_cells, tiles->resolution[0], tiles->resolution[1], nullptr, nullptr,
-                             g->n_items, ++ctx->table_stamp, ctx->table_next_id++, 1};
-      if (hipMalloc((void **)&e.d_tiles, sizeof(BgnnTileMeta) * g->n_tiles) == hipSuccess &&
-          hipMalloc((void **)&e.d_items, sizeof(BgnnWorkItem) * g->n_items) == hipSuccess) {
-        ctx->table_cache.push_back(e);
-        g->d_tiles = e.d_tiles; g->d_items = e.d_items; g->tables_cached = true; g->table_cache_id = e.id;
-      } else {
-        (void)hipGetLastError();
-        if (e.d_tiles) (void)hipFree(e.d_tiles);
-        cacheable = false;
-      }
-    }
-  }
-  // ragged batches: every host-built table travels in ONE block (one staging copy, one H2D) -- with 50 000-node VR batches
-  // the per-batch host work is what bounds the stream
-  std::vector<char> blockh;
-  size_t o_tiles = 0, o_items = 0, o_items2 = 0, o_items3 = 0, o_atile = 0, o_apos = 0;
-  if (!uniform) {
-    auto put = [&](const void *p, size_t bytes) {
-      const size_t at = (blockh.size() + 255) & ~(size_t)255;
-      blockh.resize(at + bytes);
-      memcpy(blockh.data() + at, p, bytes);
-      return at;
-    };
-    o_tiles = put(g->h_tiles.data(), sizeof(BgnnTileMeta) * g->n_tiles);
-    o_items = put(items.data(), sizeof(BgnnWorkItem) * items.size());
-    o_items2 = put(items2.data(), sizeof(BgnnWorkItem) * items2.size());
-    if (g->atlas_h) {
-      o_atile = put(&atlas_meta, sizeof(atlas_meta));
-      o_apos = put(atlas_pos.data(), sizeof(int32_t) * atlas_pos.size());
-    } else {
-      o_items3 = put(items3.data(), sizeof(BgnnWorkItem) * items3.size());
-    }
-    GALLOC(g->d_tables, char, blockh.size())
-    if (rc == BGNN_OK) {
-      g->d_tiles = (BgnnTileMeta *)(g->d_tables + o_tiles); g->d_items = (BgnnWorkItem *)(g->d_tables + o_items);
-      g->d_items2 = (BgnnWorkItem *)(g->d_tables + o_items2);
-      if (g->atlas_h) { g->d_atlas_tile = (BgnnTileMeta *)(g->d_tables + o_atile); g->d_atlas_pos = (int32_t *)(g->d_tables + o_apos); }
-      else g->d_items3 = (BgnnWorkItem *)(g->d_tables + o_items3);
-    }
-  } else if (!g->tables_cached) {
-    GALLOC(g->d_tiles, BgnnTileMeta, g->n_tiles)
-    GALLOC(g->d_items, BgnnWorkItem, g->n_items)
-  }
-  GALLOC(g->d_node_id, int32_t, cells)
-  GALLOC(g->d_cell_of_node, int32_t, cells)
-  GALLOC(g->d_counts, int64_t, 4)
-  GALLOC(g->d_x8, float, cells * 8)
-  GALLOC(g->d_local_std, float, cells)
-  GALLOC(g->d_nbr, int32_t, cells * g->K)
-  // default edge feature list on a stencil the fused kernels know: compact edge storage (graph_build.hip, FeatureArgs)
-  // every edge feature list is a selection / ordering of (distance, depth_difference, slope, zero): all of them are built compact
-  // (round 3: the default list only -- any other list carried the full table and ran on the unfused kernels)
-  g->compact_edges = g->K == 4 || g->K == 8 || g->K == 16;
-  for (int i = 0; i < 4; ++i) g->edge_ids[i] = i < g->ED ? opts->edge_features[i] : BGNN_EF_ZERO;
-  g->edge_default = g->ED == 3 && opts->edge_features[0] == BGNN_EF_DISTANCE && opts->edge_features[1] == BGNN_EF_DEPTH_DIFFERENCE &&
-                    opts->edge_features[2] == BGNN_EF_SLOPE;
-  if (g->compact_edges) {
-    GALLOC(g->d_slope, float, cells * g->K)
-    GALLOC(g->d_node_depth, float, cells)
-    GALLOC(g->d_tile_dist, float4, g->n_tiles)
-  } else {
-    GALLOC(g->d_eattr, float, cells * g->K * g->ED)
-  }
-  if (g->atlas_h) GALLOC(g->d_atlas, int32_t, (size_t)g->atlas_h * g->atlas_w)
-  if (g->atlas_h && g->compact_edges) GALLOC(g->d_atlas_tile_of, int32_t, (size_t)g->atlas_h * g->atlas_w)
-#undef GALLOC
-  if (rc == BGNN_OK && !uniform) rc = ctx_upload(ctx, blockh.data(), blockh.size(), g->d_tables);
-  if (rc == BGNN_OK && uniform && !hit) rc = ctx_upload(ctx, g->h_tiles.data(), sizeof(BgnnTileMeta) * g->n_tiles, g->d_tiles);
-  if (rc == BGNN_OK && uniform && !hit) rc = ctx_upload(ctx, items.data(), sizeof(BgnnWorkItem) * items.size(), g->d_items);
-  if (rc == BGNN_OK) rc = launch_graph_build(ctx, g, tiles, opts);
-  if (rc != BGNN_OK) { graph_free(g); return rc; }
-  ctx->live_graphs.insert(g);
-  *out = g;
-  return BGNN_OK;
-}
-
-int bgnn_graph_from_edges(bgnn_ctx *ctx, int64_t n_nodes, int32_t n_feat, const float *x, int64_t n_edges,
-                          const int64_t *edge_index, int32_t edge_dim, const float *edge_attr, bgnn_graph **out) {
-  BGNN_REQUIRE(ctx && out, "bgnn_graph_from_edges: NULL argument");
-  BGNN_REQUIRE(n_nodes >= 0 && n_nodes < ((int64_t)1 << 31) && n_edges >= 0 && n_edges < ((int64_t)1 << 31),
-               "graph too large");
-  BGNN_REQUIRE(n_feat >= 1 && n_feat <= 8, "n_feat=%d unsupported (1..8)", n_feat);
-  BGNN_REQUIRE(edge_dim >= 1 && edge_dim <= 4, "edge_dim=%d unsupported (1..4)", edge_dim);
-  BGNN_REQUIRE((x || n_nodes == 0) && (edge_index || n_edges == 0) && (edge_attr || n_edges == 0), "NULL tensor");
-  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
-  bgnn_graph *g = new bgnn_graph();
-  g->ctx = ctx; g->kind = 1; g->F = n_feat; g->ED = edge_dim; g->K = 0;
-  g->total_cells = (int32_t)n_nodes; g->row_capacity = (int32_t)n_nodes; g->generic_E = n_edges;
-  int rc = launch_generic_build(ctx, g, n_nodes, n_feat, x, n_edges, edge_index, edge_dim, edge_attr);
-  if (rc != BGNN_OK) { graph_free(g); return rc; }
-  ctx->live_graphs.insert(g);
-  *out = g;
-  return BGNN_OK;
-}
-
-int bgnn_graph_destroy(bgnn_graph *g) {
-  if (!g) return BGNN_OK;
-  graph_free(g);
-  return BGNN_OK;
-}
-
-int bgnn_graph_counts(bgnn_graph *g, int64_t *n_nodes, int64_t *n_edges, int32_t *n_feat, int32_t *edge_dim,
-                      int64_t *node_off, int64_t *edge_off) {
-  BGNN_REQUIRE(g, "graph is NULL");
-  bgnn_ctx *ctx = g->ctx;
-  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
-  if (n_feat) *n_feat = g->F;
-  if (edge_dim) *edge_dim = g->ED;
-  if (g->kind == 1) {
-    if (n_nodes) *n_nodes = g->total_cells;
-    if (n_edges) *n_edges = g->generic_E;
-    if (node_off) { node_off[0] = 0; node_off[1] = g->total_cells; }
-    if (edge_off) { edge_off[0] = 0; edge_off[1] = g->generic_E; }
-    return BGNN_OK;
-  }
-  BGNN_TRY(launch_graph_count_edges(g));
-  std::vector<int64_t> tc((size_t)g->n_tiles * 2);
-  BGNN_HIP_CHECK(hipMemcpyAsync(tc.data(), ctx->ws[5], tc.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  BGNN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  int64_t nn = 0, ne = 0;
-  for (int t = 0; t < g->n_tiles; ++t) {
-    if (node_off) node_off[t] = nn;
-    if (edge_off) edge_off[t] = ne;
-    nn += tc[t]; ne += tc[g->n_tiles + t];
-  }
-  if (node_off) node_off[g->n_tiles] = nn;
-  if (edge_off) edge_off[g->n_tiles] = ne;
-  g->n_nodes_host = nn; g->n_edges_host = ne;
-  if (n_nodes) *n_nodes = nn;
-  if (n_edges) *n_edges = ne;
-  return BGNN_OK;
-}
-
-int bgnn_graph_export(bgnn_graph *g, float *x, int64_t *edge_index, float *edge_attr, float *pos,
-                      int64_t *valid_rows, int64_t *valid_cols, float *local_std, int64_t *batch) {
-  BGNN_REQUIRE(g, "graph is NULL");
-  BGNN_REQUIRE(g->kind == 0, "bgnn_graph_export: only graphs built by bgnn_graph_build can be exported");
-  BGNN_HIP_CHECK(hipSetDevice(g->ctx->device));
-  return launch_graph_export(g, x, edge_index, edge_attr, pos, valid_rows, valid_cols, local_std, batch);
-}
-
-int bgnn_graph_scatter(bgnn_graph *g, const float *node_values, float fill, float *grid) {
-  BGNN_REQUIRE(g && node_values && grid, "bgnn_graph_scatter: NULL argument");
-  BGNN_REQUIRE(g->kind == 0, "Data object missing grid_shape metadata");
-  BGNN_HIP_CHECK(hipSetDevice(g->ctx->device));
-  return launch_graph_scatter(g, node_values, fill, grid);
 }
 
 // ---- forward ----------------------------------------------------------------------------------
@@ -924,7 +581,7 @@ int bgnn_infer_tiles(bgnn_ctx *ctx, bgnn_model *m, const bgnn_tiles *tiles, cons
   bgnn_graph *g = nullptr;
   float *const grids[3] = {classification, confidence, correction};
   // (the compaction scan writes the node count there itself; a ragged batch's canvas fill zero-fills the result grids on its way)
-  BGNN_TRY(graph_build_impl(ctx, tiles, opts, &g, n_nodes_out, grids));
+  BGNN_TRY(graph_build(ctx, tiles, opts, &g, n_nodes_out, grids));
   const int64_t rows = g->row_capacity;
   GridOut go;
   go.cls = classification; go.conf = confidence; go.corr = correction; go.norm_floor = norm_floor;

@@ -14,6 +14,7 @@
 #include "../../include/bgnn_train.h"
 #include "../../include/bgnn_optim.h"
 #include "model_images.h"   // WeightLayout, ImageMap: the weight blob's and the packed model's layouts (host only)
+#include "graph_plan.h"     // BgnnTileMeta, BgnnWorkItem, GraphPlan: the layout of a tile batch (host only)
 
 namespace bgnn {
 
@@ -59,19 +60,6 @@ struct ProfRecord {
 };
 
 }  // namespace bgnn
-
-// Per-tile metadata (device + host copy)
-struct BgnnTileMeta {
-  int32_t h, w;
-  int32_t cell_off;   // first cell of the tile in the concatenated cell space
-  int32_t pad;
-  double rx, ry;      // resolution (x, y)
-};
-
-// Work item of the tile-structured kernels: a band of rows of one tile
-struct BgnnWorkItem {
-  int32_t tile, r0, nr, pad;
-};
 
 // Run-time switches of a context.  Defaults come from the environment ONCE, at bgnn_ctx_create (BGNN_SPLIT_F16 /
 // BGNN_SPLIT_BF16, BGNN_NO_FUSED, BGNN_NO_FOLD, ...); afterwards only bgnn_ctx_set_option changes them -- no getenv on
@@ -218,6 +206,7 @@ struct bgnn_model {
 
 struct bgnn_graph {
   bgnn_ctx *ctx;
+  mutable std::vector<void *> blocks;   // every pool block this graph was given (graph_alloc): what graph_free releases
   int kind;                   // 0 = stencil grid graph (ELL), 1 = generic CSR
   int32_t n_tiles = 0;
   int32_t total_cells = 0;    // grid: number of cells; generic: number of nodes
@@ -271,12 +260,11 @@ struct bgnn_graph {
   // 8x16 cell blocks for the fused layer kernel
   BgnnWorkItem *d_items3 = nullptr;
   int32_t n_blocks3 = 0, bh3 = 0, bw3 = 0;
-  int32_t max_w = 0;
+  int32_t max_h = 0, max_w = 0;
   // Atlas of a RAGGED batch (refinement grids of 3..50 cells a side): the grids are shelf-packed, with a gutter of invalid cells
   // as wide as the stencil's reach, into one canvas whose 8x16 blocks the fused layer kernels walk instead of per-grid blocks
   // (which are 68 % full on config 4's grids; the canvas is ~85 % full).  d_atlas[canvas cell] = node id or -1.
   int32_t *d_atlas = nullptr;
-  char *d_tables = nullptr;               // ragged batch: ONE block with every host-built table (tiles, items*, canvas tables)
   BgnnTileMeta *d_atlas_tile = nullptr;   // the canvas as ONE tile {h, w, cell_off = 0}
   int32_t *d_atlas_pos = nullptr;         // [n_tiles][2] = (row, column) of each grid's origin on the canvas
   int32_t atlas_h = 0, atlas_w = 0;
@@ -291,6 +279,35 @@ namespace bgnn {
 
 int ctx_workspace(bgnn_ctx *ctx, int slot, size_t bytes, void **out);
 int ctx_upload(bgnn_ctx *ctx, const void *host, size_t bytes, void *dev);
+
+// ---- graph handles (graph_api.hip) ----------------------------------------------------------
+// bgnn_graph_build with the two extras of bgnn_infer_tiles: the caller's copy of the node count, the result grids a canvas fill clears
+int graph_build(bgnn_ctx *ctx, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, bgnn_graph **out, int64_t *n_nodes_copy,
+                float *const *clear_grids);
+void graph_free(bgnn_graph *g);
+// The one way a member of a bgnn_graph gets device memory: a pool block the graph records, released by graph_free -- at build
+// time or on demand (ensure_edge_attrs, ensure_transposed_index).  Scratch of a single call is not a member: plain pool.alloc.
+template <class T>
+int graph_alloc(const bgnn_graph *g, T *&ptr, size_t count) {
+  void *p = nullptr;
+  BGNN_TRY(g->ctx->pool.alloc(count * sizeof(T), &p));
+  g->blocks.push_back(p);
+  ptr = (T *)p;
+  return BGNN_OK;
+}
+// The node-feature columns of a tile batch: the requested features (uncertainty skipped when the batch has none), then uncertainty
+// appended when given and not listed (graph_construction.py:288-316).  -> their number; ids (optional) receives the first 8
+inline int node_feature_columns(const bgnn_tiles *tiles, const bgnn_graph_opts *opts, int *ids) {
+  int nf = 0;
+  bool listed_unc = false;
+  auto add = [&](int fid) { if (ids && nf < 8) ids[nf] = fid; ++nf; };
+  for (int i = 0; i < opts->n_node_features; ++i) {
+    if (opts->node_features[i] == BGNN_NF_UNCERTAINTY) { listed_unc = true; if (!tiles->uncertainty) continue; }
+    add(opts->node_features[i]);
+  }
+  if (tiles->uncertainty && !listed_unc) add(BGNN_NF_UNCERTAINTY);
+  return nf;
+}
 
 // ---- host helpers shared by bgnn_api.hip, model_pack.hip and train_api.hip ------------------
 int model_canonical_V(bgnn_model *m, const bgnn_graph *g, const float **out);        // model_pack.hip

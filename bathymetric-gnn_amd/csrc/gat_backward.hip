@@ -274,12 +274,11 @@ int ensure_transposed_index(const bgnn_graph *g) {
   BGNN_TRY(ensure_stencil_table(g));
   const int64_t rows = g->row_capacity;
   const int64_t cap = g->kind == 1 ? std::max<int64_t>(g->generic_E, 1) : std::max<int64_t>(rows * g->K, 1);
-  void *p0 = nullptr, *p1 = nullptr, *p2 = nullptr, *p3 = nullptr;
-  BGNN_TRY(ctx->pool.alloc((size_t)(rows + 1) * sizeof(int32_t), &p0));
-  BGNN_TRY(ctx->pool.alloc((size_t)cap * sizeof(int32_t), &p1));
-  BGNN_TRY(ctx->pool.alloc((size_t)cap * sizeof(int32_t), &p2));
+  void *p3 = nullptr;
+  BGNN_TRY(graph_alloc(g, g->d_tr_ptr, rows + 1));
+  BGNN_TRY(graph_alloc(g, g->d_tr_slot, cap));
+  BGNN_TRY(graph_alloc(g, g->d_tr_dst, cap));
   BGNN_TRY(ctx->pool.alloc((size_t)std::max<int64_t>(rows, 1) * 2 * sizeof(int32_t), &p3));
-  g->d_tr_ptr = (int32_t *)p0; g->d_tr_slot = (int32_t *)p1; g->d_tr_dst = (int32_t *)p2;
   int32_t *cnt = (int32_t *)p3, *cursor = cnt + rows;
   const int32_t *rowptr = g->kind == 1 ? g->d_rowptr : nullptr;
   BGNN_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)rows * 2 * sizeof(int32_t), ctx->stream));

@@ -1239,11 +1239,7 @@ int ensure_stencil_table(const bgnn_graph *g) {
 int ensure_edge_attrs(const bgnn_graph *g) {
   if (g->kind != 0 || !g->compact_edges || g->eattr_valid || g->total_cells <= 0) return BGNN_OK;
   bgnn_ctx *ctx = g->ctx;
-  if (!g->d_eattr) {
-    void *p = nullptr;
-    BGNN_TRY(ctx->pool.alloc((size_t)g->total_cells * g->K * g->ED * sizeof(float), &p));
-    g->d_eattr = (float *)p;
-  }
+  if (!g->d_eattr) BGNN_TRY(graph_alloc(g, g->d_eattr, (size_t)g->total_cells * g->K * g->ED));
   const Stencil st = make_stencil(g->K);
   hipLaunchKernelGGL(expand_edge_attrs_kernel, dim3((unsigned)((g->total_cells + 255) / 256)), dim3(256), 0, ctx->stream, g->d_tiles,
                      g->n_tiles, g->d_node_id, (int64_t)g->total_cells, st, g->d_slope, g->d_node_depth, g->d_eattr, g->ED,
@@ -1256,8 +1252,7 @@ int ensure_edge_attrs(const bgnn_graph *g) {
 int launch_graph_build(bgnn_ctx *ctx, bgnn_graph *g, const bgnn_tiles *tiles, const bgnn_graph_opts *opts) {
   const Stencil st = make_stencil(opts->connectivity);
   const int64_t cells = g->total_cells;
-  int max_h = 0, max_w = 0;
-  for (auto &t : g->h_tiles) { if (t.h > max_h) max_h = t.h; if (t.w > max_w) max_w = t.w; }
+  const int max_h = g->max_h, max_w = g->max_w;
   // box statistics: 64 running sums per workgroup fill the chip from ~500 workgroups up; below that (a single tile: four workgroups
   // a pass) the 16-wide instances put four times the CUs to work and leave a quarter of the loads, divisions and stores between barriers
   const int64_t wide_wgs = (int64_t)((max_h + 63) / 64) * g->n_tiles;
@@ -1343,15 +1338,7 @@ int launch_graph_build(bgnn_ctx *ctx, bgnn_graph *g, const bgnn_tiles *tiles, co
     a.slope = g->d_slope; a.node_depth = g->d_node_depth; a.tile_dist = g->d_tile_dist;            // (compact: d_eattr is null here)
     g->nbr_valid = false; g->eattr_valid = !g->compact_edges;
     a.F = g->F; a.ED = g->ED;
-    // final column list: requested features (uncertainty skipped when absent), then
-    // uncertainty appended when given and not listed (:288-316)
-    int nf = 0; bool listed_unc = false;
-    for (int i = 0; i < opts->n_node_features; ++i) {
-      int fid = opts->node_features[i];
-      if (fid == BGNN_NF_UNCERTAINTY) { listed_unc = true; if (!tiles->uncertainty) continue; }
-      a.feat_ids[nf++] = fid;
-    }
-    if (tiles->uncertainty && !listed_unc) a.feat_ids[nf++] = BGNN_NF_UNCERTAINTY;
+    (void)node_feature_columns(tiles, opts, a.feat_ids);
     for (int i = 0; i < opts->n_edge_features; ++i) a.edge_ids[i] = opts->edge_features[i];
     // the LDS-tiled form pays where its 8 x 64 chunks are mostly full: uniform batches of tiles at least one chunk wide and tall.
     // Refinement grids of 3 .. 50 cells a side (ragged VR batches) leave it 10 % full and three barriers per chunk: measured 4x slower
@@ -1509,18 +1496,13 @@ __global__ void generic_gather_attr_kernel(const int32_t *eid, int64_t nnz_cap, 
 
 int launch_generic_build(bgnn_ctx *ctx, bgnn_graph *g, int64_t n_nodes, int32_t n_feat, const float *x, int64_t n_edges,
                          const int64_t *edge_index, int32_t edge_dim, const float *edge_attr) {
-  DevPool &P = ctx->pool;
   const int64_t N = n_nodes, E = n_edges;
-  int rc = BGNN_OK;
-#define GALLOC(ptr, type, count) if (rc == BGNN_OK) { void *_p = nullptr; rc = P.alloc((size_t)((count) > 0 ? (count) : 1) * sizeof(type), &_p); ptr = (type *)_p; }
-  GALLOC(g->d_counts, int64_t, 4)
-  GALLOC(g->d_x8, float, N * 8)
-  GALLOC(g->d_rowptr, int32_t, N + 1)
-  GALLOC(g->d_nbr, int32_t, E)
-  GALLOC(g->d_edge_perm, int32_t, E)
-  GALLOC(g->d_eattr, float, E * edge_dim)
-#undef GALLOC
-  BGNN_TRY(rc);
+  BGNN_TRY(graph_alloc(g, g->d_counts, 4));          // (a count of 0 gives the pool's smallest block)
+  BGNN_TRY(graph_alloc(g, g->d_x8, N * 8));
+  BGNN_TRY(graph_alloc(g, g->d_rowptr, N + 1));
+  BGNN_TRY(graph_alloc(g, g->d_nbr, E));
+  BGNN_TRY(graph_alloc(g, g->d_edge_perm, E));
+  BGNN_TRY(graph_alloc(g, g->d_eattr, E * edge_dim));
   const int64_t counts[4] = {N, E, 0, 0};
   BGNN_TRY(ctx_upload(ctx, counts, sizeof(counts), g->d_counts));
   if (N == 0) return BGNN_OK;

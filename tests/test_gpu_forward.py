@@ -1339,6 +1339,118 @@ def test_ragged_batch_canvas_walk_equals_per_grid_blocks(connectivity, path, gpu
     assert set(np.unique(a[0].cpu().numpy())) <= {0.0, 1.0, 2.0} and float(a[1].max()) > 0
 
 
+def _vr_shapes():
+    """the 65 shapes of test_ragged_batch_canvas_walk_equals_per_grid_blocks (tests/graph_plan_check.cpp: kVrShapes)"""
+    rng = np.random.default_rng(5)
+    return [(int(rng.integers(3, 51)), int(rng.integers(3, 51))) for _ in range(60)] + [(2, 2), (2, 90), (70, 3), (3, 300), (50, 50)]
+
+
+def _many_small_grids():
+    """tests/graph_plan_check.cpp, many_small_grids: 420 grids of 2..8 cells a side from the same integer generator"""
+    x, sides = 12345, []
+    for _ in range(840):
+        x = (x * 1103515245 + 12345) & 0x7fffffff
+        sides.append(2 + (x >> 16) % 7)
+    return list(zip(sides[0::2], sides[1::2]))
+
+
+@pytest.mark.parametrize("connectivity", ["8-connected", "16-dilated"])
+@pytest.mark.parametrize("batch", ["many420", "rejected_canvas"])
+def test_canvas_step_rule_for_many_grids_and_rejected_canvas(batch, connectivity, gpu_device):
+    """The two branches of the canvas packer no other GPU test reaches (host side: tests/test_host_graph_plan.py, cases many420_* and
+    rejected_canvas): more than 400 grids in a batch (the coarser candidate step), and two big grids of different size whose canvas
+    would hold more blocks than they have on their own (rejected: per-grid blocks).  Exact path; ragged_atlas = 1 must equal
+    ragged_atlas = 0 bit for bit, and the first and the last grid must be within 1e-4 of the float32 oracle."""
+    from bathymetric_gnn_amd import runtime as rt, synthetic
+    from bathymetric_gnn_amd.data import GraphBuilder
+    from bathymetric_gnn_amd.models.pipeline import TileBatchEngine
+    shapes = _many_small_grids() if batch == "many420" else [(40, 48), (33, 64)]
+    assert len(shapes) == (420 if batch == "many420" else 2) and shapes[0] == ((8, 8) if batch == "many420" else (40, 48))
+    sd = synthetic.synthetic_state_dict(in_channels=8, seed=1234)
+    model = _model(sd, in_channels=8)
+    gb = GraphBuilder(device=gpu_device, connectivity=connectivity)
+    eng = TileBatchEngine(model, gb, gpu_device)
+    grids = [synthetic.synthetic_tile(h, w, 700 + i, "V1" if min(h, w) >= 20 else "V0") for i, (h, w) in enumerate(shapes)]
+    depth = [g[0] for g in grids]; mask = [g[1] for g in grids]; unc = [np.abs(g[0]) * 0.01 for g in grids]
+    hw, res, d, m, u = gb.upload_tiles(depth, mask, unc, [(0.5, 0.5)] * len(grids))
+    ctx = rt.get_context(gpu_device)
+    try:
+        ctx.set_option("ragged_atlas", 1)
+        a = eng.infer_device(hw, res, d, m, u).clone()
+        ctx.set_option("ragged_atlas", 0)
+        b = eng.infer_device(hw, res, d, m, u).clone()
+    finally:
+        ctx.set_option("ragged_atlas", 1)
+    assert torch.equal(a, b)
+    out = a.cpu().numpy()
+    offs = np.concatenate([[0], np.cumsum([h * w for h, w in shapes])])
+    for t in (0, len(shapes) - 1):
+        h, w = shapes[t]
+        assert mask[t].any()
+        og = graph_cpu.build_graph(depth[t], mask[t], unc[t], (0.5, 0.5), connectivity=connectivity)
+        ref = gat_cpu.process_tile(sd, og)
+        got = out[:, offs[t]:offs[t + 1]].reshape(3, h, w)
+        e_conf = float(np.abs(got[1] - ref["confidence"]).max()); e_corr = float(np.abs(got[2] - ref["correction"]).max())
+        print(f"{batch} {connectivity} grid {t} ({h}x{w}): |d confidence| {e_conf:.3g}  |d correction| {e_corr:.3g}")
+        assert e_conf < TOL and e_corr < TOL
+        sure = _sure_grid(sd, og)
+        assert np.array_equal(got[0][sure], ref["classification"][sure])
+        assert np.all(got[:, ~mask[t]] == 0)
+
+
+def test_repeated_batches_reach_a_pool_steady_state(gpu_device):
+    """Graph handles give their buffers back to the context's pool: from the second batch of a shape on, a context allocates nothing.
+    One uniform batch (8 tiles of 64 x 64: cached tables) and one ragged batch (the 65 VR shapes: one table block, a canvas) five times
+    each on ONE context: free device memory after the second run equals that after the fifth, and every run gives the same grids."""
+    from bathymetric_gnn_amd import runtime as rt, synthetic
+    from bathymetric_gnn_amd.data import GraphBuilder
+    from bathymetric_gnn_amd.models.pipeline import TileBatchEngine
+    model = _model(synthetic.synthetic_state_dict(in_channels=8, seed=1234), in_channels=8)
+    gb = GraphBuilder(device=gpu_device)
+    ctx = rt.new_context(gpu_device)
+    eng = TileBatchEngine(model, gb, gpu_device, ctx=ctx)
+    for shapes in ([(64, 64)] * 8, _vr_shapes()):
+        grids = [synthetic.synthetic_tile(h, w, 300 + i, "V1" if min(h, w) >= 20 else "V0") for i, (h, w) in enumerate(shapes)]
+        hw, res, d, m, u = gb.upload_tiles([g[0] for g in grids], [g[1] for g in grids], [np.abs(g[0]) * 0.01 for g in grids],
+                                           [(0.7, 0.9)] * len(grids))
+        out = torch.empty((3, d.numel()), dtype=torch.float32, device=gpu_device)
+        first = torch.empty_like(out)
+        free = []
+        for i in range(5):
+            eng.infer_device(hw, res, d, m, u, out=out)
+            torch.cuda.synchronize()
+            if i == 0:
+                first.copy_(out)
+                assert float(first[1].max()) > 0
+            assert torch.equal(out, first)
+            torch.cuda.synchronize()
+            free.append(torch.cuda.mem_get_info(gpu_device)[0])
+        print("free device memory after each run:", free)
+        assert free[1] == free[4]
+    ctx.close()
+
+
+def test_rejected_batch_leaves_the_context_usable(gpu_device):
+    """A batch with a 1 x 5 tile is refused by the planner, before a handle exists (ValueError, worded like numpy's np.gradient); the
+    next valid batch on the same context gives what a fresh context gives, bit for bit."""
+    from bathymetric_gnn_amd import runtime as rt, synthetic
+    from bathymetric_gnn_amd.data import GraphBuilder
+    from bathymetric_gnn_amd.models.pipeline import TileBatchEngine
+    model = _model(synthetic.synthetic_state_dict(seed=1234))
+    gb = GraphBuilder(device=gpu_device)
+    shapes = [(40, 36), (1, 5), (24, 30)]
+    grids = [synthetic.synthetic_tile(h, w, 40 + i, "V1")[0] if h > 1 else np.full((h, w), 10.0, np.float32) for i, (h, w) in enumerate(shapes)]
+    ctx = rt.new_context(gpu_device)
+    eng = TileBatchEngine(model, gb, gpu_device, ctx=ctx)
+    with pytest.raises(ValueError, match=r"Shape of array too small to calculate a numerical gradient.*tile 1 is 1x5"):
+        eng.infer_device(*gb.upload_tiles(grids, None, None, [(0.5, 0.5)] * 3))
+    ctx.end()
+    good = gb.upload_tiles([grids[0], grids[2]], None, None, [(0.5, 0.5)] * 2)
+    after = eng.infer_device(*good).clone()
+    fresh = TileBatchEngine(model, gb, gpu_device, ctx=rt.new_context(gpu_device)).infer_device(*good)
+    assert torch.equal(after, fresh) and float(after[1].max()) > 0
+
+
 def test_extractor_layer_inside_the_lin0_gemm_is_bit_identical(gpu_device):
     """Option fused_front (default on): at >= 65 536 rows the exact path runs feature extractor layer 1 inside the lin_0 GEMM
     (same MFMA sequence, h1 stays in registers) instead of as its own launch.  Every output must be bit-identical; the bf16
