@@ -6,8 +6,10 @@ from .tiling import Tile, TileSpec, TileManager, TileMerger
 from .vr_bag import RefinementGrid, VRBagHandler, VRBagWriter, SRBagHandler, SRBagWriter, SidecarBuilder, detect_bag_type
 from .synthetic_noise import NoiseAugmentor, NoiseBatch, NoiseLabel, SyntheticNoiseGenerator, training_targets
 from .ground_truth import Alignment, GroundTruth, align_survey_pair, compute_ground_truth, ground_truth_stats
+from .noise_analysis import analyze_noise_patterns, print_analysis
 
 __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "TileSpec", "TileManager", "TileMerger",
            "RefinementGrid", "VRBagHandler", "VRBagWriter", "SRBagHandler", "SRBagWriter", "SidecarBuilder", "detect_bag_type",
            "SyntheticNoiseGenerator", "NoiseAugmentor", "NoiseLabel", "NoiseBatch", "training_targets",
-           "Alignment", "GroundTruth", "align_survey_pair", "compute_ground_truth", "ground_truth_stats"]
+           "Alignment", "GroundTruth", "align_survey_pair", "compute_ground_truth", "ground_truth_stats",
+           "analyze_noise_patterns", "print_analysis"]

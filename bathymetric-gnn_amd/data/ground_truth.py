@@ -155,6 +155,11 @@ class GroundTruth:
         """``(labels, difference, noisy_depth, uncertainty)``: the leading arguments of ``TileStore.from_ground_truth``."""
         return self.labels, self.difference, self.noisy_depth, self.uncertainty
 
+    def analyze(self, **kw) -> Dict[str, Any]:
+        """The reference's noise pattern analysis of this ground truth (``noise_analysis.analyze_noise_patterns``)."""
+        from .noise_analysis import analyze_noise_patterns
+        return analyze_noise_patterns(self, **kw)
+
 
 def _window_to_device(plane, window, device) -> torch.Tensor:
     r0, r1, c0, c1 = window

@@ -260,6 +260,24 @@ EVAL_ACC_DTYPE = [("total", "<i8"), ("correct", "<i8"), ("confusion", "<i8", (4,
                   ("covered_correct", "<i8", (5,)), ("conf_sum", "<f8"), ("conf_sq", "<f8"), ("conf_correct_sum", "<f8"),
                   ("conf_incorrect_sum", "<f8"), ("conf_cells", "<i8")]
 
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_analysis.h declares (noise pattern analysis of a ground truth)
+_ANALYSIS_SIGNATURES = {
+    "bgnn_noise_analysis_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "bgnn_noise_analysis": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t] + [C.c_void_p] * 3),
+}
+# BGNN_NA_*: the result block of a noise pattern analysis
+NA_MAX_CELLS = 2 ** 31 - 1
+NA_DEPTH_EDGES = (0, 10, 20, 50, 100, 200, 500, 1000, 10000)
+NA_SIZE_EDGES = (1, 2, 5, 10, 50, 100, 1000, 10000)
+NA_BYTES = 528
+NA_DTYPE = [("valid", "<i8"), ("noise", "<i8"), ("seafloor", "<i8"), ("positive", "<i8"), ("negative", "<i8"), ("nonfinite", "<i8"),
+            ("bin_noise", "<i8", (8,)), ("bin_valid", "<i8", (8,)), ("abs_sum", "<f8"), ("sq_sum", "<f8"), ("dev_sq_sum", "<f8"),
+            ("pos_sum", "<f8"), ("neg_sum", "<f8"), ("bin_abs_sum", "<f8", (8,)), ("abs_max", "<f4"), ("pad", "<f4"),
+            ("mag_rank", "<i8", (6,)), ("mag_value", "<f4", (6,)), ("num_clusters", "<i8"), ("cluster_cells", "<i8"),
+            ("max_cluster", "<i8"), ("isolated", "<i8"), ("size_bins", "<i8", (7,)), ("size_mid", "<i8", (2,)),
+            ("rough_count", "<i8", (2,)), ("rough_sum", "<f8", (2,)), ("rough_mid", "<f8", (4,))]
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -270,7 +288,7 @@ class BgnnError(RuntimeError):
 
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
-    include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h and include/bgnn_eval.h.  Needs no GPU."""
+    include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h and include/bgnn_analysis.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -283,7 +301,7 @@ def load_library(path: Optional[str] = None):
         lib = C.CDLL(p)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
                 list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
-                list(_EVAL_SIGNATURES.items()):
+                list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,136 @@
+"""Noise pattern analysis on the device against the reference's own output: every fixture under tests/golden/analysis (written by
+make_golden_analysis.py with the reference's ``analyze_ground_truth``) from host arrays and from device tensors, under the rules
+of _analysis_cpu; once through ``GroundTruth.analyze()``; equal bits from two calls; and random masks at three densities on a
+300 x 517 grid -- up to the site-percolation threshold, where ragged clusters cross every tile border -- against the numpy / scipy
+restatement.  An 8-connected labelling fails ``checkerboard_64``, a lost cross-tile merge fails ``serpentine_128``, ``comb_130x67``
+and the random masks."""
+import numpy as np
+import pytest
+import torch
+from scipy import ndimage
+
+from _analysis_cpu import ANALYSIS_CASES, ROUGH_RTOL, STRICT_CASES, check_analysis, load_analysis_case, numpy_analysis, numpy_analysis_block
+from _eval_checks import grids_of, load_case, sum_tolerance
+
+pytestmark = pytest.mark.gpu
+INTEGER_FIELDS = ("valid", "noise", "seafloor", "positive", "negative", "nonfinite", "bin_noise", "bin_valid", "mag_rank", "mag_value",
+                  "abs_max", "num_clusters", "cluster_cells", "max_cluster", "isolated", "size_bins", "size_mid")
+
+
+@pytest.mark.parametrize("on_device", [False, True], ids=["host_arrays", "device_tensors"])
+@pytest.mark.parametrize("name", ANALYSIS_CASES)
+def test_fixture(name, on_device, gpu_device):
+    from bathymetric_gnn_amd.data import analyze_noise_patterns
+    planes, want, _ = load_analysis_case(name)
+    given = tuple(torch.from_numpy(p.copy()).to(gpu_device) for p in planes) if on_device else planes
+    got = analyze_noise_patterns(given, file=name + ".tif", device=gpu_device)
+    check_analysis(got, want, planes, strict=name in STRICT_CASES)
+
+
+def test_float32_label_band(gpu_device):
+    from bathymetric_gnn_amd.data import analyze_noise_patterns
+    planes, want, _ = load_analysis_case("mixed_97x203")
+    band = planes[0].astype(np.float32)
+    for labels in (band, torch.from_numpy(band).to(gpu_device)):
+        check_analysis(analyze_noise_patterns((labels,) + planes[1:], file="mixed_97x203.tif", device=gpu_device), want, planes)
+
+
+def test_ground_truth_analyze(gpu_device):
+    from bathymetric_gnn_amd.data import compute_ground_truth
+    g, _ = load_case("truth", "large")
+    clean, noisy = grids_of(g)
+    gt = compute_ground_truth(clean, noisy, 0.15, device=gpu_device)
+    got = gt.analyze(file="large.tif")
+    planes = tuple(t.cpu().numpy() for t in (gt.labels, gt.difference, gt.noisy_depth, gt.clean_depth))
+    assert int((planes[0] == 2).sum()) > 0
+    check_analysis(got, numpy_analysis(*planes, file="large.tif"), planes, strict=True, fixture=False)
+
+
+@pytest.mark.parametrize("name", ["mixed_97x203", "serpentine_128", "ties"])
+def test_two_calls_give_equal_bits(name, gpu_device):
+    from bathymetric_gnn_amd.data.noise_analysis import noise_analysis_build
+    planes, _, _ = load_analysis_case(name)
+    dev = tuple(torch.from_numpy(p.copy()).to(gpu_device) for p in planes)
+    first = noise_analysis_build(*dev).cpu().numpy()
+    second = noise_analysis_build(*dev).cpu().numpy()
+    assert first.tobytes() == second.tobytes()
+
+
+@pytest.mark.parametrize("density", [0.3, 0.5, 0.593])
+def test_random_mask_past_the_fixtures(density, gpu_device):
+    from bathymetric_gnn_amd.data.noise_analysis import analysis_from_block, noise_analysis_build, split_result
+    rng = np.random.default_rng([20240816, int(density * 1000)])
+    h, w = 300, 517
+    labels = np.where(rng.random((h, w)) < density, 2, 0).astype(np.int32)
+    labels[rng.random((h, w)) < 0.02] = -1
+    rr, cc = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    clean = (-40 + 0.03 * rr + 0.02 * cc + 0.1 * rng.standard_normal((h, w))).astype(np.float32)
+    difference = (0.05 * rng.standard_normal((h, w))).astype(np.float32)
+    noise = labels == 2
+    difference[noise] = ((0.2 + rng.exponential(0.3, int(noise.sum()))) * rng.choice([-1.0, 1.0], int(noise.sum()))).astype(np.float32)
+    difference[labels < 0] = np.nan
+    noisy = (clean + np.nan_to_num(difference)).astype(np.float32)
+    noisy[:, :200] += np.float32(25)                           # two populated depth bins
+    planes = (labels, difference, noisy, clean)
+    want_block, want_cn, want_cv = numpy_analysis_block(*planes)
+    out = noise_analysis_build(*(torch.from_numpy(p).to(gpu_device) for p in planes)).cpu().numpy()
+    block, cn, cv = split_result(out, w)
+    assert np.array_equal(cn, want_cn) and np.array_equal(cv, want_cv)
+    for k in INTEGER_FIELDS + ("rough_count",):
+        assert np.array_equal(block[k], want_block[k]), (k, block[k], want_block[k])
+    labeled, _ = ndimage.label(noise)                           # (the input's own property: many clusters lie across tile borders)
+    tile = (rr // 16) * 1000 + cc // 64
+    first = ndimage.minimum(tile, labeled, np.arange(1, labeled.max() + 1))
+    last = ndimage.maximum(tile, labeled, np.arange(1, labeled.max() + 1))
+    assert int((first != last).sum()) > 100
+    want = analysis_from_block(want_block, want_cn, want_cv, (h, w), "random.tif")
+    check_analysis(analysis_from_block(block, cn, cv, (h, w), "random.tif"), want, planes, strict=True, fixture=False)
+
+
+@pytest.mark.parametrize("shape,with_roughness", [((2, 131073), True), ((1030, 2049), False)], ids=["2049_tiles", "2062_chunks_2145_tiles"])
+def test_more_work_than_one_launch_grid(shape, with_roughness, gpu_device):
+    """Every kernel launches at most 2048 workgroups and strides over the rest: 2 x 131073 has 2049 tiles of 16 x 64 (one workgroup
+    takes a second tile, with its LDS reused), 1030 x 2049 has 2062 chunks of 1024 cells and 2145 tiles (held to numpy on
+    everything but the roughness, whose 25-plane restatement is too slow at that size)."""
+    from bathymetric_gnn_amd.data.noise_analysis import noise_analysis_build, split_result
+    rng = np.random.default_rng([20240817, shape[0]])
+    h, w = shape
+    labels = np.where(rng.random(shape) < 0.55, 2, 0).astype(np.int32)
+    labels[rng.random(shape) < 0.02] = -1
+    clean = (-40 + 0.1 * rng.standard_normal(shape)).astype(np.float32)
+    difference = ((0.2 + rng.exponential(0.3, shape)) * rng.choice([-1.0, 1.0], shape)).astype(np.float32)
+    noisy = (clean + difference).astype(np.float32)
+    planes = (labels, difference, noisy, clean)
+    want_block, want_cn, want_cv = numpy_analysis_block(*planes, with_roughness=with_roughness)
+    block, cn, cv = split_result(noise_analysis_build(*(torch.from_numpy(p).to(gpu_device) for p in planes)).cpu().numpy(), w)
+    assert np.array_equal(cn, want_cn) and np.array_equal(cv, want_cv)
+    for k in INTEGER_FIELDS:
+        assert np.array_equal(block[k], want_block[k]), (k, block[k], want_block[k])
+    n = int(block["noise"])
+    for k in ("abs_sum", "sq_sum", "dev_sq_sum", "pos_sum", "neg_sum"):
+        assert abs(float(block[k]) - float(want_block[k])) <= sum_tolerance(n) * abs(float(want_block[k])), k
+    if with_roughness:
+        assert np.array_equal(block["rough_count"], want_block["rough_count"])
+        for k in ("rough_sum", "rough_mid"):
+            assert np.allclose(block[k], want_block[k], rtol=ROUGH_RTOL, atol=0), (k, block[k], want_block[k])
+
+
+def test_nonfinite_noise_difference_raises(gpu_device):
+    from bathymetric_gnn_amd.data import analyze_noise_patterns
+    planes, _, _ = load_analysis_case("two_clusters_even")
+    difference = planes[1].copy()
+    difference[2, 4] = np.nan
+    with pytest.raises(ValueError, match="not finite"):
+        analyze_noise_patterns((planes[0], difference, planes[2], planes[3]), device=gpu_device)
+
+
+def test_refusals(gpu_device):
+    from bathymetric_gnn_amd.data import analyze_noise_patterns
+    from bathymetric_gnn_amd.data.noise_analysis import noise_analysis_build
+    empty = np.zeros((0, 7), np.float32)
+    assert analyze_noise_patterns((empty.astype(np.int32), empty, empty, empty), file="e.tif", device=gpu_device) == {"file": "e.tif", "shape": [0, 7]}
+    a = torch.zeros((4, 4), dtype=torch.float32, device=gpu_device)
+    with pytest.raises(TypeError):
+        noise_analysis_build(a, a, a, a)                        # labels must be int32 here
+    with pytest.raises(ValueError):
+        noise_analysis_build(a.to(torch.int32), a, a, a[:2].contiguous())
