@@ -1,5 +1,5 @@
 """Mirror of the reference's ``data`` package for the hot path: graph construction, tiling, synthetic training
-noise, ground truth from a clean / noisy survey pair and the ``BathymetricGrid`` container (file-format I/O -- GDAL / h5py -- is outside the path; VR BAGs enter as their two HDF5 arrays)."""
+noise, ground truth from a clean / noisy survey pair, feature labels from charted objects and the ``BathymetricGrid`` container (file-format I/O -- GDAL / h5py -- is outside the path; VR BAGs enter as their two HDF5 arrays)."""
 from .graph_construction import GraphBuilder, GraphData, Data
 from .grid import BathymetricGrid
 from .tiling import Tile, TileSpec, TileManager, TileMerger
@@ -7,9 +7,13 @@ from .vr_bag import RefinementGrid, VRBagHandler, VRBagWriter, SRBagHandler, SRB
 from .synthetic_noise import NoiseAugmentor, NoiseBatch, NoiseLabel, SyntheticNoiseGenerator, training_targets
 from .ground_truth import Alignment, GroundTruth, align_survey_pair, compute_ground_truth, ground_truth_stats
 from .noise_analysis import analyze_noise_patterns, print_analysis
+from .feature_labels import (FEATURE_CLASSES, FeatureLabels, S57Feature, create_feature_labels, feature_pixel_table, feature_plan,
+                             rasterize_features)
 
 __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "TileSpec", "TileManager", "TileMerger",
            "RefinementGrid", "VRBagHandler", "VRBagWriter", "SRBagHandler", "SRBagWriter", "SidecarBuilder", "detect_bag_type",
            "SyntheticNoiseGenerator", "NoiseAugmentor", "NoiseLabel", "NoiseBatch", "training_targets",
            "Alignment", "GroundTruth", "align_survey_pair", "compute_ground_truth", "ground_truth_stats",
-           "analyze_noise_patterns", "print_analysis"]
+           "analyze_noise_patterns", "print_analysis",
+           "FEATURE_CLASSES", "FeatureLabels", "S57Feature", "create_feature_labels", "feature_pixel_table", "feature_plan",
+           "rasterize_features"]

@@ -120,6 +120,8 @@ class GroundTruth:
     clean_survey: str = "None"
     noisy_survey: str = "None"
     _host_block: Any = None
+    applied_features: Optional[int] = None          # set by with_features: the features that were applied ...
+    feature_block: Optional[torch.Tensor] = None    # ... and the statistics block of that call (int64 [3], runtime.FL_STATS_DTYPE)
 
     def block(self):
         """The statistics block on the host (``runtime.GT_STATS_DTYPE``).  The first call synchronises; later ones do not."""
@@ -154,6 +156,23 @@ class GroundTruth:
     def training_planes(self):
         """``(labels, difference, noisy_depth, uncertainty)``: the leading arguments of ``TileStore.from_ground_truth``."""
         return self.labels, self.difference, self.noisy_depth, self.uncertainty
+
+    def with_features(self, features, feature_radius: Optional[Dict[str, float]] = None) -> "GroundTruth":
+        """This ground truth with charted features painted over its seafloor (``feature_labels``, overlay mode, with this ground
+        truth's own ``transform``): a cell labelled 0 inside a feature's disc takes the feature's label (class 1); noise (2) and
+        no data (-1) stay what they are.  Only ``labels`` is new, the other planes are shared, not copied.  ``stats()`` of the
+        result is that of the pair as prepared; the feature counts come from ``feature_stats()``."""
+        from .feature_labels import feature_pixel_table, rasterize_features
+        table, applied = feature_pixel_table(features, self.transform, tuple(self.labels.shape), feature_radius)
+        labels, block = rasterize_features(table, base_labels=self.labels)
+        return dataclasses.replace(self, labels=labels, applied_features=applied, feature_block=block)
+
+    def feature_stats(self) -> Dict[str, int]:
+        """``{"applied_features", "feature_cells", "valid_cells", "painted_cells"}`` of ``with_features`` (synchronises)."""
+        if self.feature_block is None:
+            raise ValueError("no features were applied: this ground truth does not come from with_features")
+        from .feature_labels import feature_stats
+        return feature_stats(self.feature_block, self.applied_features)
 
     def analyze(self, **kw) -> Dict[str, Any]:
         """The reference's noise pattern analysis of this ground truth (``noise_analysis.analyze_noise_patterns``)."""

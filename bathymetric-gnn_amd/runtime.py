@@ -278,6 +278,22 @@ NA_DTYPE = [("valid", "<i8"), ("noise", "<i8"), ("seafloor", "<i8"), ("positive"
             ("max_cluster", "<i8"), ("isolated", "<i8"), ("size_bins", "<i8", (7,)), ("size_mid", "<i8", (2,)),
             ("rough_count", "<i8", (2,)), ("rough_sum", "<f8", (2,)), ("rough_mid", "<f8", (4,))]
 
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_features.h declares (feature labels from charted objects)
+_FEATURES_SIGNATURES = {
+    "bgnn_feature_labels_plan_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64]),
+    "bgnn_feature_labels_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t]),
+    "bgnn_feature_labels_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_size_t]),
+    "bgnn_feature_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64,
+                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+# BGNN_FL_*: the bins of the host plan, the limits, the statistics block of a feature-label call
+FL_BIN = 64
+FL_MAX_CELLS = 2 ** 31 - 1
+FL_MAX_FEATURES = 2 ** 31 - 2
+FL_STATS_BYTES = 24
+FL_STATS_DTYPE = [("valid", "<i8"), ("feature", "<i8"), ("painted", "<i8")]
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -288,7 +304,8 @@ class BgnnError(RuntimeError):
 
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
-    include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h and include/bgnn_analysis.h.  Needs no GPU."""
+    include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h and
+    include/bgnn_features.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -301,7 +318,7 @@ def load_library(path: Optional[str] = None):
         lib = C.CDLL(p)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
                 list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
-                list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()):
+                list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
