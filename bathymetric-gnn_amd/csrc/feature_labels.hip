@@ -16,6 +16,7 @@
 // Compiled with -ffp-contract=off like its neighbours (the validity test is two float32 comparisons; nothing here contracts).
 #include "bgnn_internal.h"
 #include "feature_plan.h"
+#include "plane_util.h"
 
 namespace bgnn {
 namespace {
@@ -26,8 +27,6 @@ constexpr int FL_CHUNK = 256;                         // list entries staged at 
 constexpr int FL_GRID_PER_CU = 16;                    // workgroups per CU at most: two rounds of the eight that fit
 constexpr int FL_ROWS = 4, FL_COLS = 4;               // cells of a thread: 4 along a row, in rows 16 apart
 static_assert(FL_BIN == 64 && FL_THREADS == (FL_BIN / FL_COLS) * (FL_BIN / FL_ROWS), "a thread owns 16 cells of a 64 x 64 bin");
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct FlArgs {
   const float *depth;            // depth mode (else nullptr)
@@ -40,8 +39,6 @@ struct FlArgs {
   int32_t rows, cols, bins_c, bins;
   float nodata;
 };
-
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 
 // VEC: cols is a multiple of 4 and the planes are 16-byte aligned: every thread's four cells are one aligned 16-byte access, all
 // inside the grid or all outside.

@@ -1,60 +1,54 @@
 // Ground truth from a survey pair and model evaluation (include/bgnn_eval.h): the two steps of the reference's workflow around
 // training and inference, on planes that stay in HBM.
 //
-// Ground truth: the median of (noisy - clean) over the valid cells is an exact radix selection over the order-preserving uint32
-// image of the float32 difference.
+// Ground truth: the median of (noisy - clean) over the valid cells is an exact radix selection (radix_select.h, the implementation
+// the noise analysis selects its order statistics with: here two ranks, int64 counts) over the order-preserving uint32 image of the
+// float32 difference, in digits of 11, 11 and 10 bits.
 //   gt_first_pass     reads both depth planes (8 B / cell), writes the raw difference into the `difference` plane (NaN = invalid,
-//                     4 B / cell) and counts the top 11 key bits
-//   gt_refine_pass    re-reads the raw difference (4 B / cell) and counts the next 11 / 10 bits of the keys under the current
-//                     prefix: once per rank, since the two middle ranks of an even count can part ways at any level
-//   gt_select         one workgroup: walks the level's histogram and narrows prefix and rank of both ranks; after the last level
-//                     the prefixes are the two keys, and the offset is formed as numpy's mean of two float32 does
+//                     4 B / cell) and counts the top digit
+//   gt_refine_pass    re-reads the raw difference (4 B / cell) and counts the next digit of the keys under the current prefixes:
+//                     one histogram while both middle ranks share a prefix, two once they have parted (at any level)
+//   gt_select         one workgroup: select_digit narrows prefix and rank of both ranks; the first level sets the ranks
+//                     (n - 1) / 2 and n / 2 from the total; after the last level the prefixes are the two keys, and the offset is
+//                     formed as numpy's mean of two float32 does
 //   gt_label_pass     difference = raw - offset, labels, masked uncertainty (4-8 B in, 8-12 B out per cell) and the per-workgroup
-//                     partials of the statistics; gt_finish adds them in workgroup order
-// All passes are HBM-bound streams.  Real differences cluster around the offset, so most lanes of a wave hit one or two bins of a
-// histogram: hist_add peels the wave's two most frequent candidates (the first remaining lane's bin, twice) into one LDS atomic
-// each before the rest add singly.  Histograms are integer LDS atomics merged with integer global atomics: counts do not depend
-// on scheduling.
+//                     partials of the statistics (block_reduce); gt_finish adds them in workgroup order
+// All passes are HBM-bound streams.
 //
 // Evaluation: eval_pass counts every integer of compute_metrics as wave ballots (28 per 64 cells, scalar adds), sums the three
 // float64 confidence terms per thread in a fixed order, and leaves one partial row per workgroup; eval_finish adds the rows in
 // workgroup order into the accumulator block.
 //
 // Compiled with -ffp-contract=off: the subtraction, the offset's add-then-halve and the float64 squares round as written.
+#include <type_traits>
+
 #include "bgnn_internal.h"
+#include "radix_select.h"
 #include "../../include/bgnn_eval.h"
 
 namespace bgnn {
 
-constexpr int EV_THREADS = 256;
+constexpr int EV_THREADS = BLOCK_THREADS;
 constexpr int EV_ITEMS = 4;                          // consecutive cells per thread and step: one 16-byte load per plane
 constexpr int EV_TILE = EV_THREADS * EV_ITEMS;
 constexpr int EV_MAX_GRID = 2048;                    // 256 CUs x 8 workgroups
 constexpr int EV_WAVES = EV_THREADS / 64;
 
 // the grid of every streaming pass: a function of `cells` alone
-static inline int stream_grid(int64_t cells) {
-  const int64_t tiles = (cells + EV_TILE - 1) / EV_TILE;
-  return (int)(tiles < 1 ? 1 : (tiles > EV_MAX_GRID ? EV_MAX_GRID : tiles));
-}
+static inline int stream_grid(int64_t cells) { return capped_grid((cells + EV_TILE - 1) / EV_TILE, EV_MAX_GRID); }
 
 // ---- ground truth ----------------------------------------------------------------------------------------------------
-constexpr int GT_L1_BITS = 11, GT_L2_BITS = 11, GT_L3_BITS = 10;
-constexpr int GT_L1_BINS = 1 << GT_L1_BITS, GT_L2_BINS = 1 << GT_L2_BITS, GT_L3_BINS = 1 << GT_L3_BITS;
-static_assert(GT_L1_BITS + GT_L2_BITS + GT_L3_BITS == 32, "the three levels cover the key");
-// workspace: int64 histograms [L1 | L2 rank lo | L2 rank hi | L3 rank lo | L3 rank hi], the selection state, the partials
-constexpr int GT_H1 = 0, GT_H2 = GT_H1 + GT_L1_BINS, GT_H3 = GT_H2 + 2 * GT_L2_BINS, GT_HIST_WORDS = GT_H3 + 2 * GT_L3_BINS;
-constexpr uint32_t GT_NO_PREFIX = 0xFFFFFFFFu;       // matches no key at levels 2 and 3 (their prefixes have 11 / 22 bits)
-
-struct GtSelect {            // 64 bytes
-  uint32_t prefix[2];        // the key bits fixed so far, for the lower and the upper middle rank
-  int64_t rank[2];           // the ranks among the keys under those prefixes
-  int64_t n;                 // valid cells
-  uint32_t same;             // both ranks under one prefix: only the first histogram of the level is filled
-  float offset;
-  int64_t pad[3];
-};
-static_assert(sizeof(GtSelect) == 64, "selection state");
+using GtDigits = Digits<11, 11, 10>;
+static_assert(GtDigits::covers<uint32_t>(), "the three levels cover the key");
+using GtState = SelectState<2, uint32_t>;            // the lower and the upper middle rank
+// workspace: int64 histograms (a pair may exceed 2^32 cells) [level 0 | level 1 x 2 groups | level 2 x 2 groups], the selection
+// state, the partials
+constexpr int gt_hist_word(int level) {
+  int w = 0;
+  for (int l = 0; l < level; ++l) w += (l == 0 ? 1 : 2) << GtDigits::width(l);
+  return w;
+}
+constexpr int GT_HIST_WORDS = gt_hist_word(GtDigits::N);
 
 struct GtPartial {           // one per workgroup of gt_label_pass
   double noise_abs_sum, seafloor_sum;
@@ -65,16 +59,7 @@ struct GtPartial {           // one per workgroup of gt_label_pass
 static_assert(sizeof(GtPartial) == 40, "partial row");
 
 constexpr size_t GT_STATE_OFFSET = (size_t)GT_HIST_WORDS * 8;
-constexpr size_t GT_PARTIAL_OFFSET = GT_STATE_OFFSET + sizeof(GtSelect);
-
-__device__ __forceinline__ uint32_t order_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+constexpr size_t GT_PARTIAL_OFFSET = GT_STATE_OFFSET + sizeof(GtState);
 
 template <bool VEC, typename T>
 __device__ __forceinline__ void load_items(const T *p, int64_t i, int64_t n, T (&v)[EV_ITEMS], T fill) {
@@ -104,39 +89,13 @@ __device__ __forceinline__ void store_items(T *p, int64_t i, int64_t n, const T 
   }
 }
 
-// One count per active lane into an LDS histogram.  Called by whole waves (the ballots need every lane).  Two rounds take the bin
-// of the first lane still waiting and add all its lanes at once; a clustered plane is done after them, a uniform one pays two
-// ballots and goes on lane by lane.
-__device__ __forceinline__ void hist_add(int32_t *hist, bool active, uint32_t bin) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long waiting = __ballot(active);
-#pragma unroll
-  for (int round = 0; round < 2; ++round) {
-    if (waiting == 0) break;                                    // (uniform)
-    const int leader = __ffsll(waiting) - 1;
-    const uint32_t lb = (uint32_t)__builtin_amdgcn_readlane((int)bin, leader);
-    const bool mine = active && bin == lb;
-    const unsigned long long m = __ballot(mine);
-    if (lane == leader) atomicAdd(&hist[lb], (int32_t)__popcll(m));
-    if (mine) active = false;
-    waiting &= ~m;
-  }
-  if (active) atomicAdd(&hist[bin], 1);
-}
-
-__device__ __forceinline__ void hist_flush(const int32_t *lds, int bins, int64_t *global) {
-  for (int b = threadIdx.x; b < bins; b += EV_THREADS) {
-    const int32_t c = lds[b];
-    if (c != 0) atomicAdd(reinterpret_cast<unsigned long long *>(global + b), (unsigned long long)c);
-  }
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(EV_THREADS) void gt_first_pass(const float *__restrict__ clean, const float *__restrict__ noisy,
                                                             int64_t cells, float nodata, float *__restrict__ raw_out,
                                                             int64_t *__restrict__ hist) {
-  __shared__ int32_t lds[GT_L1_BINS];
-  for (int b = threadIdx.x; b < GT_L1_BINS; b += EV_THREADS) lds[b] = 0;
+  constexpr int BINS = 1 << GtDigits::width(0);
+  __shared__ int32_t lds[BINS];
+  for (int b = threadIdx.x; b < BINS; b += EV_THREADS) lds[b] = 0;
   __syncthreads();
   const float nan = __uint_as_float(0x7FC00000u);
   for (int64_t base = (int64_t)blockIdx.x * EV_TILE; base < cells; base += (int64_t)gridDim.x * EV_TILE) {
@@ -152,116 +111,57 @@ __global__ __launch_bounds__(EV_THREADS) void gt_first_pass(const float *__restr
     }
     store_items<VEC>(raw_out, i, cells, raw);
 #pragma unroll
-    for (int k = 0; k < EV_ITEMS; ++k) hist_add(lds, ok[k], order_key(raw[k]) >> (32 - GT_L1_BITS));
+    for (int k = 0; k < EV_ITEMS; ++k) hist_add(lds, ok[k], order_key(raw[k]) >> GtDigits::shift(0));
   }
   __syncthreads();
-  hist_flush(lds, GT_L1_BINS, hist);
+  hist_flush(lds, BINS, hist);
 }
 
-// SHIFT: the bits below this level's digit; BITS: the digit's width.  The bits above the digit are the prefix.
-template <bool VEC, int SHIFT, int BITS>
+template <bool VEC, int LEVEL>
 __global__ __launch_bounds__(EV_THREADS) void gt_refine_pass(const float *__restrict__ raw_in, int64_t cells,
-                                                             const GtSelect *__restrict__ sel, int64_t *__restrict__ hist) {
-  constexpr int BINS = 1 << BITS;
-  __shared__ int32_t lds[2 * BINS];
-  for (int b = threadIdx.x; b < 2 * BINS; b += EV_THREADS) lds[b] = 0;
-  const uint32_t p0 = sel->prefix[0], p1 = sel->prefix[1];
-  const bool two = sel->same == 0;                              // (uniform)
-  __syncthreads();
+                                                             const GtState *__restrict__ sel, int64_t *__restrict__ hist) {
+  using Counter = DigitCounter<2, uint32_t, GtDigits::shift(LEVEL), GtDigits::width(LEVEL)>;
+  __shared__ int32_t lds[2 * Counter::BINS];
+  Counter counter;
+  counter.init(sel, lds);
   const float nan = __uint_as_float(0x7FC00000u);
   for (int64_t base = (int64_t)blockIdx.x * EV_TILE; base < cells; base += (int64_t)gridDim.x * EV_TILE) {
     const int64_t i = base + (int64_t)threadIdx.x * EV_ITEMS;
     float raw[EV_ITEMS];
     load_items<VEC>(raw_in, i, cells, raw, nan);
 #pragma unroll
-    for (int k = 0; k < EV_ITEMS; ++k) {
-      const bool ok = raw[k] == raw[k];
-      const uint32_t key = order_key(raw[k]);
-      const uint32_t top = key >> (SHIFT + BITS), bin = (key >> SHIFT) & (BINS - 1);
-      hist_add(lds, ok && top == p0, bin);
-      if (two) hist_add(lds + BINS, ok && top == p1, bin);
-    }
+    for (int k = 0; k < EV_ITEMS; ++k) counter.add(raw[k] == raw[k], order_key(raw[k]));
   }
-  __syncthreads();
-  hist_flush(lds, two ? 2 * BINS : BINS, hist);
+  counter.flush(hist);
 }
 
-// LEVEL 1: ranks from the total.  LEVEL 3: the prefixes become the keys and the offset is formed.
-template <int LEVEL, int BITS>
-__global__ __launch_bounds__(EV_THREADS) void gt_select(const int64_t *__restrict__ hist, GtSelect *sel, char *stats) {
-  constexpr int BINS = 1 << BITS, PER = BINS / EV_THREADS;
-  __shared__ int64_t part[EV_THREADS + 1];
-  __shared__ uint32_t out_prefix[2];
-  __shared__ int64_t out_rank[2];
-  const int t = threadIdx.x;
-  GtSelect s{};
-  if (LEVEL > 1) s = *sel;                 // (every thread reads the state here; thread 0 writes it after the last barrier)
-  const bool same = LEVEL == 1 || s.same != 0;
-  if (t == 0) {                            // what stays when there is no valid cell
-    out_prefix[0] = out_prefix[1] = GT_NO_PREFIX;
-    out_rank[0] = out_rank[1] = 0;
-  }
-  for (int which = 0; which < 2; ++which) {
-    const int64_t *h = hist + ((which == 1 && !same) ? BINS : 0);
-    int64_t local[PER], sum = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) { local[k] = h[t * PER + k]; sum += local[k]; }
-    __syncthreads();                       // (the previous round's readers of part[] are done)
-    part[t] = sum;
-    __syncthreads();
-    if (t == 0) {
-      int64_t run = 0;
-      for (int k = 0; k < EV_THREADS; ++k) { const int64_t v = part[k]; part[k] = run; run += v; }
-      part[EV_THREADS] = run;
+// One workgroup per level.  Level 0: the ranks from the total.  The last level: the prefixes are the keys and the offset is formed.
+template <int LEVEL>
+__global__ __launch_bounds__(EV_THREADS) void gt_select(const int64_t *__restrict__ hist, GtState *sel, char *stats) {
+  __shared__ SelectScratch<2, uint32_t> sh;
+  select_digit<LEVEL == 0, GtDigits::width(LEVEL)>(hist, sel, sh, 2, [](const int64_t *part, int64_t *rank) {
+    const int64_t n = part[EV_THREADS];
+    if (n > 0) { rank[0] = (n - 1) / 2; rank[1] = n / 2; }
+  });
+  if (LEVEL == GtDigits::N - 1 && threadIdx.x == 0) {
+    const GtState &o = sh.out;
+    const int64_t n = o.rank0[0] < 0 ? 0 : o.rank0[0] + o.rank0[1] + 1;      // (n - 1) / 2 + n / 2 = n - 1
+    float offset = __uint_as_float(0x7FC00000u);
+    if (n > 0) {
+      const float a = key_value(o.prefix[0]), b = key_value(o.prefix[1]);
+      offset = (n & 1) ? a : (a + b) / 2.0f;                   // numpy: add.reduce in float32, then the division by the count
     }
-    __syncthreads();
-    int64_t rank = s.rank[which];
-    uint32_t prefix = s.prefix[which];
-    if (LEVEL == 1) {
-      s.n = part[EV_THREADS];
-      rank = which == 0 ? (s.n - 1) / 2 : s.n / 2;
-      prefix = 0;
-    }
-    int64_t below = part[t];
-    if (s.n > 0 && rank >= below && rank < below + sum) {       // exactly one thread: rank < the count under the prefix
-#pragma unroll
-      for (int k = 0; k < PER; ++k) {
-        if (rank >= below && rank < below + local[k]) {
-          out_prefix[which] = (prefix << BITS) | (uint32_t)(t * PER + k);
-          out_rank[which] = rank - below;
-        }
-        below += local[k];
-      }
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    GtSelect o{};
-    o.prefix[0] = out_prefix[0]; o.prefix[1] = out_prefix[1];
-    o.rank[0] = out_rank[0]; o.rank[1] = out_rank[1];
-    o.n = s.n;
-    o.same = out_prefix[0] == out_prefix[1] ? 1u : 0u;
-    o.offset = 0.0f;
-    if (LEVEL == 3) {
-      float offset = __uint_as_float(0x7FC00000u);
-      if (s.n > 0) {
-        const float a = key_value(out_prefix[0]), b = key_value(out_prefix[1]);
-        offset = (s.n & 1) ? a : (a + b) / 2.0f;               // numpy: add.reduce in float32, then the division by the count
-      }
-      o.offset = offset;
-      *reinterpret_cast<float *>(stats + BGNN_GT_STATS_OFFSET) = offset;
-      *reinterpret_cast<int64_t *>(stats + BGNN_GT_STATS_VALID) = s.n;
-    }
-    *sel = o;
+    *reinterpret_cast<float *>(stats + BGNN_GT_STATS_OFFSET) = offset;
+    *reinterpret_cast<int64_t *>(stats + BGNN_GT_STATS_VALID) = n;
   }
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(EV_THREADS) void gt_label_pass(float *__restrict__ difference, const float *__restrict__ unc_in,
                                                             float *__restrict__ unc_out, int32_t *__restrict__ labels, int64_t cells,
-                                                            float threshold, const GtSelect *__restrict__ sel,
+                                                            float threshold, const char *__restrict__ stats,
                                                             GtPartial *__restrict__ partials) {
-  const float offset = sel->offset;
+  const float offset = *reinterpret_cast<const float *>(stats + BGNN_GT_STATS_OFFSET);      // (gt_select of the last level)
   const float nan = __uint_as_float(0x7FC00000u);
   double noise_sum = 0.0, sea_sum = 0.0;
   float noise_max = 0.0f;
@@ -297,26 +197,15 @@ __global__ __launch_bounds__(EV_THREADS) void gt_label_pass(float *__restrict__ 
     }
   }
   // the workgroup's partial: a fixed tree over the threads
-  __shared__ double r_noise[EV_THREADS], r_sea[EV_THREADS];
-  __shared__ float r_max[EV_THREADS];
-  __shared__ int64_t r_nn[EV_THREADS], r_ns[EV_THREADS];
-  const int t = threadIdx.x;
-  r_noise[t] = noise_sum; r_sea[t] = sea_sum; r_max[t] = noise_max; r_nn[t] = (int64_t)n_noise; r_ns[t] = (int64_t)n_sea;
-  __syncthreads();
-  for (int w = EV_THREADS / 2; w > 0; w >>= 1) {
-    if (t < w) {
-      r_noise[t] += r_noise[t + w]; r_sea[t] += r_sea[t + w];
-      r_max[t] = r_max[t + w] > r_max[t] ? r_max[t + w] : r_max[t];
-      r_nn[t] += r_nn[t + w]; r_ns[t] += r_ns[t + w];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    GtPartial p{};
-    p.noise_abs_sum = r_noise[0]; p.seafloor_sum = r_sea[0]; p.noise = r_nn[0]; p.seafloor = r_ns[0];
-    p.noise_abs_max = r_max[0];
-    partials[blockIdx.x] = p;
-  }
+  __shared__ int64_t red[EV_THREADS];
+  const auto later = [](float a, float b) { return b > a ? b : a; };
+  GtPartial p{};
+  p.noise_abs_sum = block_reduce(noise_sum, red, SumOp());
+  p.seafloor_sum = block_reduce(sea_sum, red, SumOp());
+  p.noise_abs_max = block_reduce(noise_max, red, later);
+  p.noise = block_reduce((int64_t)n_noise, red, SumOp());
+  p.seafloor = block_reduce((int64_t)n_sea, red, SumOp());
+  if (threadIdx.x == 0) partials[blockIdx.x] = p;
 }
 
 // The sum of src[0], src[stride], ... (n terms) in ascending order, formed by one wave: lane l adds the run [32 l, 32 l + 32),
@@ -339,31 +228,28 @@ __device__ __forceinline__ double ordered_sum(const double *src, int stride, int
 
 __global__ __launch_bounds__(EV_THREADS) void gt_finish(const GtPartial *__restrict__ partials, int n, char *stats) {
   __shared__ double lane_sums[2][64];
-  __shared__ int64_t r_nn[EV_THREADS], r_ns[EV_THREADS];
-  __shared__ float r_max[EV_THREADS];
+  __shared__ int64_t red[EV_THREADS];
   static_assert(sizeof(GtPartial) % 8 == 0 && offsetof(GtPartial, seafloor_sum) == 8, "the float64 sums lead the partial row");
   const int t = threadIdx.x;
   int64_t nn = 0, ns = 0;
-  float mx = 0.0f;
+  float mx = 0.0f;                                             // (magnitudes: no NaN, so the maximum is the same in any order)
   for (int k = t; k < n; k += EV_THREADS) {
     nn += partials[k].noise; ns += partials[k].seafloor;
     mx = partials[k].noise_abs_max > mx ? partials[k].noise_abs_max : mx;
   }
-  r_nn[t] = nn; r_ns[t] = ns; r_max[t] = mx;
-  {                                                            // the two float64 sums, a wave each (the barrier inside covers r_*)
-    const int j = t >> 6;
-    const double *src = j < 2 ? reinterpret_cast<const double *>(partials) + j : nullptr;
-    const double total = ordered_sum(src, (int)(sizeof(GtPartial) / 8), n, lane_sums[j & 1]);
-    if (j < 2 && (t & 63) == 0)
-      *reinterpret_cast<double *>(stats + (j == 0 ? BGNN_GT_STATS_NOISE_ABS_SUM : BGNN_GT_STATS_SEAFLOOR_SUM)) = total;
-  }
+  nn = block_reduce(nn, red, SumOp());
+  ns = block_reduce(ns, red, SumOp());
+  mx = block_reduce(mx, red, [](float a, float b) { return b > a ? b : a; });
   if (t == 128) {
-    nn = 0; ns = 0; mx = 0.0f;
-    for (int k = 0; k < EV_THREADS; ++k) { nn += r_nn[k]; ns += r_ns[k]; mx = r_max[k] > mx ? r_max[k] : mx; }
     *reinterpret_cast<int64_t *>(stats + BGNN_GT_STATS_NOISE) = nn;
     *reinterpret_cast<int64_t *>(stats + BGNN_GT_STATS_SEAFLOOR) = ns;
     *reinterpret_cast<float *>(stats + BGNN_GT_STATS_NOISE_ABS_MAX) = mx;
   }
+  const int j = t >> 6;                                        // the two float64 sums, a wave each
+  const double *src = j < 2 ? reinterpret_cast<const double *>(partials) + j : nullptr;
+  const double total = ordered_sum(src, (int)(sizeof(GtPartial) / 8), n, lane_sums[j & 1]);
+  if (j < 2 && (t & 63) == 0)
+    *reinterpret_cast<double *>(stats + (j == 0 ? BGNN_GT_STATS_NOISE_ABS_SUM : BGNN_GT_STATS_SEAFLOOR_SUM)) = total;
 }
 
 // ---- evaluation ------------------------------------------------------------------------------------------------------
@@ -485,7 +371,7 @@ using namespace bgnn;
 extern "C" size_t bgnn_ground_truth_workspace_bytes(int64_t cells) {
   if (cells < 0) return 0;
   const size_t bytes = GT_PARTIAL_OFFSET + (size_t)stream_grid(cells) * sizeof(GtPartial);
-  return (bytes + 255) & ~(size_t)255;
+  return align256(bytes);
 }
 
 extern "C" int bgnn_ground_truth_build(bgnn_ctx *ctx, const float *clean, const float *noisy, const float *noisy_unc, int64_t cells,
@@ -504,7 +390,7 @@ extern "C" int bgnn_ground_truth_build(bgnn_ctx *ctx, const float *clean, const 
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
   char *w = static_cast<char *>(ws);
   int64_t *hist = reinterpret_cast<int64_t *>(w);
-  GtSelect *sel = reinterpret_cast<GtSelect *>(w + GT_STATE_OFFSET);
+  GtState *sel = reinterpret_cast<GtState *>(w + GT_STATE_OFFSET);
   GtPartial *partials = reinterpret_cast<GtPartial *>(w + GT_PARTIAL_OFFSET);
   char *st = static_cast<char *>(stats);
   const int grid = stream_grid(cells);
@@ -515,23 +401,18 @@ extern "C" int bgnn_ground_truth_build(bgnn_ctx *ctx, const float *clean, const 
                    (!unc_out || (aligned16(unc_in) && aligned16(unc_out)));
   hipStream_t s = ctx->stream;
   BGNN_HIP_CHECK(hipMemsetAsync(w, 0, GT_PARTIAL_OFFSET, s));
-  if (vec) {
-    hipLaunchKernelGGL(gt_first_pass<true>, g, b, 0, s, clean, noisy, cells, nd, difference, hist + GT_H1);
-    hipLaunchKernelGGL((gt_select<1, GT_L1_BITS>), one, b, 0, s, hist + GT_H1, sel, st);
-    hipLaunchKernelGGL((gt_refine_pass<true, GT_L3_BITS, GT_L2_BITS>), g, b, 0, s, difference, cells, sel, hist + GT_H2);
-    hipLaunchKernelGGL((gt_select<2, GT_L2_BITS>), one, b, 0, s, hist + GT_H2, sel, st);
-    hipLaunchKernelGGL((gt_refine_pass<true, 0, GT_L3_BITS>), g, b, 0, s, difference, cells, sel, hist + GT_H3);
-    hipLaunchKernelGGL((gt_select<3, GT_L3_BITS>), one, b, 0, s, hist + GT_H3, sel, st);
-    hipLaunchKernelGGL(gt_label_pass<true>, g, b, 0, s, difference, unc_in, unc_out, labels, cells, thr, sel, partials);
-  } else {
-    hipLaunchKernelGGL(gt_first_pass<false>, g, b, 0, s, clean, noisy, cells, nd, difference, hist + GT_H1);
-    hipLaunchKernelGGL((gt_select<1, GT_L1_BITS>), one, b, 0, s, hist + GT_H1, sel, st);
-    hipLaunchKernelGGL((gt_refine_pass<false, GT_L3_BITS, GT_L2_BITS>), g, b, 0, s, difference, cells, sel, hist + GT_H2);
-    hipLaunchKernelGGL((gt_select<2, GT_L2_BITS>), one, b, 0, s, hist + GT_H2, sel, st);
-    hipLaunchKernelGGL((gt_refine_pass<false, 0, GT_L3_BITS>), g, b, 0, s, difference, cells, sel, hist + GT_H3);
-    hipLaunchKernelGGL((gt_select<3, GT_L3_BITS>), one, b, 0, s, hist + GT_H3, sel, st);
-    hipLaunchKernelGGL(gt_label_pass<false>, g, b, 0, s, difference, unc_in, unc_out, labels, cells, thr, sel, partials);
-  }
+  const auto passes = [&](auto vec_flag) {                     // the seven launches, for aligned (VEC) or unaligned planes
+    constexpr bool VEC = decltype(vec_flag)::value;
+    hipLaunchKernelGGL(gt_first_pass<VEC>, g, b, 0, s, clean, noisy, cells, nd, difference, hist + gt_hist_word(0));
+    hipLaunchKernelGGL(gt_select<0>, one, b, 0, s, hist + gt_hist_word(0), sel, st);
+    hipLaunchKernelGGL((gt_refine_pass<VEC, 1>), g, b, 0, s, difference, cells, sel, hist + gt_hist_word(1));
+    hipLaunchKernelGGL(gt_select<1>, one, b, 0, s, hist + gt_hist_word(1), sel, st);
+    hipLaunchKernelGGL((gt_refine_pass<VEC, 2>), g, b, 0, s, difference, cells, sel, hist + gt_hist_word(2));
+    hipLaunchKernelGGL(gt_select<2>, one, b, 0, s, hist + gt_hist_word(2), sel, st);
+    hipLaunchKernelGGL(gt_label_pass<VEC>, g, b, 0, s, difference, unc_in, unc_out, labels, cells, thr, st, partials);
+  };
+  if (vec) passes(std::true_type{});
+  else passes(std::false_type{});
   hipLaunchKernelGGL(gt_finish, one, b, 0, s, partials, grid, st);
   BGNN_HIP_CHECK(hipGetLastError());
   return BGNN_OK;

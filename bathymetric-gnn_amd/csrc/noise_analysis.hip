@@ -10,12 +10,12 @@
 //                    the class sums, and the top 11 bits of that key.  na_refine<ROUGH> x 5 narrows both classes' two middle ranks
 //                    in one 64-bit key space: every noise key lies above every seafloor key
 //   ccl_local .. ccl_stats   connected components of the noise mask, below; na_refine<SIZE> x 2 selects the median cluster size
-//   na_select        one workgroup after every histogram pass: walks the histograms and narrows prefix and rank of every rank
+//   na_select        one workgroup after every histogram pass: narrows prefix and rank of every rank (radix_select.h, select_digit)
 //   na_finish        one workgroup: adds the partial rows in workgroup order into the result block
 //
-// Multi-rank radix selection.  Ranks whose keys share the prefix fixed so far share one histogram ("group"); a level's pass
-// compares each key with the at most six group prefixes.  The histograms are integer LDS atomics merged with integer global
-// atomics, hist_add peels a wave's two most frequent bins first (ground_truth.hip explains why).
+// Multi-rank radix selection: radix_select.h, the implementation the ground truth selects its median with; here up to six ranks
+// and uint32 counts (cells are below 2^31).  This file keeps the streaming loops, the rule that sets each selection's ranks from the
+// first level's totals, and what is written to the block after the last level.
 //
 // Connected components (4-connectivity, scipy.ndimage.label's default structure): label equivalence by union-find over int32
 // cell indices, parent[i] = -1 off the noise mask.
@@ -41,34 +41,39 @@
 //
 // Compiled with -ffp-contract=off: the float32 rank arithmetic of numpy's percentile and the float64 squares round as written.
 #include "bgnn_internal.h"
+#include "radix_select.h"
 #include "../../include/bgnn_analysis.h"
 
 namespace bgnn {
 namespace {
 
-constexpr int NA_THREADS = 256;
+constexpr int NA_THREADS = BLOCK_THREADS;
 constexpr int NA_ITEMS = 4;                           // cells per thread and step of a streaming pass (each load coalesced)
 constexpr int NA_CHUNK = NA_THREADS * NA_ITEMS;
 constexpr int NA_MAX_GRID = 2048;                     // 256 CUs x 8 workgroups
-constexpr int NA_BINS = 2048;                         // 11-bit digits (the last digit of a key may be narrower)
 constexpr int NA_RANKS = 6;
-constexpr int NA_LEVELS = 6;                          // of a 64-bit key: 11 x 5 + 9; a 32-bit key has 11 + 11 + 10
 constexpr int TILE_R = 16, TILE_C = 64;               // tile of ccl_local / na_rough: 1024 cells
 constexpr int HALO_R = TILE_R + 4, HALO_C = TILE_C + 4;
 constexpr int ROW_WORDS = 40;                         // a partial row: 8-byte words
 
 enum { SEL_MAG = 0, SEL_ROUGH = 1, SEL_SIZE = 2, SEL_COUNT = 3 };
 
-struct SelState {
-  uint64_t prefix[NA_RANKS];       // the key bits fixed so far, per rank (NO_PREFIX: the rank does not exist)
-  uint64_t gprefix[NA_RANKS];      // the same per group: the distinct prefixes
-  int64_t rank[NA_RANKS];          // the rank among the keys under the prefix
-  int64_t rank0[NA_RANKS];         // the rank among all keys
-  int32_t group[NA_RANKS];         // the histogram the rank reads at the next level (-1: none)
-  int32_t ngroups, nranks;
+// What each selection selects: its key, the key's digits (most significant first), its ranks
+template <int SEL> struct Selection {                 // SEL_MAG: the bits of |difference|; SEL_SIZE: a cluster's cell count
+  using Key = uint32_t;
+  using D = Digits<11, 11, 10>;
+  static constexpr int nranks = SEL == SEL_MAG ? 6 : 2;
 };
-static_assert(sizeof(SelState) <= 256, "selection state");
-constexpr uint64_t NO_PREFIX = ~0ull;                 // matches no key: a prefix below the last level has fewer than 64 bits
+template <> struct Selection<SEL_ROUGH> {             // the roughness plane's float64 words, the class in the sign bit
+  using Key = uint64_t;
+  using D = Digits<11, 11, 11, 11, 11, 9>;
+  static constexpr int nranks = 4;
+};
+template <int SEL> using SelState = SelectState<NA_RANKS, typename Selection<SEL>::Key>;
+constexpr int NA_BINS = 1 << 11;                      // of every selection's top digit, and the widest
+constexpr int NA_LEVELS = Selection<SEL_ROUGH>::D::N;
+static_assert(Selection<SEL_MAG>::D::covers<uint32_t>() && Selection<SEL_ROUGH>::D::covers<uint64_t>(), "the digits cover the key");
+static_assert(sizeof(SelState<SEL_ROUGH>) <= 256 && Selection<SEL_MAG>::D::N <= NA_LEVELS, "workspace slots");
 
 // workspace: [histograms | selection states] (cleared by one memset), the partial rows, then the three planes
 constexpr size_t WS_LEVEL_WORDS = (size_t)NA_RANKS * NA_BINS;
@@ -78,60 +83,9 @@ constexpr size_t WS_CLEAR_BYTES = WS_STATE + (size_t)SEL_COUNT * 256;
 constexpr size_t WS_ROWS = WS_CLEAR_BYTES;
 constexpr size_t WS_PLANES = WS_ROWS + (size_t)NA_MAX_GRID * ROW_WORDS * 8;
 static_assert(WS_PLANES % 256 == 0, "planes are 256-byte aligned");
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-inline int capped_grid(int64_t work_items) {
-  return (int)(work_items < 1 ? 1 : (work_items > NA_MAX_GRID ? NA_MAX_GRID : work_items));
-}
-
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-
-// One count per active lane into an LDS histogram; called by whole waves (see ground_truth.hip: hist_add).
-__device__ __forceinline__ void hist_add(int32_t *hist, bool active, uint32_t bin) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long waiting = __ballot(active);
-#pragma unroll
-  for (int round = 0; round < 2; ++round) {
-    if (waiting == 0) break;                                    // (uniform)
-    const int leader = __ffsll(waiting) - 1;
-    const uint32_t lb = (uint32_t)__builtin_amdgcn_readlane((int)bin, leader);
-    const bool mine = active && bin == lb;
-    const unsigned long long m = __ballot(mine);
-    if (lane == leader) atomicAdd(&hist[lb], (int32_t)__popcll(m));
-    if (mine) active = false;
-    waiting &= ~m;
-  }
-  if (active) atomicAdd(&hist[bin], 1);
-}
-
-__device__ __forceinline__ void hist_flush(const int32_t *lds, int bins, uint32_t *global) {
-  for (int b = threadIdx.x; b < bins; b += NA_THREADS) {
-    const int32_t c = lds[b];
-    if (c != 0) atomicAdd(global + b, (uint32_t)c);
-  }
-}
-
-// A fixed tree over the workgroup's threads; every thread calls it, every thread gets the result.
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, void *scratch, Op op) {
-  static_assert(sizeof(T) <= 8, "scratch holds 8 bytes per thread");
-  T *s = static_cast<T *>(scratch);
-  const int t = threadIdx.x;
-  __syncthreads();                                              // (the previous call's readers are done)
-  s[t] = v;
-  __syncthreads();
-  for (int w = NA_THREADS / 2; w > 0; w >>= 1) {
-    if (t < w) s[t] = op(s[t], s[t + w]);
-    __syncthreads();
-  }
-  return s[0];
-}
-__device__ __forceinline__ int64_t block_sum_i(uint32_t v, void *s) {
-  return block_reduce<int64_t>((int64_t)v, s, [](int64_t a, int64_t b) { return a + b; });
-}
-__device__ __forceinline__ double block_sum_d(double v, void *s) {
-  return block_reduce<double>(v, s, [](double a, double b) { return a + b; });
-}
+__device__ __forceinline__ int64_t block_sum_i(uint32_t v, void *s) { return block_reduce((int64_t)v, s, SumOp()); }
+__device__ __forceinline__ double block_sum_d(double v, void *s) { return block_reduce(v, s, SumOp()); }
 __device__ __forceinline__ void put_i(int64_t *row, int k, int64_t v) { if (threadIdx.x == 0) row[k] = v; }
 __device__ __forceinline__ void put_d(int64_t *row, int k, double v) { if (threadIdx.x == 0) row[k] = __double_as_longlong(v); }
 
@@ -180,7 +134,7 @@ __global__ __launch_bounds__(NA_THREADS) void na_stream(const int32_t *__restric
         if (d < 0.0f) cd[3] += (double)d;
         mx = mag > mx ? mag : mx;
       }
-      hist_add(lds, nf, __float_as_uint(mag) >> 21);
+      hist_add(lds, nf, __float_as_uint(mag) >> Selection<SEL_MAG>::D::shift(0));
     }
   }
   __syncthreads();
@@ -190,7 +144,7 @@ __global__ __launch_bounds__(NA_THREADS) void na_stream(const int32_t *__restric
   for (int k = 0; k < ST_INTS; ++k) put_i(row, k, block_sum_i(ci[k], red));
 #pragma unroll
   for (int k = 0; k < ST_SUMS; ++k) put_d(row, ST_INTS + k, block_sum_d(cd[k], red));
-  const float m = block_reduce<float>(mx, red, [](float a, float b) { return a > b ? a : b; });
+  const float m = block_reduce(mx, red, [](float a, float b) { return a > b ? a : b; });
   put_i(row, ST_INTS + ST_SUMS, (int64_t)__float_as_uint(m));
 }
 
@@ -233,7 +187,7 @@ struct Source {
 };
 
 template <int SEL>
-__device__ __forceinline__ bool source_key(const Source &s, int64_t i, uint64_t &key) {
+__device__ __forceinline__ bool source_key(const Source &s, int64_t i, typename Selection<SEL>::Key &key) {
   if (SEL == SEL_MAG) {
     const float d = s.diff[i];
     key = __float_as_uint(fabsf(d));
@@ -247,21 +201,20 @@ __device__ __forceinline__ bool source_key(const Source &s, int64_t i, uint64_t 
   }
 }
 
-// SHIFT: the bits below this level's digit; BITS: the digit's width; the bits above the digit are the prefix.
-// DEV (SEL_MAG): also the partial of sum ((double)|d| - mean)^2 with mean = abs_sum / n from the block (word 0 of the row).
-template <int SEL, int SHIFT, int BITS, bool DEV>
-__global__ __launch_bounds__(NA_THREADS) void na_refine(Source src, int64_t cells, const SelState *__restrict__ sel,
+// The histogram pass of level LEVEL >= 1 of selection SEL.  Level 1 of SEL_MAG also leaves the partial of
+// sum ((double)|d| - mean)^2 with mean = abs_sum / n from the block (DEV; word 0 of the row).
+template <int SEL, int LEVEL>
+__global__ __launch_bounds__(NA_THREADS) void na_refine(Source src, int64_t cells, const SelState<SEL> *__restrict__ sel,
                                                         uint32_t *__restrict__ hist, const char *__restrict__ block,
                                                         int64_t *__restrict__ rows) {
-  constexpr int BINS = 1 << BITS;
-  __shared__ int32_t lds[NA_RANKS * NA_BINS];
+  using Key = typename Selection<SEL>::Key;
+  using D = typename Selection<SEL>::D;
+  using Counter = DigitCounter<NA_RANKS, Key, D::shift(LEVEL), D::width(LEVEL)>;
+  constexpr bool DEV = SEL == SEL_MAG && LEVEL == 1;
+  __shared__ int32_t lds[NA_RANKS * Counter::BINS];
   __shared__ int64_t red[NA_THREADS];
-  const int ng = sel->ngroups;                                  // (uniform; 0 without a key)
-  uint64_t gp[NA_RANKS];
-#pragma unroll
-  for (int g = 0; g < NA_RANKS; ++g) gp[g] = sel->gprefix[g];
-  for (int b = threadIdx.x; b < ng * NA_BINS; b += NA_THREADS) lds[b] = 0;
-  __syncthreads();
+  Counter counter;
+  counter.init(sel, lds);
   double mean = 0.0, dev = 0.0;
   if (DEV) {
     const int64_t n = *reinterpret_cast<const int64_t *>(block + BGNN_NA_NOISE) - *reinterpret_cast<const int64_t *>(block + BGNN_NA_NONFINITE);
@@ -271,21 +224,16 @@ __global__ __launch_bounds__(NA_THREADS) void na_refine(Source src, int64_t cell
 #pragma unroll
     for (int k = 0; k < NA_ITEMS; ++k) {
       const int64_t i = base + k * NA_THREADS + threadIdx.x;
-      uint64_t key = 0;
+      Key key = 0;
       const bool ok = i < cells && source_key<SEL>(src, i, key);
       if (DEV && ok) {
         const double e = (double)__uint_as_float((uint32_t)key) - mean;
         dev += e * e;
       }
-      const uint64_t top = key >> (SHIFT + BITS);
-      const uint32_t bin = (uint32_t)(key >> SHIFT) & (BINS - 1);
-#pragma unroll
-      for (int g = 0; g < NA_RANKS; ++g)
-        if (g < ng) hist_add(lds + g * NA_BINS, ok && top == gp[g], bin);      // (uniform condition)
+      counter.add(ok, key);
     }
   }
-  __syncthreads();
-  for (int g = 0; g < ng; ++g) hist_flush(lds + g * NA_BINS, BINS, hist + (size_t)g * NA_BINS);
+  counter.flush(hist);
   if (DEV) put_d(rows + (int64_t)blockIdx.x * ROW_WORDS, 0, block_sum_d(dev, red));
 }
 
@@ -301,105 +249,41 @@ __device__ __forceinline__ void percentile_ranks(int64_t n, float p, int64_t &lo
   if (v < 0.0f) lo = hi = 0;
 }
 
-// One workgroup.  FIRST: the single histogram of the top digit; the ranks come from its totals.  LAST: the prefixes are the keys.
-template <int SEL, int BITS, bool FIRST, bool LAST>
-__global__ __launch_bounds__(NA_THREADS) void na_select(const uint32_t *__restrict__ hist, SelState *sel, char *block) {
-  constexpr int BINS = 1 << BITS, PER = BINS / NA_THREADS;
-  static_assert(PER >= 1, "a digit has at least 8 bits");
-  __shared__ int64_t part[NA_THREADS + 1];
-  __shared__ SelState in, out;
-  const int t = threadIdx.x;
-  if (t == 0) {
-    if (FIRST) {
-      for (int r = 0; r < NA_RANKS; ++r) { in.prefix[r] = 0; in.gprefix[r] = 0; in.rank[r] = -1; in.rank0[r] = -1; in.group[r] = 0; }
-      in.ngroups = 1;
-      in.nranks = SEL == SEL_MAG ? 6 : (SEL == SEL_ROUGH ? 4 : 2);
-    } else {
-      in = *sel;
-    }
-    for (int r = 0; r < NA_RANKS; ++r) { out.prefix[r] = NO_PREFIX; out.gprefix[r] = NO_PREFIX; out.rank[r] = -1; out.group[r] = -1; }
-  }
-  __syncthreads();
-  const int ng = in.ngroups;
-  for (int g = 0; g < ng; ++g) {
-    const uint32_t *h = hist + (size_t)g * NA_BINS;
-    int64_t local[PER], sum = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) { local[k] = (int64_t)h[t * PER + k]; sum += local[k]; }
-    __syncthreads();                       // (the previous round's readers of part[] are done)
-    part[t] = sum;
-    __syncthreads();
-    if (t == 0) {
-      int64_t run = 0;
-      for (int k = 0; k < NA_THREADS; ++k) { const int64_t v = part[k]; part[k] = run; run += v; }
-      part[NA_THREADS] = run;
-      if (FIRST) {                         // the ranks, from the totals
-        const int64_t n = run;
-        if (SEL == SEL_ROUGH) {            // keys with the sign bit (noise) are the upper half of the top digit
-          const int64_t ns = part[NA_THREADS / 2], nn = n - ns;
-          if (ns > 0) { in.rank[0] = (ns - 1) / 2; in.rank[1] = ns / 2; }
-          if (nn > 0) { in.rank[2] = ns + (nn - 1) / 2; in.rank[3] = ns + nn / 2; }
-        } else if (n > 0) {
-          in.rank[0] = (n - 1) / 2; in.rank[1] = n / 2;
-          if (SEL == SEL_MAG) {
-            percentile_ranks(n, 90.0f, in.rank[2], in.rank[3]);
-            percentile_ranks(n, 99.0f, in.rank[4], in.rank[5]);
-          }
-        }
-        for (int r = 0; r < NA_RANKS; ++r) {
-          in.rank0[r] = in.rank[r];
-          if (in.rank[r] < 0) in.group[r] = -1;
-        }
-      }
-    }
-    __syncthreads();
-    const int64_t start = part[t];
-    for (int r = 0; r < in.nranks; ++r) {
-      const int64_t rank = in.rank[r];
-      if (in.group[r] != g || rank < 0) continue;
-      if (rank >= start && rank < start + sum) {                // exactly one thread: rank < the count under the prefix
-        int64_t below = start;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-          if (rank >= below && rank < below + local[k]) {
-            out.prefix[r] = (in.prefix[r] << BITS) | (uint64_t)(t * PER + k);
-            out.rank[r] = rank - below;
-          }
-          below += local[k];
-        }
-      }
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    int groups = 0;
-    for (int r = 0; r < in.nranks; ++r) {
-      out.rank0[r] = in.rank0[r];
-      if (out.rank[r] < 0) continue;
-      int g = -1;
-      for (int q = 0; q < r; ++q)
-        if (out.rank[q] >= 0 && out.prefix[q] == out.prefix[r]) { g = out.group[q]; break; }
-      if (g < 0) { g = groups++; out.gprefix[g] = out.prefix[r]; }
-      out.group[r] = g;
-    }
-    for (int r = in.nranks; r < NA_RANKS; ++r) out.rank0[r] = -1;
-    out.ngroups = groups;
-    out.nranks = in.nranks;
-    *sel = out;
-    if (LAST) {
+// One workgroup after the histogram pass of level LEVEL.  Level 0: the ranks from the totals.  The last level: the prefixes are
+// the keys, written to the block.
+template <int SEL, int LEVEL>
+__global__ __launch_bounds__(NA_THREADS) void na_select(const uint32_t *__restrict__ hist, SelState<SEL> *sel, char *block) {
+  using Key = typename Selection<SEL>::Key;
+  using D = typename Selection<SEL>::D;
+  __shared__ SelectScratch<NA_RANKS, Key> sh;
+  select_digit<LEVEL == 0, D::width(LEVEL)>(hist, sel, sh, Selection<SEL>::nranks, [](const int64_t *part, int64_t *rank) {
+    const int64_t n = part[NA_THREADS];
+    if (SEL == SEL_ROUGH) {                // keys with the sign bit (noise) are the upper half of the top digit
+      const int64_t ns = part[NA_THREADS / 2], nn = n - ns;
+      if (ns > 0) { rank[0] = (ns - 1) / 2; rank[1] = ns / 2; }
+      if (nn > 0) { rank[2] = ns + (nn - 1) / 2; rank[3] = ns + nn / 2; }
+    } else if (n > 0) {
+      rank[0] = (n - 1) / 2; rank[1] = n / 2;
       if (SEL == SEL_MAG) {
-        for (int r = 0; r < BGNN_NA_MAG_RANKS; ++r) {
-          reinterpret_cast<int64_t *>(block + BGNN_NA_MAG_RANK)[r] = out.rank0[r];
-          reinterpret_cast<uint32_t *>(block + BGNN_NA_MAG_VALUE)[r] = out.rank[r] >= 0 ? (uint32_t)out.prefix[r] : 0x7FC00000u;
-        }
-      } else if (SEL == SEL_SIZE) {
-        for (int r = 0; r < 2; ++r) reinterpret_cast<int64_t *>(block + BGNN_NA_SIZE_MID)[r] = out.rank[r] >= 0 ? (int64_t)out.prefix[r] : 0;
-      } else {                             // block order: noise lo, hi (ranks 2, 3), seafloor lo, hi (ranks 0, 1); the sign bit goes
-        for (int r = 0; r < 4; ++r) {
-          const int from = (r + 2) & 3;
-          reinterpret_cast<uint64_t *>(block + BGNN_NA_ROUGH_MID)[r] =
-              out.rank[from] >= 0 ? (out.prefix[from] & 0x7FFFFFFFFFFFFFFFull) : 0x7FF8000000000000ull;
-        }
+        percentile_ranks(n, 90.0f, rank[2], rank[3]);
+        percentile_ranks(n, 99.0f, rank[4], rank[5]);
+      }
+    }
+  });
+  if (LEVEL == D::N - 1 && threadIdx.x == 0) {
+    const SelState<SEL> &out = sh.out;
+    if (SEL == SEL_MAG) {
+      for (int r = 0; r < BGNN_NA_MAG_RANKS; ++r) {
+        reinterpret_cast<int64_t *>(block + BGNN_NA_MAG_RANK)[r] = out.rank0[r];
+        reinterpret_cast<uint32_t *>(block + BGNN_NA_MAG_VALUE)[r] = out.rank[r] >= 0 ? (uint32_t)out.prefix[r] : 0x7FC00000u;
+      }
+    } else if (SEL == SEL_SIZE) {
+      for (int r = 0; r < 2; ++r) reinterpret_cast<int64_t *>(block + BGNN_NA_SIZE_MID)[r] = out.rank[r] >= 0 ? (int64_t)out.prefix[r] : 0;
+    } else {                               // block order: noise lo, hi (ranks 2, 3), seafloor lo, hi (ranks 0, 1); the sign bit goes
+      for (int r = 0; r < 4; ++r) {
+        const int from = (r + 2) & 3;
+        reinterpret_cast<uint64_t *>(block + BGNN_NA_ROUGH_MID)[r] =
+            out.rank[from] >= 0 ? ((uint64_t)out.prefix[from] & 0x7FFFFFFFFFFFFFFFull) : 0x7FF8000000000000ull;
       }
     }
   }
@@ -466,7 +350,7 @@ __global__ __launch_bounds__(NA_THREADS) void na_rough(const float *__restrict__
       if (in) plane[i] = bits;
       if (ok && noise) { cnt[0] += 1; sum[0] += rough; }
       if (ok && sea) { cnt[1] += 1; sum[1] += rough; }
-      hist_add(lds, ok, (uint32_t)(bits >> 53));
+      hist_add(lds, ok, (uint32_t)(bits >> Selection<SEL_ROUGH>::D::shift(0)));
     }
   }
   __syncthreads();
@@ -616,17 +500,39 @@ __global__ __launch_bounds__(NA_THREADS) void ccl_stats(int64_t cells, const int
 #pragma unroll
         for (int b = 0; b < BGNN_NA_SIZE_BINS; ++b) ci[3 + b] += (s >= edge[b] && s < edge[b + 1]);
       }
-      hist_add(lds, root, (uint32_t)s >> 21);
+      hist_add(lds, root, (uint32_t)s >> Selection<SEL_SIZE>::D::shift(0));
     }
   }
   __syncthreads();
   hist_flush(lds, NA_BINS, hist);
   int64_t *row = rows + (int64_t)blockIdx.x * ROW_WORDS;
   put_i(row, 0, block_sum_i(ci[0], red));
-  put_i(row, 1, block_reduce<int64_t>(total, red, [](int64_t a, int64_t b) { return a + b; }));
+  put_i(row, 1, block_reduce(total, red, SumOp()));
 #pragma unroll
   for (int k = 2; k < 3 + BGNN_NA_SIZE_BINS; ++k) put_i(row, k, block_sum_i(ci[k], red));
-  put_i(row, 3 + BGNN_NA_SIZE_BINS, block_reduce<int64_t>(mx, red, [](int64_t a, int64_t b) { return a > b ? a : b; }));
+  put_i(row, 3 + BGNN_NA_SIZE_BINS, block_reduce(mx, red, [](int64_t a, int64_t b) { return a > b ? a : b; }));
+}
+
+// The launches of selection SEL once its top digit is counted: na_select of level 0, then na_refine and na_select of every further
+// level; after_first_refine() goes between the two of level 1.
+struct SelLaunch {
+  hipStream_t stream;
+  int grid;
+  Source src;
+  int64_t cells;
+  char *workspace, *block;
+  int64_t *rows;
+};
+template <int SEL, int LEVEL = 0, typename F>
+void launch_selection(const SelLaunch &a, F after_first_refine) {
+  uint32_t *hist = reinterpret_cast<uint32_t *>(a.workspace) + (size_t)SEL * WS_SEL_WORDS + (size_t)LEVEL * WS_LEVEL_WORDS;
+  SelState<SEL> *state = reinterpret_cast<SelState<SEL> *>(a.workspace + WS_STATE + (size_t)SEL * 256);
+  if constexpr (LEVEL > 0) {
+    hipLaunchKernelGGL((na_refine<SEL, LEVEL>), dim3(a.grid), dim3(NA_THREADS), 0, a.stream, a.src, a.cells, state, hist, a.block, a.rows);
+    if (LEVEL == 1) after_first_refine();
+  }
+  hipLaunchKernelGGL((na_select<SEL, LEVEL>), dim3(1), dim3(NA_THREADS), 0, a.stream, hist, state, a.block);
+  if constexpr (LEVEL + 1 < Selection<SEL>::D::N) launch_selection<SEL, LEVEL + 1>(a, after_first_refine);
 }
 
 inline bool within_limit(int64_t rows, int64_t cols) { return rows >= 1 && cols >= 1 && rows <= (int64_t)BGNN_NA_MAX_CELLS / cols; }
@@ -665,8 +571,7 @@ extern "C" int bgnn_noise_analysis(bgnn_ctx *ctx, const int32_t *labels, const f
   const int64_t cells = rows * cols;
   char *w = static_cast<char *>(workspace), *blk = static_cast<char *>(block);
   uint32_t *hists = reinterpret_cast<uint32_t *>(w);
-  auto hist = [&](int sel, int level) { return hists + (size_t)sel * WS_SEL_WORDS + (size_t)level * WS_LEVEL_WORDS; };
-  auto state = [&](int sel) { return reinterpret_cast<SelState *>(w + WS_STATE + (size_t)sel * 256); };
+  auto top_hist = [&](int sel) { return hists + (size_t)sel * WS_SEL_WORDS; };
   int64_t *part = reinterpret_cast<int64_t *>(w + WS_ROWS);
   int32_t *parent = reinterpret_cast<int32_t *>(w + WS_PLANES);
   int32_t *size = reinterpret_cast<int32_t *>(w + WS_PLANES + align256((size_t)cells * 4));
@@ -676,11 +581,12 @@ extern "C" int bgnn_noise_analysis(bgnn_ctx *ctx, const int32_t *labels, const f
   tg.tiles_r = (int32_t)((rows + TILE_R - 1) / TILE_R); tg.tiles_c = (int32_t)((cols + TILE_C - 1) / TILE_C);
   const int64_t tiles = (int64_t)tg.tiles_r * tg.tiles_c;
   const int64_t borders = (int64_t)(tg.tiles_r - 1) * cols + (int64_t)(tg.tiles_c - 1) * rows;
-  const int g_stream = capped_grid((cells + NA_CHUNK - 1) / NA_CHUNK), g_tiles = capped_grid(tiles);
-  const int g_cells = capped_grid((cells + NA_THREADS - 1) / NA_THREADS), g_borders = capped_grid((borders + NA_THREADS - 1) / NA_THREADS);
+  const auto grid_of = [](int64_t work_items) { return capped_grid(work_items, NA_MAX_GRID); };
+  const int g_stream = grid_of((cells + NA_CHUNK - 1) / NA_CHUNK), g_tiles = grid_of(tiles);
+  const int g_cells = grid_of((cells + NA_THREADS - 1) / NA_THREADS), g_borders = grid_of((borders + NA_THREADS - 1) / NA_THREADS);
   const dim3 b(NA_THREADS), one(1), fin(64);
   hipStream_t s = ctx->stream;
-  Source src{labels, difference, parent, size, rough};
+  const SelLaunch sel{s, g_stream, Source{labels, difference, parent, size, rough}, cells, w, blk, part};
 
   BGNN_HIP_CHECK(hipMemsetAsync(w, 0, WS_CLEAR_BYTES, s));
   BGNN_HIP_CHECK(hipMemsetAsync(blk, 0, BGNN_NA_BYTES, s));
@@ -688,7 +594,7 @@ extern "C" int bgnn_noise_analysis(bgnn_ctx *ctx, const int32_t *labels, const f
   BGNN_HIP_CHECK(hipMemsetAsync(col_valid, 0, (size_t)cols * 4, s));
 
   // 1, 2: magnitude, sign, depth bins; the six order statistics of |difference|
-  hipLaunchKernelGGL(na_stream, dim3(g_stream), b, 0, s, labels, difference, noisy, cells, hist(SEL_MAG, 0), part);
+  hipLaunchKernelGGL(na_stream, dim3(g_stream), b, 0, s, labels, difference, noisy, cells, top_hist(SEL_MAG), part);
   {
     FinishMap m{};
     map_run(m, 0, BGNN_NA_VALID, ST_INTS);
@@ -697,42 +603,27 @@ extern "C" int bgnn_noise_analysis(bgnn_ctx *ctx, const int32_t *labels, const f
     map_run(m, 2, BGNN_NA_ABS_MAX, 1);
     hipLaunchKernelGGL(na_finish, one, fin, 0, s, part, g_stream, m, blk);
   }
-  hipLaunchKernelGGL((na_select<SEL_MAG, 11, true, false>), one, b, 0, s, hist(SEL_MAG, 0), state(SEL_MAG), blk);
-  hipLaunchKernelGGL((na_refine<SEL_MAG, 10, 11, true>), dim3(g_stream), b, 0, s, src, cells, state(SEL_MAG), hist(SEL_MAG, 1), blk, part);
-  {
+  launch_selection<SEL_MAG>(sel, [&] {
     FinishMap m{};
     map_run(m, 1, BGNN_NA_DEV_SQ_SUM, 1);
     hipLaunchKernelGGL(na_finish, one, fin, 0, s, part, g_stream, m, blk);
-  }
-  hipLaunchKernelGGL((na_select<SEL_MAG, 11, false, false>), one, b, 0, s, hist(SEL_MAG, 1), state(SEL_MAG), blk);
-  hipLaunchKernelGGL((na_refine<SEL_MAG, 0, 10, false>), dim3(g_stream), b, 0, s, src, cells, state(SEL_MAG), hist(SEL_MAG, 2), blk, part);
-  hipLaunchKernelGGL((na_select<SEL_MAG, 10, false, true>), one, b, 0, s, hist(SEL_MAG, 2), state(SEL_MAG), blk);
+  });
 
-  // 5: roughness and its class medians: six digits of 11, 11, 11, 11, 11 and 9 bits
-  hipLaunchKernelGGL(na_rough, dim3(g_tiles), b, 0, s, clean, labels, tg, rough, hist(SEL_ROUGH, 0), part);
+  // 5: roughness and its class medians
+  hipLaunchKernelGGL(na_rough, dim3(g_tiles), b, 0, s, clean, labels, tg, rough, top_hist(SEL_ROUGH), part);
   {
     FinishMap m{};
     map_run(m, 0, BGNN_NA_ROUGH_COUNT, 2);
     map_run(m, 1, BGNN_NA_ROUGH_SUM, 2);
     hipLaunchKernelGGL(na_finish, one, fin, 0, s, part, g_tiles, m, blk);
   }
-  hipLaunchKernelGGL((na_select<SEL_ROUGH, 11, true, false>), one, b, 0, s, hist(SEL_ROUGH, 0), state(SEL_ROUGH), blk);
-  hipLaunchKernelGGL((na_refine<SEL_ROUGH, 42, 11, false>), dim3(g_stream), b, 0, s, src, cells, state(SEL_ROUGH), hist(SEL_ROUGH, 1), blk, part);
-  hipLaunchKernelGGL((na_select<SEL_ROUGH, 11, false, false>), one, b, 0, s, hist(SEL_ROUGH, 1), state(SEL_ROUGH), blk);
-  hipLaunchKernelGGL((na_refine<SEL_ROUGH, 31, 11, false>), dim3(g_stream), b, 0, s, src, cells, state(SEL_ROUGH), hist(SEL_ROUGH, 2), blk, part);
-  hipLaunchKernelGGL((na_select<SEL_ROUGH, 11, false, false>), one, b, 0, s, hist(SEL_ROUGH, 2), state(SEL_ROUGH), blk);
-  hipLaunchKernelGGL((na_refine<SEL_ROUGH, 20, 11, false>), dim3(g_stream), b, 0, s, src, cells, state(SEL_ROUGH), hist(SEL_ROUGH, 3), blk, part);
-  hipLaunchKernelGGL((na_select<SEL_ROUGH, 11, false, false>), one, b, 0, s, hist(SEL_ROUGH, 3), state(SEL_ROUGH), blk);
-  hipLaunchKernelGGL((na_refine<SEL_ROUGH, 9, 11, false>), dim3(g_stream), b, 0, s, src, cells, state(SEL_ROUGH), hist(SEL_ROUGH, 4), blk, part);
-  hipLaunchKernelGGL((na_select<SEL_ROUGH, 11, false, false>), one, b, 0, s, hist(SEL_ROUGH, 4), state(SEL_ROUGH), blk);
-  hipLaunchKernelGGL((na_refine<SEL_ROUGH, 0, 9, false>), dim3(g_stream), b, 0, s, src, cells, state(SEL_ROUGH), hist(SEL_ROUGH, 5), blk, part);
-  hipLaunchKernelGGL((na_select<SEL_ROUGH, 9, false, true>), one, b, 0, s, hist(SEL_ROUGH, 5), state(SEL_ROUGH), blk);
+  launch_selection<SEL_ROUGH>(sel, [] {});
 
   // 3, 4: clusters, the per-column counts, the median cluster size
   hipLaunchKernelGGL(ccl_local, dim3(g_tiles), b, 0, s, labels, tg, parent, size, col_noise, col_valid);
   hipLaunchKernelGGL(ccl_merge, dim3(g_borders), b, 0, s, tg, parent);
   hipLaunchKernelGGL(ccl_flatten, dim3(g_cells), b, 0, s, cells, parent, size);
-  hipLaunchKernelGGL(ccl_stats, dim3(g_stream), b, 0, s, cells, parent, size, hist(SEL_SIZE, 0), part);
+  hipLaunchKernelGGL(ccl_stats, dim3(g_stream), b, 0, s, cells, parent, size, top_hist(SEL_SIZE), part);
   {
     FinishMap m{};
     map_run(m, 0, BGNN_NA_NUM_CLUSTERS, 2);
@@ -740,11 +631,7 @@ extern "C" int bgnn_noise_analysis(bgnn_ctx *ctx, const int32_t *labels, const f
     map_run(m, 3, BGNN_NA_MAX_CLUSTER, 1);
     hipLaunchKernelGGL(na_finish, one, fin, 0, s, part, g_stream, m, blk);
   }
-  hipLaunchKernelGGL((na_select<SEL_SIZE, 11, true, false>), one, b, 0, s, hist(SEL_SIZE, 0), state(SEL_SIZE), blk);
-  hipLaunchKernelGGL((na_refine<SEL_SIZE, 10, 11, false>), dim3(g_stream), b, 0, s, src, cells, state(SEL_SIZE), hist(SEL_SIZE, 1), blk, part);
-  hipLaunchKernelGGL((na_select<SEL_SIZE, 11, false, false>), one, b, 0, s, hist(SEL_SIZE, 1), state(SEL_SIZE), blk);
-  hipLaunchKernelGGL((na_refine<SEL_SIZE, 0, 10, false>), dim3(g_stream), b, 0, s, src, cells, state(SEL_SIZE), hist(SEL_SIZE, 2), blk, part);
-  hipLaunchKernelGGL((na_select<SEL_SIZE, 10, false, true>), one, b, 0, s, hist(SEL_SIZE, 2), state(SEL_SIZE), blk);
+  launch_selection<SEL_SIZE>(sel, [] {});
   BGNN_HIP_CHECK(hipGetLastError());
   return BGNN_OK;
 }

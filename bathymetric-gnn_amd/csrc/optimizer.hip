@@ -6,26 +6,19 @@
 #include <cmath>
 
 #include "bgnn_internal.h"
+#include "plane_util.h"
 
 using namespace bgnn;
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = BLOCK_THREADS;
 
 struct AdamChunk { uint64_t offset; uint32_t count, slot; };        // <= BGNN_ADAMW_CHUNK elements of one slot
 struct AdamSlot { double step_size, bc2_sqrt; };                    // lr / (1 - beta1^t), sqrt(1 - beta2^t)
 
-// fixed tree over the block's 256 running sums; the result in thread 0
-__device__ inline double block_sum_fixed(double s, double *sh) {
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = kBlock / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
-  return sh[0];
-}
+// fixed tree over the block's 256 running sums (no leading barrier: each kernel calls it once, on scratch nobody has read)
+__device__ inline double block_sum_fixed(double s, double *sh) { return block_reduce<false>(s, sh, SumOp()); }
 
 // partial[c] = sum of g^2 over chunk c: thread t takes elements t, t + 256, ... in order, then the tree
 __global__ void __launch_bounds__(kBlock) adamw_sumsq_kernel(const float *g, const AdamChunk *chunks, double *partial) {

@@ -13,6 +13,7 @@
 //                    rounds after every blob) and systematic terms, the four outputs
 // Only noise_local_std has arithmetic weight (242 LDS reads and float64 operations per cell); the rest moves 5 .. 55 B per cell.
 #include "bgnn_internal.h"
+#include "plane_util.h"
 #include "../../include/bgnn_noise.h"
 
 #include <math.h>
@@ -79,37 +80,10 @@ __device__ __forceinline__ double noise_uniform(uint64_t key, uint32_t stream, u
   return (double)(noise_bits(key, stream, cell) >> 11) * 0x1.0p-53;
 }
 
-// fixed-order tree sums over the 256 threads of a workgroup; every thread gets the result
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-__device__ __forceinline__ float block_min(float v, float *sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] = fminf(sh[threadIdx.x], sh[threadIdx.x + s]);
-    __syncthreads();
-  }
-  return sh[0];
-}
-__device__ __forceinline__ float block_max(float v, float *sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] = fmaxf(sh[threadIdx.x], sh[threadIdx.x + s]);
-    __syncthreads();
-  }
-  return sh[0];
-}
+// fixed-order trees over the 256 threads of a workgroup (plane_util.h); every thread gets the result
+__device__ __forceinline__ double block_sum(double v, double *sh) { return block_reduce(v, sh, SumOp()); }
+__device__ __forceinline__ float block_min(float v, float *sh) { return block_reduce(v, sh, [](float a, float b) { return fminf(a, b); }); }
+__device__ __forceinline__ float block_max(float v, float *sh) { return block_reduce(v, sh, [](float a, float b) { return fmaxf(a, b); }); }
 
 __global__ __launch_bounds__(256) void noise_stats1(NoiseArgs a) {
   __shared__ double shd[256];
@@ -357,7 +331,6 @@ struct NoiseLayout {
   int32_t max_sblk, max_ablk;
 };
 
-static size_t noise_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // false: arguments bgnn_noise_generate refuses (`why`, `code` say which way)
 static bool noise_layout(int32_t n_tiles, const int32_t *hw, int32_t n_blobs, NoiseLayout &L, const char **why, int *code) {
@@ -379,13 +352,13 @@ static bool noise_layout(int32_t n_tiles, const int32_t *hw, int32_t n_blobs, No
   L.tiles = o; o += (size_t)n_tiles * sizeof(NoiseTile);
   L.plans = o; o += (size_t)n_tiles * sizeof(bgnn_noise_plan);
   L.blobs = o; o += (size_t)n_blobs * sizeof(bgnn_noise_blob);
-  L.host_bytes = o; o = noise_align(o);
-  L.scal = o; o = noise_align(o + (size_t)n_tiles * sizeof(NoiseScalars));
-  L.p1 = o; o = noise_align(o + (size_t)n_tiles * NOISE_NB1 * 6 * sizeof(double));
-  L.p2 = o; o = noise_align(o + (size_t)n_tiles * NOISE_NB1 * sizeof(double));
-  L.lmm = o; o = noise_align(o + (size_t)n_tiles * L.max_sblk * sizeof(NoiseLmm));
-  L.segcnt = o; o = noise_align(o + (size_t)n_tiles * L.max_ablk * sizeof(int32_t));
-  L.lstd = o; o = noise_align(o + (size_t)L.cells * sizeof(float));
+  L.host_bytes = o; o = align256(o);
+  L.scal = o; o = align256(o + (size_t)n_tiles * sizeof(NoiseScalars));
+  L.p1 = o; o = align256(o + (size_t)n_tiles * NOISE_NB1 * 6 * sizeof(double));
+  L.p2 = o; o = align256(o + (size_t)n_tiles * NOISE_NB1 * sizeof(double));
+  L.lmm = o; o = align256(o + (size_t)n_tiles * L.max_sblk * sizeof(NoiseLmm));
+  L.segcnt = o; o = align256(o + (size_t)n_tiles * L.max_ablk * sizeof(int32_t));
+  L.lstd = o; o = align256(o + (size_t)L.cells * sizeof(float));
   L.total = o;
   return true;
 }

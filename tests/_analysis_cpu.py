@@ -121,6 +121,31 @@ def numpy_analysis(labels, difference, noisy, clean, file="None"):
     return analysis_from_block(block, col_noise, col_valid, np.asarray(labels).shape, file)
 
 
+# the ground truth's constructed keys (_eval_checks.adversarial_case) whose magnitudes the six-rank selection is held to
+MAGNITUDE_KEY_CASES = ("uniform_keys_4098", "uniform_keys_4099", "straddle_level1", "straddle_level2", "first_bin_owner",
+                       "last_bin_owner", "denormals")
+
+
+def magnitude_key_case(name):
+    """``(planes, block, col_noise, col_valid)``: a 1 x n grid whose ``difference`` is ``|values|`` of
+    ``adversarial_case(name)``, every label 2, both depths 0, and the restatement's result (built once; read-only)."""
+    if ("keys", name) not in _cache:
+        from _eval_checks import adversarial_case
+        difference = np.abs(adversarial_case(name).values).reshape(1, -1)
+        assert difference.dtype == F32 and np.isfinite(difference).all()
+        zero = np.zeros_like(difference)
+        planes = (np.full(difference.shape, 2, np.int32), difference, zero, zero)
+        for a in planes:
+            a.setflags(write=False)
+        _cache[("keys", name)] = (planes,) + numpy_analysis_block(*planes)
+    return _cache[("keys", name)]
+
+
+def ulps_apart(a, b):
+    """The distance of two float32 values of one sign in units of the last place."""
+    return abs(int(F32(a).view(np.int32)) - int(F32(b).view(np.int32)))
+
+
 def _same(a, b):
     """Equal values of equal type (NaN equals NaN)."""
     if isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b):

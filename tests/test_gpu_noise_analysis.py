@@ -2,14 +2,16 @@
 make_golden_analysis.py with the reference's ``analyze_ground_truth``) from host arrays and from device tensors, under the rules
 of _analysis_cpu; once through ``GroundTruth.analyze()``; equal bits from two calls; and random masks at three densities on a
 300 x 517 grid -- up to the site-percolation threshold, where ragged clusters cross every tile border -- against the numpy / scipy
-restatement.  An 8-connected labelling fails ``checkerboard_64``, a lost cross-tile merge fails ``serpentine_128``, ``comb_130x67``
+restatement; the six-rank selection on the keys constructed for the ground truth's two-rank one, and both against each other.
+An 8-connected labelling fails ``checkerboard_64``, a lost cross-tile merge fails ``serpentine_128``, ``comb_130x67``
 and the random masks."""
 import numpy as np
 import pytest
 import torch
 from scipy import ndimage
 
-from _analysis_cpu import ANALYSIS_CASES, ROUGH_RTOL, STRICT_CASES, check_analysis, load_analysis_case, numpy_analysis, numpy_analysis_block
+from _analysis_cpu import (ANALYSIS_CASES, MAGNITUDE_KEY_CASES, ROUGH_RTOL, STRICT_CASES, check_analysis, load_analysis_case,
+                           magnitude_key_case, numpy_analysis, numpy_analysis_block, ulps_apart)
 from _eval_checks import grids_of, load_case, sum_tolerance
 
 pytestmark = pytest.mark.gpu
@@ -113,6 +115,51 @@ def test_more_work_than_one_launch_grid(shape, with_roughness, gpu_device):
         assert np.array_equal(block["rough_count"], want_block["rough_count"])
         for k in ("rough_sum", "rough_mid"):
             assert np.allclose(block[k], want_block[k], rtol=ROUGH_RTOL, atol=0), (k, block[k], want_block[k])
+
+
+@pytest.mark.parametrize("name", MAGNITUDE_KEY_CASES)
+def test_six_ranks_on_the_ground_truths_adversarial_keys(name, gpu_device):
+    """The magnitudes are the keys tests/test_gpu_truth_eval_edges.py holds the median to (uniform over the key space, a middle
+    pair that parts at the first / the second digit boundary, a median that owns the first / the last place of its bin,
+    denormals): here all six ranks go through them.  Ranks and selected values are numpy's, bit for bit."""
+    from bathymetric_gnn_amd.data.noise_analysis import analysis_from_block, noise_analysis_build, split_result
+    planes, want_block, want_cn, want_cv = magnitude_key_case(name)
+    shape = planes[0].shape
+    out = noise_analysis_build(*(torch.from_numpy(p.copy()).to(gpu_device) for p in planes)).cpu().numpy()
+    block, cn, cv = split_result(out, shape[1])
+    assert np.array_equal(block["mag_rank"], want_block["mag_rank"]), (block["mag_rank"], want_block["mag_rank"])
+    assert block["mag_value"].tobytes() == want_block["mag_value"].tobytes(), (block["mag_value"], want_block["mag_value"])
+    got = analysis_from_block(block, cn, cv, shape, name)["magnitude"]
+    want = analysis_from_block(want_block, want_cn, want_cv, shape, name)["magnitude"]
+    assert got["median"] == want["median"], (got, want)
+    for k in ("p90", "p99"):
+        assert float(np.float32(got[k])) == got[k] and ulps_apart(got[k], want[k]) <= 1, (k, got[k], want[k])
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (1, 2), (97, 203), (64, 33)], ids=["one_cell", "two_cells", "odd_97x203", "even_64x33"])
+def test_median_of_the_analysis_is_the_ground_truths_offset(shape, gpu_device):
+    """One selection behind both: on strictly positive differences d (clean 0, noisy d, so noisy - clean is d exactly) the ground
+    truth's offset is the analysis's lower middle magnitude for an odd count and the float32 mean of its two middle ones for an
+    even count, bit for bit."""
+    from bathymetric_gnn_amd import runtime
+    from bathymetric_gnn_amd.data.ground_truth import ground_truth_build
+    from bathymetric_gnn_amd.data.noise_analysis import noise_analysis_build, split_result
+    rng = np.random.default_rng([20240818, shape[0], shape[1]])
+    d = (0.01 + rng.exponential(0.3, shape)).astype(np.float32)
+    d[rng.random(shape) < 0.3] = np.float32(0.2109375)          # ties around the middle
+    assert (d > 0).all() and np.isfinite(d).all()
+    n = d.size
+    noisy = torch.from_numpy(d).to(gpu_device)
+    clean = torch.zeros_like(noisy)
+    stats = ground_truth_build(clean, noisy)[3]
+    truth = np.frombuffer(stats.cpu().numpy().tobytes(), np.dtype(runtime.GT_STATS_DTYPE))[0]
+    labels = torch.full(shape, 2, dtype=torch.int32, device=gpu_device)
+    block, _, _ = split_result(noise_analysis_build(labels, noisy, noisy, clean).cpu().numpy(), shape[1])
+    assert int(truth["valid"]) == n and int(block["noise"]) == n
+    a, b = (np.float32(v) for v in block["mag_value"][:2])
+    assert (a, b) == tuple(np.sort(d.reshape(-1))[[(n - 1) // 2, n // 2]])
+    want = a if n % 2 else np.float32(a + b) / np.float32(2)
+    assert np.float32(truth["offset"]).tobytes() == np.float32(want).tobytes(), (truth["offset"], want)
 
 
 def test_nonfinite_noise_difference_raises(gpu_device):

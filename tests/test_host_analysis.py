@@ -7,7 +7,8 @@ import math
 import numpy as np
 import pytest
 
-from _analysis_cpu import ANALYSIS_CASES, STRICT_CASES, check_analysis, load_analysis_case, numpy_analysis, numpy_analysis_block
+from _analysis_cpu import (ANALYSIS_CASES, MAGNITUDE_KEY_CASES, STRICT_CASES, check_analysis, load_analysis_case, magnitude_key_case,
+                           numpy_analysis, numpy_analysis_block, ulps_apart)
 
 EXPECTED = {"mixed_97x203", "serpentine_128", "comb_130x67", "checkerboard_64", "all_noise_128", "two_clusters_even", "no_noise",
             "no_seafloor", "bin_edges", "inf_neighbour", "one_row_1x300", "one_col_300x1", "one_cell", "percentile_ranks_101",
@@ -50,6 +51,19 @@ def test_percentile_ranks_follow_numpy():
         assert float(np.median(v)) == float(v[ranks[0]] if n % 2 else np.float32(v[ranks[0]] + v[ranks[1]]) / np.float32(2))
         assert np.percentile(v, 90) == _lerp(v[ranks[2]], v[ranks[3]], g90), n
         assert np.percentile(v, 99) == _lerp(v[ranks[4]], v[ranks[5]], g99), n
+
+
+@pytest.mark.parametrize("name", MAGNITUDE_KEY_CASES)
+def test_restatement_takes_the_ground_truths_adversarial_keys(name):
+    """What tests/test_gpu_noise_analysis.py holds the six-rank selection to: the restatement accepts the ground truth's
+    constructed keys as magnitudes (all finite, every cell noise), and its order statistics are numpy's own."""
+    from bathymetric_gnn_amd.data.noise_analysis import analysis_from_block
+    planes, block, cn, cv = magnitude_key_case(name)
+    mag = planes[1].reshape(-1)
+    assert int(block["noise"]) == mag.size and int(block["nonfinite"]) == 0 and 1001 <= mag.size <= 4099
+    m = analysis_from_block(block, cn, cv, planes[0].shape, name)["magnitude"]
+    assert m["median"] == float(np.median(mag)) and m["max"] == float(mag.max())
+    assert ulps_apart(m["p90"], np.percentile(mag, 90)) <= 1 and ulps_apart(m["p99"], np.percentile(mag, 99)) <= 1
 
 
 def test_nonfinite_noise_difference_is_refused():

@@ -19,7 +19,7 @@ def main():
     filt = subprocess.run(["c++filt"], input="\n".join(b.split()[0] for b in blocks), capture_output=True, text=True).stdout.split("\n")
     for b, dem in zip(blocks, filt):
         g = lambda k: (re.search(k + r": (\d+)", b) or [None, "?"])[1]
-        dem = dem.replace("bgnn::", "").replace("void ", "")
+        dem = dem.replace("bgnn::", "").replace("(anonymous namespace)::", "").replace("void ", "")
         dem = re.sub(r"\(.*", "", dem)
         if flt and not any(f in dem for f in flt):
             continue
