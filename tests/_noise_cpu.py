@@ -5,7 +5,10 @@ arithmetic the kernels use: per-tile scalars accumulated in float64 and rounded 
 standard deviation in float64 stored as float32, the reference's float32 / float64 mix in every term.  It takes the same plan
 (scalars + blob list) and the same optional injected per-cell fields as ``bgnn_noise_generate``.  tests/test_host_noise.py pins
 it against the reference's recorded outputs; tests/test_gpu_noise.py then uses it as the yardstick for the device's own draws.
+The second half builds the tiles and the exact expectations of tests/test_gpu_noise_scale.py (training tile sizes).
 """
+import functools
+
 import numpy as np
 
 GOLD = 0x9E3779B97F4A7C15
@@ -109,7 +112,8 @@ def generate(depth, valid, plan, params, seed=0, fields=None):
     mean = vd.sum() / nv
     std32 = np.float32(np.sqrt(((vd - mean) ** 2).sum() / nv))
     range32 = np.float32(depth[valid].max()) - np.float32(depth[valid].min())
-    ls = local_std(np.where(valid, depth, nanmean))
+    filled = np.where(valid, depth, nanmean)
+    ls = local_std(filled) if filled.size <= 1 << 16 else local_std_banded(filled)      # (the same bits: test_host_noise.py)
     lmin, lmax = ls.min(), ls.max()
     cx = (ls - lmin) / (lmax - lmin) if lmax > lmin else np.zeros_like(ls)
     info.update(nanmean=nanmean, depth_std=std32, depth_range=range32, local_std=ls, complexity=cx)
@@ -291,3 +295,293 @@ def check_fixture(out, path, c):
         mag_bound = c * (r + EPS32)
     return check_outputs(out, depth, valid, info, z["noisy_depth64"], z["noise_mask"], z["noise_magnitude"], z["classification"],
                          noisy_bound, mag_bound, label)
+
+
+# ---- tiles at training sizes (tests/test_gpu_noise_scale.py; the inputs are checked by tests/test_host_noise.py) ---------------------
+RUN = 256                # cells per run of the device's rank-select (one noise_apply workgroup)
+STRIPS = 256             # strips of runs: one per thread of noise_finalize
+STATS_STRIDE = 64 * 256  # cells one trip of the statistics passes covers (NOISE_NB1 workgroups of 256 threads)
+
+
+def local_std_banded(filled, band=32, window=11, mode="edge", shift=0):
+    """``local_std`` in bands of ``band`` rows, so that a 1024 x 1024 tile needs no [cells, 121] float64 array; the defaults
+    give its bits.  ``window``, ``mode`` (numpy.pad) and ``shift`` (columns the window is moved to the right) restate it wrongly
+    on purpose, for the checks that the complexity probe sees such a defect."""
+    h, w = filled.shape
+    r, n = window // 2, window * window
+    p = np.pad(filled.astype(np.float64), ((r, r), (r - shift, r + shift)), mode=mode)
+    out = np.empty((h, w), np.float32)
+    for r0 in range(0, h, band):
+        r1 = min(h, r0 + band)
+        win = np.lib.stride_tricks.sliding_window_view(p[r0:r1 + 2 * r], (window, window)).reshape(r1 - r0, w, n)
+        mean = win.sum(-1) / float(n)
+        out[r0:r1] = np.sqrt(((win - mean[..., None]) ** 2).sum(-1) / float(n)).astype(np.float32)
+    return out
+
+
+def spike_density_map(ls, spike_density, complexity_correlation):
+    """The density map of ``generate`` from a local_std map (float32 throughout)."""
+    lmin, lmax = ls.min(), ls.max()
+    cx = (ls - lmin) / (lmax - lmin) if lmax > lmin else np.zeros_like(ls)
+    return np.float32(spike_density) * (np.float32(1) + np.float32(complexity_correlation) * (cx - np.float32(0.5)))
+
+
+def run_counts(valid):
+    """Valid cells of every run of RUN cells of a tile, row-major (the device's ``segcnt``)."""
+    flat = np.asarray(valid, bool).ravel()
+    return np.add.reduceat(flat.astype(np.int64), np.arange(0, flat.size, RUN))
+
+
+def select_path(valid, k):
+    """Where the device's rank-select meets the k-th valid cell: its run, its strip (``per`` runs per strip) and the categories
+    the tests of the blob centres want covered."""
+    c = run_counts(valid)
+    nr = len(c)
+    per = (nr + STRIPS - 1) // STRIPS
+    run = int(np.searchsorted(np.cumsum(c), k, side="right"))
+    strip = run // per
+    strip_count = np.add.reduceat(c, np.arange(0, nr, per))
+    return {"run": run, "strip": strip, "per": per, "runs": nr,
+            "after_empty_strip": bool(strip > 0 and strip_count[strip - 1] == 0),
+            "last_strip": strip == (nr - 1) // per,
+            "not_first_run_of_strip": run % per != 0,
+            "final_partial_run": bool(run == nr - 1 and valid.size % RUN != 0)}
+
+
+def device_rank_select(valid, u):
+    """noise_finalize's rank-select, step by step: a prefix over the strips, a walk over the runs of one strip, a walk over the
+    cells of one run.  (row, col) like ``kth_valid_cell``, or None where the device leaves the blob unresolved."""
+    flat = np.asarray(valid, bool).ravel()
+    n, seg = flat.size, run_counts(valid)
+    nr = len(seg)
+    per = (nr + STRIPS - 1) // STRIPS
+    pre = [0]
+    for t in range(STRIPS):
+        pre.append(pre[-1] + int(seg[t * per:min(t * per + per, nr)].sum()))
+    nv = pre[STRIPS]
+    if nv <= 0:
+        return None
+    k = min(max(int(u * float(nv)), 0), nv - 1)
+    j = 0
+    while j < STRIPS - 1 and pre[j + 1] <= k:
+        j += 1
+    left, sg = k - pre[j], j * per
+    sg_end = min(sg + per, nr)
+    while sg < sg_end - 1 and left >= seg[sg]:
+        left -= int(seg[sg])
+        sg += 1
+    for i in range(sg * RUN, min(sg * RUN + RUN, n)):
+        if flat[i]:
+            if left == 0:
+                return divmod(i, valid.shape[1])
+            left -= 1
+    return None
+
+
+def centre_draws(valid, total, seed, each=4):
+    """Blob-centre draws ``u`` for a tile: 0, nextafter(1, 0) and 1 (clamps to the last valid cell), then (k + 0.5) / n_valid
+    for k = 0, n_valid - 1, n_valid // 2, the last cell before and the first cell of up to ``each`` + 2 strip boundaries (those
+    after an empty strip and the last one first) and run boundaries inside a strip (the final run first), and random k up to
+    ``total`` draws.  Returns (us, ks): ks[i] = the rank the device must resolve us[i] to."""
+    nv = int(np.asarray(valid).sum())
+    c = run_counts(valid)
+    nr = len(c)
+    per = (nr + STRIPS - 1) // STRIPS
+    before = np.concatenate([[0], np.cumsum(c)[:-1]])            # valid cells before every run
+    strip_count = np.add.reduceat(c, np.arange(0, nr, per))
+    ks = [0, nv - 1, nv // 2]
+    rng = np.random.default_rng(seed)
+
+    def pick(cands, first):
+        cands = [int(x) for x in cands]
+        head = [x for x in first if x in cands]
+        rest = [x for x in cands if x not in head]
+        if len(rest) > each:
+            rest = sorted(rng.choice(rest, each, replace=False).tolist())
+        return head + rest
+
+    strips = [j for j in range(1, len(strip_count)) if strip_count[j] > 0 and before[j * per] > 0]
+    after_empty = [j for j in strips if strip_count[j - 1] == 0]
+    for j in pick(strips, after_empty[:1] + strips[-1:]):
+        ks += [int(before[j * per]) - 1, int(before[j * per])]
+    runs = [r for r in range(nr) if r % per != 0 and c[r] > 0 and before[r] > 0]
+    for r in pick(runs, runs[-1:]):
+        ks += [int(before[r]) - 1, int(before[r])]
+    ks += rng.integers(0, nv, max(0, total - 3 - len(ks))).tolist()
+    one = float(np.nextafter(1.0, 0.0))
+    us = [0.0, one, 1.0] + [(k + 0.5) / nv for k in ks]
+    return us, [0, min(int(one * nv), nv - 1), nv - 1] + ks
+
+
+def expected_unit_blobs(depth, valid, us):
+    """What blobs of size 1 and magnitude draw 1.0 at intensity 1.0 must give, bit for bit: a size-1 blob covers its centre alone
+    and adds exp(0) x depth_range there, once per blob in list order.  Returns noisy, mask, magnitude, depth_range."""
+    depth = np.ascontiguousarray(depth, np.float32)
+    noisy, mask, mag = depth.copy(), np.zeros(depth.shape, bool), np.zeros(depth.shape, np.float32)
+    idx = np.flatnonzero(np.asarray(valid, bool).ravel())
+    if len(idx) == 0:
+        return noisy, mask, mag, np.float32(0)
+    vd = depth.ravel()[idx]
+    range32 = np.float32(vd.max()) - np.float32(vd.min())
+    for u in us:
+        i = idx[min(int(u * len(idx)), len(idx) - 1)]
+        noisy.flat[i] = np.float32(np.float64(noisy.flat[i]) + np.float64(range32))
+        mask.flat[i] = True
+        mag.flat[i] = range32
+    return noisy, mask, mag, range32
+
+
+def _field(h, w, seed):
+    from bathymetric_gnn_amd import synthetic
+    return synthetic.synthetic_tile(h, w, seed, "V0")[0]
+
+
+CENTRE_NAMES = ("260x253 0.9 valid", "17x16 full", "7x11 full", "300x517 0.01 valid", "300x517 rows 40..199 invalid", "64x64 no valid cell",
+                "260x253 only the first cell", "260x253 only the last cell", "260x253 only the last partial run", "3x30000 0.5 valid",
+                "512x512 V1", "1024x1024 V1")
+SCALAR_NAMES = ("holes 1e6", "holes NaN", "valid among the last 300")
+
+
+def centre_case(i):
+    """(name, depth, valid, draws) of tile i of ``centre_tiles``; a tile without a valid cell still gets a list of draws."""
+    name, depth, valid, total, _ = centre_tiles()[i]
+    us = centre_draws(valid, total, 100 + i)[0] if valid.any() else [j / total for j in range(total)] + [1.0]
+    return name, depth, valid, us
+
+
+@functools.lru_cache(maxsize=None)
+def centre_tiles():
+    """[(name, depth, valid, draws wanted, categories its draws must reach)] of the blob-centre tests, in batch order: the
+    272-cell and 77-cell tiles come before the large ones, whose runs then start at cell offsets of the batch that are a multiple
+    of neither 256 nor 4."""
+    from bathymetric_gnn_amd import synthetic
+    rng = np.random.default_rng(20240)
+    out = []
+
+    def add(name, h, w, seed, valid, total, cats):
+        out.append((name, _field(h, w, seed), np.ascontiguousarray(valid), total, cats))
+
+    add("260x253 0.9 valid", 260, 253, 1, rng.random((260, 253)) < 0.9, 720, ("last_strip", "not_first_run_of_strip", "final_partial_run"))
+    add("17x16 full", 17, 16, 2, np.ones((17, 16), bool), 24, ("final_partial_run",))
+    add("7x11 full", 7, 11, 9, np.ones((7, 11), bool), 12, ("final_partial_run",))
+    add("300x517 0.01 valid", 300, 517, 3, rng.random((300, 517)) < 0.01, 96, ("last_strip", "not_first_run_of_strip", "final_partial_run"))
+    v = np.ones((300, 517), bool)
+    v[40:200] = False
+    add("300x517 rows 40..199 invalid", 300, 517, 4, v, 96, ("after_empty_strip", "last_strip", "not_first_run_of_strip", "final_partial_run"))
+    add("64x64 no valid cell", 64, 64, 5, np.zeros((64, 64), bool), 8, ())
+    for name, cells in (("first cell", [0]), ("last cell", [260 * 253 - 1]), ("last partial run", list(range(256 * 256 + 3, 260 * 253, 7)))):
+        v = np.zeros(260 * 253, bool)
+        v[cells] = True
+        add(f"260x253 only the {name}", 260, 253, 6, v.reshape(260, 253), 16, ("last_strip", "final_partial_run") if cells[0] else ())
+    add("3x30000 0.5 valid", 3, 30000, 7, rng.random((3, 30000)) < 0.5, 64, ("last_strip", "not_first_run_of_strip", "final_partial_run"))
+    for side in (512, 1024):
+        d, m, _ = synthetic.synthetic_tile(side, side, 8 + side, "V1")
+        out.append((f"{side}x{side} V1", d, m, 96, ("last_strip", "not_first_run_of_strip")))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def scalar_tiles():
+    """[(name, depth, valid)] for the per-tile scalars at 300 x 517 (workgroups of the statistics passes make 9 or 10 trips):
+    a tile at -4000 m with centimetre relief (float32 holds it to 0.24 mm; a one-pass variance in float32 loses all of it),
+    minimum and maximum in cells that only the last trip reads, invalid cells holding 1.0e6 / NaN; and a tile whose valid cells
+    lie among its last 300 only."""
+    from _conditioning import deep_tile
+    h, w = 300, 517
+    n = h * w
+    from bathymetric_gnn_amd import synthetic
+    relief = -4000.0 + 0.01 * (deep_tile(h, w, 11, "V0", depth=-4000.0)[0].astype(np.float64) + 4000.0)
+    m = synthetic.synthetic_tile(h, w, 11, "V1")[1].copy()
+    last_trip = (n - 1) // STATS_STRIDE * STATS_STRIDE
+    relief.flat[last_trip + 2500] = relief.min() - 0.5
+    relief.flat[n - 1] = relief.max() + 0.5
+    m.flat[last_trip + 2500] = m.flat[n - 1] = True
+    out = [("holes 1e6", np.where(m, relief, 1.0e6).astype(np.float32), m),
+           ("holes NaN", np.where(m, relief, np.nan).astype(np.float32), m)]
+    tail = np.zeros(n, bool)
+    tail[n - 300:] = np.random.default_rng(12).random(300) < 0.5
+    tail[n - 1] = True
+    tail = tail.reshape(h, w)
+    out.append(("valid among the last 300", np.where(tail, relief, 1.0e6).astype(np.float32), tail))
+    return out
+
+
+def longdouble_std32(depth, valid):
+    """Two-pass population standard deviation of the valid cells in np.longdouble, rounded to float32."""
+    v = np.asarray(depth)[np.asarray(valid, bool)].astype(np.longdouble)
+    mean = v.sum() / np.longdouble(len(v))
+    return np.float32(np.sqrt(((v - mean) ** 2).sum() / np.longdouble(len(v))))
+
+
+@functools.lru_cache(maxsize=None)
+def probe_tiles():
+    """[(name, depth, valid)] of the complexity probe, the largest last."""
+    from bathymetric_gnn_amd import synthetic
+    out = []
+    for h, w, seed in ((16, 16, 31), (17, 33, 32), (37, 19, 33), (3, 700, 34), (700, 3, 35), (1, 40, 36)):
+        out.append((f"{h}x{w}", _field(h, w, seed), np.ones((h, w), bool)))
+    d, m, _ = synthetic.synthetic_tile(48, 40, 37, "V1")
+    d = d.copy()
+    d[~m] = _field(48, 40, 38)[~m]
+    d.flat[np.flatnonzero(~m.ravel())[3]] = np.inf
+    out.append(("48x40 inf in an invalid cell", d, m))
+    d, m, _ = synthetic.synthetic_tile(260, 253, 39, "V1")
+    out.append(("260x253 NaN holes", np.where(m, d, np.float32(np.nan)), m))
+    out.append(("260x253 1e6 holes", d, m))
+    return out
+
+
+PROBE_DENSITY, PROBE_CC = 0.005, 1.0
+PROBE_PARAMS = {"enable_gaussian": False, "enable_spikes": True, "enable_blobs": False, "enable_systematic": False,
+                "complexity_correlation": PROBE_CC, "spike_magnitude_range": (1.0, 5.0)}
+
+
+def complexity_probe(depth, valid, c):
+    """Makes every valid cell of a tile sensitive to its local_std: the injected uniform field is density x (1 + s delta), s = +1 /
+    -1 on a chessboard and density the restatement's map, so that exactly the -1 squares spike.  ``delta`` = c x eps32 x
+    (2 lmax / (lmax - lmin) + 2): a one-ulp float32 move of a cell's local_std, of lmin or of lmax moves the complexity by at most
+    about eps32 x (lmax / (lmax - lmin) + 1) and the density relatively by twice that (2 c eps32 where the complexity is off).
+    The sign and magnitude fields hold +-1 and multiples of 0.5 in [1, 5], so a spike's value is exact in float64.
+    Returns (fields, delta, expected outputs of ``generate`` with these fields, its plan)."""
+    h, w = depth.shape
+    plan = {"sample": 0, "intensity": 1.0, "gaussian_std_factor": 0.0, "spike_density": PROBE_DENSITY, "blobs": [], "artifact": 0,
+            "amplitude_factor": 0.0, "freq_a": 0.0, "freq_b": 0.0, "phase": 0.0}
+    rr, cc = np.indices((h, w))
+    fields = {"uniform": np.ones((h, w)), "sign": np.where((rr // 2 + cc) % 2, 1, -1).astype(np.int8),
+              "magnitude": 1.0 + 0.5 * ((3 * rr + cc) % 9)}
+    with np.errstate(invalid="ignore"):
+        info = generate(depth, valid, plan, PROBE_PARAMS, fields=fields)[4]
+        ls = info["local_std"]
+        lmin, lmax = float(ls.min()), float(ls.max())
+        ratio = lmax / (lmax - lmin) if lmax > lmin else 0.0
+        delta = c * EPS32 * (2.0 * ratio + 2.0)
+        s = np.where((rr + cc) % 2 == 0, 1.0, -1.0)
+        fields["uniform"] = info["density"].astype(np.float64) * (1.0 + s * delta)
+        ref = generate(depth, valid, plan, PROBE_PARAMS, fields=fields)
+    return fields, delta, ref, (s < 0) & valid
+
+
+# (h, w, tile seed of synthetic_tile V1, generator seed): own draws against the restatement, sample 0 each
+OWN_CASES = ((260, 253, 3, 2024), (300, 517, 4, 77), (512, 512, 21, 5), (1024, 1024, 22, 6))
+OWN_BATCH_SEED = 77
+OWN_BATCH_SAMPLES = (1, 2, 3, 0, 4)          # the 300 x 517 tile keeps sample 0: it must come out as it does alone
+
+
+@functools.lru_cache(maxsize=None)
+def own_batch_tiles():
+    """260 x 253, 17 x 16 (272 cells: the next tile starts misaligned), a tile without a valid cell, 300 x 517, 1 x 40."""
+    from bathymetric_gnn_amd import synthetic
+    t = lambda h, w, seed, variant="V1": synthetic.synthetic_tile(h, w, seed, variant)[:2]
+    return [t(260, 253, 3), t(17, 16, 5), (t(64, 64, 1)[0], np.zeros((64, 64), bool)), t(300, 517, 4), t(1, 40, 6, "V0")]
+
+
+def own_reference(depth, valid, plan, params, seed):
+    """``generate`` on a device plan (data/synthetic_noise.py ``draw_plan``) and the bounds of the own-draw rule: noisy_depth
+    c x eps32 x max |noisy|, magnitude c x eps32 (the caller multiplies by c)."""
+    q = dict(plan)
+    q["spike_density"] = float(plan["spike_density_draw"]) * plan["intensity"]
+    q["artifact"] = ARTIFACTS.index(plan["artifact"])
+    ref = generate(depth, valid, q, params, seed=seed)
+    ref[4].setdefault("blob_cells", np.zeros(valid.shape, bool))
+    scale = float(np.abs(ref[0][valid]).max()) if valid.any() else 0.0
+    return ref, scale
