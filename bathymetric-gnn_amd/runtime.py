@@ -294,6 +294,23 @@ FL_MAX_FEATURES = 2 ** 31 - 2
 FL_STATS_BYTES = 24
 FL_STATS_DTYPE = [("valid", "<i8"), ("feature", "<i8"), ("painted", "<i8")]
 
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_tilestore.h declares (training tiles cut from planes in HBM)
+_TILESTORE_SIGNATURES = {
+    "bgnn_tile_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "bgnn_tile_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bgnn_tile_cut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                C.c_double, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t]),
+}
+TILE_VALID_LABEL, TILE_VALID_DEPTH = 0, 1          # BGNN_TILE_VALID_*
+TILE_MAX_PLANES = 4                                # BGNN_TILE_MAX_PLANES
+TILE_BAND_ROWS = 32                                # BGNN_TILE_BAND_ROWS
+TILE_COUNTS = 4                                    # BGNN_TILE_COUNTS: valid, class 0, class 1, class 2
+# bgnn_tile_box (BGNN_TILE_BOX_BYTES = 32)
+TILE_BOX_DTYPE = np.dtype([("row0", "<i8"), ("col0", "<i8"), ("h", "<i4"), ("w", "<i4"), ("dst", "<i8")])
+TILE_BOX_BYTES = TILE_BOX_DTYPE.itemsize
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -304,8 +321,8 @@ class BgnnError(RuntimeError):
 
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
-    include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h and
-    include/bgnn_features.h.  Needs no GPU."""
+    include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
+    include/bgnn_features.h and include/bgnn_tilestore.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -318,7 +335,8 @@ def load_library(path: Optional[str] = None):
         lib = C.CDLL(p)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
                 list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
-                list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()):
+                list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
+                list(_TILESTORE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -12,6 +12,7 @@ and the noise of a synthetic store, a function of ``(seed, epoch, tile)``.  Two 
 ran before, and a resumed run continues the run it was saved from bit for bit."""
 from __future__ import annotations
 
+import ctypes as C
 import dataclasses
 import logging
 from pathlib import Path
@@ -86,6 +87,137 @@ def plan_ground_truth_tiles(labels: np.ndarray, tile_size: int = 512, overlap: i
     return boxes, counts
 
 
+def plan_tile_boxes(height: int, width: int, tile_size: int = 512, overlap: int = 64) -> List[Tuple[int, int, int, int]]:
+    """The candidate boxes of ``plan_ground_truth_tiles`` on a ``height x width`` raster BEFORE its validity test, in the
+    reference's order: the stride grid of full tiles, row-major, then the single far-corner tile when the raster is larger than a
+    tile both ways and either extent is no multiple of the stride.  A raster smaller than a tile in either extent yields no box.
+    Pure host arithmetic: the boxes ``scan_tile_boxes`` counts on the device."""
+    height, width, tile_size = int(height), int(width), int(tile_size)
+    stride = tile_size - int(overlap)
+    if stride <= 0:
+        raise ValueError("Tile size must be larger than overlap")
+    boxes = [(r0, c0, r0 + tile_size, c0 + tile_size)
+             for r0 in range(0, height - tile_size + 1, stride) for c0 in range(0, width - tile_size + 1, stride)]
+    if height > tile_size and width > tile_size and (height % stride != 0 or width % stride != 0):
+        boxes.append((height - tile_size, width - tile_size, height, width))
+    return boxes
+
+
+def keep_ground_truth_boxes(boxes, counts, min_valid_ratio: float = 0.1):
+    """The keep rule of ``plan_ground_truth_tiles`` on scanned counts: ``boxes[i]`` stays when ``valid / (h * w) >=
+    min_valid_ratio`` -- the float64 quotient ``np.sum(valid) / valid.size`` forms, so no tolerance is involved.  ``counts``:
+    ``[n, 4]`` integers (valid, class 0, class 1, class 2) per box.  Returns the kept boxes and the class counts summed over them
+    (overlaps counted as often as they are cut)."""
+    kept: List[Tuple[int, int, int, int]] = []
+    total = {0: 0, 1: 0, 2: 0}
+    for (r0, c0, r1, c1), row in zip(boxes, counts):
+        if int(row[0]) / ((r1 - r0) * (c1 - c0)) >= min_valid_ratio:
+            kept.append((r0, c0, r1, c1))
+            for c in (0, 1, 2):
+                total[c] += int(row[1 + c])
+    return kept, total
+
+
+def _box_table(boxes, dst=None) -> np.ndarray:
+    """``(r0, c0, r1, c1)`` boxes as the ``bgnn_tile_box`` table; ``dst``: the cell offset of every tile (default 0)."""
+    table = np.zeros(len(boxes), dtype=rt.TILE_BOX_DTYPE)
+    if len(boxes):
+        b = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+        table["row0"], table["col0"] = b[:, 0], b[:, 1]
+        extent = np.stack([b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], axis=1)
+        if (np.abs(extent) > np.iinfo(np.int32).max).any():
+            raise ValueError("a tile extent beyond int32")
+        table["h"], table["w"] = extent[:, 0], extent[:, 1]          # (an empty or inverted box stays <= 0: the library refuses it)
+        if dst is not None:
+            table["dst"] = np.asarray(dst, dtype=np.int64)
+    return table
+
+
+def _tile_plane(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.float32) or not t.is_cuda or \
+            not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous [H, W] int32 or float32 tensor on the GPU")
+    return t
+
+
+def scan_tile_boxes(plane: torch.Tensor, boxes, nodata: Optional[float] = None, ctx=None) -> torch.Tensor:
+    """``bgnn_tile_scan`` (include/bgnn_tilestore.h): the ``[n, 4]`` int64 device table of counts (valid, class 0, class 1,
+    class 2) of the ``(r0, c0, r1, c1)`` boxes of an ``[H, W]`` device plane.  An int32 plane is scanned as labels (valid: ``>= 0``),
+    a float32 plane as depths (valid: finite and ``!= nodata``; ``nodata`` None or NaN: finite only; class counts 0).  Asynchronous
+    on the context's stream, ordered against the caller's current stream; the caller's ``.cpu()`` is the synchronisation."""
+    plane = _tile_plane(plane, "plane")
+    dev = plane.device
+    ctx = ctx if ctx is not None else rt.get_context(dev)
+    table = _box_table(boxes)
+    n = len(table)
+    counts = torch.empty((n, rt.TILE_COUNTS), dtype=torch.int64, device=dev)
+    if n == 0:
+        return counts
+    ws_bytes = int(ctx.lib.bgnn_tile_workspace_bytes(n))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    mode = rt.TILE_VALID_LABEL if plane.dtype == torch.int32 else rt.TILE_VALID_DEPTH
+    ctx.begin()
+    rt.check(ctx.lib.bgnn_tile_scan(ctx.handle, rt.ptr(plane), int(plane.shape[0]), int(plane.shape[1]), mode,
+                                    float("nan") if nodata is None else float(nodata), C.c_void_p(table.ctypes.data), n, rt.ptr(ws),
+                                    C.c_size_t(ws_bytes), rt.ptr(counts)))
+    ctx.end()
+    return counts
+
+
+def cut_tile_boxes(planes: Sequence[Optional[torch.Tensor]], stores: Sequence[Optional[torch.Tensor]], boxes, offsets,
+                   mask: Optional[torch.Tensor] = None, mask_plane: int = 0, nodata: Optional[float] = None, ctx=None) -> None:
+    """``bgnn_tile_cut``: the ``(r0, c0, r1, c1)`` boxes of up to four ``[H, W]`` device planes of one shape, written row-major into
+    the flat ``stores`` (one per plane, same dtype, ``None`` beside a ``None`` plane) from cell ``offsets[i]`` on, and into ``mask``
+    (uint8) the validity of ``planes[mask_plane]`` under the predicate of its dtype (see ``scan_tile_boxes``).  One launch."""
+    given = [p for p in planes if p is not None]
+    if not given or len(planes) != len(stores) or len(planes) > rt.TILE_MAX_PLANES:
+        raise ValueError(f"1 to {rt.TILE_MAX_PLANES} planes, a store for each")
+    dev, shape = given[0].device, tuple(given[0].shape)
+    cells = None
+    for i, (p, s) in enumerate(zip(planes, stores)):
+        if (p is None) != (s is None):
+            raise ValueError(f"plane {i} and its store: both or neither")
+        if p is None:
+            continue
+        _tile_plane(p, f"plane {i}")
+        if tuple(p.shape) != shape or p.device != dev:
+            raise ValueError(f"plane {i} has shape {tuple(p.shape)} on {p.device}, plane 0 {shape} on {dev}")
+        if not isinstance(s, torch.Tensor) or s.dtype != p.dtype or s.device != dev or not s.is_contiguous():
+            raise TypeError(f"store {i} must be a contiguous {p.dtype} tensor on {dev}")
+        cells = s.numel() if cells is None else cells
+        if s.numel() != cells:
+            raise ValueError("the stores disagree on the number of cells")
+    mode = rt.TILE_VALID_LABEL
+    if mask is not None:
+        if mask.dtype != torch.uint8 or mask.device != dev or not mask.is_contiguous() or mask.numel() != cells:
+            raise TypeError(f"mask must be a contiguous uint8 tensor of {cells} cells on {dev}")
+        if not 0 <= mask_plane < len(planes) or planes[mask_plane] is None:
+            raise ValueError(f"mask_plane {mask_plane} names no given plane")
+        mode = rt.TILE_VALID_LABEL if planes[mask_plane].dtype == torch.int32 else rt.TILE_VALID_DEPTH
+    table = _box_table(boxes, offsets)
+    n = len(table)
+    if n == 0:
+        return
+    ctx = ctx if ctx is not None else rt.get_context(dev)
+    ws_bytes = int(ctx.lib.bgnn_tile_workspace_bytes(n))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    src = (C.c_void_p * len(planes))(*[None if p is None else p.data_ptr() for p in planes])
+    dst = (C.c_void_p * len(planes))(*[None if s is None else s.data_ptr() for s in stores])
+    ctx.begin()
+    rt.check(ctx.lib.bgnn_tile_cut(ctx.handle, src, dst, len(planes), shape[0], shape[1], rt.ptr(mask), int(mask_plane), mode,
+                                   float("nan") if nodata is None else float(nodata), C.c_void_p(table.ctypes.data), n, int(cells),
+                                   rt.ptr(ws), C.c_size_t(ws_bytes)))
+    ctx.end()
+
+
+def _plane_to_device(plane, dtype: torch.dtype, device) -> torch.Tensor:
+    """A host array (uploaded once) or a tensor as a contiguous ``dtype`` tensor on ``device``."""
+    if isinstance(plane, torch.Tensor):
+        return plane.to(device=device, dtype=dtype).contiguous()
+    npdt = np.int32 if dtype == torch.int32 else np.float32
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(plane).astype(npdt, copy=False))).to(device)
+
+
 def dropout_seed(seed: int, global_step: int) -> int:
     """The dropout seed of training step ``global_step`` (epoch * steps per epoch + step) of a run seeded ``seed``:
     ``(seed mod 2^31) * 2^32 + (global_step mod 2^32)``."""
@@ -96,7 +228,9 @@ class TileStore:
     """The tiles of a training set, flat in HBM with the ``hw`` / ``res`` tables ``GraphBuilder.build_from_device`` takes: the
     device-resident form of the reference's ``BathymetricGraphDataset(cache_tiles=True)`` (clean tiles, noise added per sample)
     and of its ``GroundTruthDataset`` (label / difference / noisy-depth planes).  ``batch`` turns a list of tile indices into the
-    batch's graph and the target dict of ``BathymetricGNNLoss``, without leaving the device."""
+    batch's graph and the target dict of ``BathymetricGNNLoss``, without leaving the device.  ``from_ground_truths`` and
+    ``from_survey`` build the store from planes that already lie in HBM (include/bgnn_tilestore.h: a scan of the candidate boxes, a
+    gather of the kept ones); the other constructors plan on the host."""
 
     def __init__(self, kind: str, hw, res, depth, mask, unc=None, labels=None, difference=None, class_counts=None,
                  graph_builder=None, noise_generator=None, augment: bool = True, seed: int = 0, device=None):
@@ -188,6 +322,127 @@ class TileStore:
         res = np.array([(float(resolution[0]), float(resolution[1]))] * len(boxes), np.float64)
         store = cls("ground_truth", hw, res, flat["depth"], (flat["labels"] >= 0).view(torch.uint8), flat.get("unc"),
                     labels=flat["labels"], difference=flat["difference"], class_counts=counts, device=device, **kw)
+        store.boxes = boxes
+        return store
+
+    @classmethod
+    def from_ground_truths(cls, rasters, tile_size: int = 512, overlap: int = 64, min_valid_ratio: float = 0.1, device=None,
+                           **kw) -> "TileStore":
+        """One ``"ground_truth"`` store from several ground-truth rasters (the reference's ``GroundTruthDataset`` takes a list
+        of them), planned and cut on the device: no plane leaves HBM.  ``rasters``: a sequence whose items are a
+        ``data.GroundTruth`` (its ``training_planes()``, at the resolution ``(abs(transform[1]), abs(transform[5]))``, or
+        ``(1.0, 1.0)`` without a transform) or a tuple ``(labels, difference, noisy_depth, uncertainty_or_None, resolution)`` of
+        device tensors; host arrays are accepted too and uploaded once per plane.  The rasters need not share a shape or a
+        resolution; either all of them have an uncertainty plane or none has.
+
+        Per raster: ``plan_tile_boxes``, one ``bgnn_tile_scan`` of the label plane, one copy of the counts to the host (32 bytes
+        per box: the only synchronisation), ``keep_ground_truth_boxes``, one ``bgnn_tile_cut``.  The store's planes are allocated
+        ONCE for all rasters, after a first pass that scans every raster; the second pass cuts at running offsets.  A raster that
+        yields no tile is skipped with a logged warning; no tile at all raises.
+
+        The store is ``from_ground_truth`` of every raster, concatenated, bit for bit (tiles in raster order and in the reference's
+        scan order inside a raster; the mask is ``labels >= 0``); ``boxes`` lists ``(r0, c0, r1, c1)`` per tile, ``sources`` (int32)
+        the index of its raster in ``rasters``, the class counts are summed over the rasters."""
+        from ..data.ground_truth import GroundTruth
+        device = rt.resolve_device(device)
+        ctx = rt.get_context(device)
+        names = ("labels", "difference", "depth", "unc")
+        scanned = []
+        for k, item in enumerate(rasters):
+            if isinstance(item, GroundTruth):
+                labels, difference, depth, unc = item.training_planes()
+                tr = item.transform
+                resolution = (1.0, 1.0) if tr is None else (abs(tr[1]), abs(tr[5]))
+            else:
+                labels, difference, depth, unc, resolution = item
+            given = [p for p in (labels, difference, depth, unc) if p is not None]
+            if len({isinstance(p, torch.Tensor) for p in given}) != 1:
+                raise TypeError(f"raster {k}: its planes must be all tensors or all host arrays")
+            planes = [_plane_to_device(labels, torch.int32, device), _plane_to_device(difference, torch.float32, device),
+                      _plane_to_device(depth, torch.float32, device), None if unc is None else _plane_to_device(unc, torch.float32, device)]
+            if planes[0].dim() != 2:
+                raise ValueError(f"raster {k}: labels must be a 2-D grid, got shape {tuple(planes[0].shape)}")
+            for name, p in zip(names, planes):
+                if p is not None and tuple(p.shape) != tuple(planes[0].shape):
+                    raise ValueError(f"raster {k}: {name} has shape {tuple(p.shape)}, labels {tuple(planes[0].shape)}")
+            scanned.append({"index": k, "planes": planes, "res": (float(resolution[0]), float(resolution[1]))})
+        if len({r["planes"][3] is None for r in scanned}) > 1:
+            raise ValueError("some rasters have an uncertainty plane and some have none: the graphs would differ in in_channels")
+        for r in scanned:                                # first pass: every raster's scan is queued before any count is read
+            height, width = r["planes"][0].shape
+            r["candidates"] = plan_tile_boxes(height, width, tile_size, overlap)
+            r["counts"] = scan_tile_boxes(r["planes"][0], r["candidates"], ctx=ctx)
+        class_counts = {0: 0, 1: 0, 2: 0}
+        for r in scanned:
+            r["boxes"], counts = keep_ground_truth_boxes(r["candidates"], r["counts"].cpu().numpy(), min_valid_ratio)
+            for c in class_counts:
+                class_counts[c] += counts[c]
+            if not r["boxes"]:
+                logger.warning(f"raster {r['index']} ({tuple(r['planes'][0].shape)}) yields no tile, skipping")
+        boxes = [b for r in scanned for b in r["boxes"]]
+        if not boxes:
+            raise ValueError("the ground-truth rasters yield no tile")
+        hw = np.array([(r1 - r0, c1 - c0) for r0, c0, r1, c1 in boxes], np.int32)
+        offsets = np.concatenate([[0], np.cumsum(hw[:, 0].astype(np.int64) * hw[:, 1])])
+        cells = int(offsets[-1])
+        with_unc = scanned[0]["planes"][3] is not None
+        stores = [torch.empty(cells, dtype=torch.int32, device=device), torch.empty(cells, dtype=torch.float32, device=device),
+                  torch.empty(cells, dtype=torch.float32, device=device),
+                  torch.empty(cells, dtype=torch.float32, device=device) if with_unc else None]
+        mask = torch.empty(cells, dtype=torch.uint8, device=device)
+        first = 0
+        for r in scanned:                                # second pass: one cut per raster at its running offset
+            n = len(r["boxes"])
+            cut_tile_boxes(r["planes"], stores, r["boxes"], offsets[first:first + n], mask=mask, mask_plane=0, ctx=ctx)
+            first += n
+        res = np.array([r["res"] for r in scanned for _ in r["boxes"]], np.float64)
+        store = cls("ground_truth", hw, res, stores[2], mask, stores[3], labels=stores[0], difference=stores[1],
+                    class_counts=class_counts, device=device, **kw)
+        store.boxes = boxes
+        store.sources = np.array([r["index"] for r in scanned for _ in r["boxes"]], np.int32)
+        return store
+
+    @classmethod
+    def from_survey(cls, depth, tile_manager, uncertainty=None, nodata_value: Optional[float] = 1.0e6, resolution=(1.0, 1.0),
+                    device=None, **kw) -> "TileStore":
+        """The device form of ``from_grid``: a ``"synthetic"`` store of the tiles ``tile_manager.iterate_tiles(grid,
+        skip_empty=True)`` yields for ``BathymetricGrid(depth, uncertainty, nodata_value, resolution=resolution)``, without the
+        survey leaving HBM.  ``depth`` / ``uncertainty``: ``[H, W]`` float32 device tensors (host arrays are uploaded once).
+
+        The boxes are ``tile_manager.compute_tile_grid((H, W))`` (ragged at the plane's edges); one ``bgnn_tile_scan`` in depth
+        mode counts the cells that are finite and ``!= nodata_value`` (None or NaN: finite only -- ``BathymetricGrid.valid_mask``);
+        a tile is dropped when ``valid / size < tile_manager.min_valid_ratio`` (the strict ``<`` of ``iterate_tiles``); one
+        ``bgnn_tile_cut`` gathers the rest.
+
+        What ``from_grid`` stores, restated: ``GraphBuilder.upload_tiles`` concatenates each tile's float32 depth AS IT IS --
+        invalid cells keep their value, nodata sentinel, NaN payload and infinities included -- the tile's crop of the grid's valid
+        mask as uint8, and the uncertainty as it is.  So here the depth and uncertainty words are moved untouched and the mask is
+        the predicate on the depth.  The store equals ``from_grid``'s bit for bit: ``hw``, ``res``, ``offsets``, depth, mask,
+        uncertainty, ``uniform``."""
+        device = rt.resolve_device(device)
+        ctx = rt.get_context(device)
+        planes = [_plane_to_device(depth, torch.float32, device),
+                  None if uncertainty is None else _plane_to_device(uncertainty, torch.float32, device)]
+        if planes[0].dim() != 2:
+            raise ValueError(f"depth must be a 2-D grid, got shape {tuple(planes[0].shape)}")
+        if planes[1] is not None and tuple(planes[1].shape) != tuple(planes[0].shape):
+            raise ValueError(f"uncertainty has shape {tuple(planes[1].shape)}, depth {tuple(planes[0].shape)}")
+        _, _, specs = tile_manager.compute_tile_grid(tuple(planes[0].shape))
+        candidates = [(s.row_start, s.col_start, s.row_end, s.col_end) for s in specs]
+        counts = scan_tile_boxes(planes[0], candidates, nodata=nodata_value, ctx=ctx).cpu().numpy()
+        boxes = [b for b, row in zip(candidates, counts)
+                 if not int(row[0]) / ((b[2] - b[0]) * (b[3] - b[1])) < tile_manager.min_valid_ratio]
+        if not boxes:
+            raise ValueError("a TileStore needs at least one tile")
+        hw = np.array([(r1 - r0, c1 - c0) for r0, c0, r1, c1 in boxes], np.int32)
+        offsets = np.concatenate([[0], np.cumsum(hw[:, 0].astype(np.int64) * hw[:, 1])])
+        cells = int(offsets[-1])
+        stores = [torch.empty(cells, dtype=torch.float32, device=device),
+                  None if planes[1] is None else torch.empty(cells, dtype=torch.float32, device=device)]
+        mask = torch.empty(cells, dtype=torch.uint8, device=device)
+        cut_tile_boxes(planes, stores, boxes, offsets[:-1], mask=mask, mask_plane=0, nodata=nodata_value, ctx=ctx)
+        res = np.array([(float(resolution[0]), float(resolution[1]))] * len(boxes), np.float64)
+        store = cls("synthetic", hw, res, stores[0], mask, stores[1], device=device, **kw)
         store.boxes = boxes
         return store
 
