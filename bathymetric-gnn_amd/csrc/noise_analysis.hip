@@ -27,21 +27,14 @@
 //                (integer atomicAdd: order-independent).  Roots are stable here: the merges ended with the previous kernel
 //   ccl_stats    over the global roots (parent[i] == i): count, size sum, maximum, size bins, the top size bits
 //
-// Termination, by construction.  Invariant: parent[i] <= i for every noise cell, at all times.  It holds after initialisation
-// (parent[i] = i, or the tile-local root, the smallest index of the component in the tile, in row-major order both locally and
-// globally), and the only later writes are atomicMin(&parent[a], b) with b < a and, in ccl_flatten, parent[i] = root <= i.
-//   find(x)   follows parent while parent[x] != x: each step strictly lowers x, so it ends after at most x steps whatever other
-//             threads write meanwhile (a stale read only makes it stop at an older ancestor; the atomicMin below detects that).
-//   unite(a, b)   a = find(a), b = find(b); equal: done.  Otherwise, with a > b: old = atomicMin(&parent[a], b).  old == a: a was
-//             still a root and now points at b: done.  Otherwise another thread lowered parent[a] to old < a first; whichever of
-//             old and b stayed in parent[a], the pair (old, b) still has to be united: continue with a = old.  Every iteration
-//             replaces the larger of two non-negative indices by a strictly smaller one, so a + b strictly decreases: the loop ends.
-// No thread waits for another: there is no spin-wait on a flag or a workgroup, no grid-wide barrier and no persistent kernel; a
-// workgroup's progress never depends on another workgroup being scheduled.
+// load_parent / find_root / unite, the invariant parent[i] <= i and the termination argument: union_find.h (shared with
+// review_regions.hip).  No thread waits for another: there is no spin-wait on a flag or a workgroup, no grid-wide barrier and no
+// persistent kernel; a workgroup's progress never depends on another workgroup being scheduled.
 //
 // Compiled with -ffp-contract=off: the float32 rank arithmetic of numpy's percentile and the float64 squares round as written.
 #include "bgnn_internal.h"
 #include "radix_select.h"
+#include "union_find.h"
 #include "../../include/bgnn_analysis.h"
 
 namespace bgnn {
@@ -363,33 +356,7 @@ __global__ __launch_bounds__(NA_THREADS) void na_rough(const float *__restrict__
 }
 
 // ---- 3. clusters -------------------------------------------------------------------------------------------------------------
-// GLOBAL: the parent array is in global memory and other workgroups lower it meanwhile: device-scope loads.  Else: LDS.
-template <bool GLOBAL>
-__device__ __forceinline__ int32_t load_parent(const int32_t *p, int32_t x) {
-  return GLOBAL ? __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                : __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-template <bool GLOBAL>
-__device__ __forceinline__ int32_t find_root(const int32_t *p, int32_t x) {
-  for (;;) {                                                    // parent[x] <= x: every step strictly lowers x
-    const int32_t q = load_parent<GLOBAL>(p, x);
-    if (q == x) return x;
-    x = q;
-  }
-}
-template <bool GLOBAL>
-__device__ __forceinline__ void unite(int32_t *p, int32_t a, int32_t b) {
-  for (;;) {                                                    // a + b strictly decreases: see the head of the file
-    a = find_root<GLOBAL>(p, a);
-    b = find_root<GLOBAL>(p, b);
-    if (a == b) return;
-    if (a < b) { const int32_t s = a; a = b; b = s; }
-    const int32_t old = atomicMin(p + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
+// load_parent<GLOBAL> / find_root<GLOBAL> / unite<GLOBAL>: union_find.h (GLOBAL: the parent array in global memory; else LDS)
 __global__ __launch_bounds__(NA_THREADS) void ccl_local(const int32_t *__restrict__ labels, TileGrid tg, int32_t *__restrict__ parent,
                                                         int32_t *__restrict__ size, int32_t *__restrict__ col_noise,
                                                         int32_t *__restrict__ col_valid) {

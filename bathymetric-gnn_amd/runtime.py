@@ -279,6 +279,22 @@ NA_DTYPE = [("valid", "<i8"), ("noise", "<i8"), ("seafloor", "<i8"), ("positive"
             ("rough_count", "<i8", (2,)), ("rough_sum", "<f8", (2,)), ("rough_mid", "<f8", (4,))]
 
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_review.h declares (low-confidence regions for review)
+_REVIEW_SIGNATURES = {
+    "bgnn_review_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "bgnn_review_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+}
+# BGNN_RV_*: the limit, the counts and the record of a kept region (bgnn_review_record)
+RV_MAX_CELLS = 2 ** 31 - 1
+RV_COUNTS = 4
+RV_COUNT_NAMES = ("uncertain_cells", "regions", "kept_regions", "kept_cells")
+RV_FIXED_BYTES = 81920
+RV_RECORD_DTYPE = np.dtype([("first", "<i8"), ("size", "<i8"), ("min_row", "<i4"), ("max_row", "<i4"), ("min_col", "<i4"),
+                            ("max_col", "<i4"), ("conf_sum", "<u8")])
+RV_RECORD_BYTES = RV_RECORD_DTYPE.itemsize
+
+
 # symbol -> (restype, argtypes); every symbol include/bgnn_features.h declares (feature labels from charted objects)
 _FEATURES_SIGNATURES = {
     "bgnn_feature_labels_plan_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64]),
@@ -322,7 +338,7 @@ class BgnnError(RuntimeError):
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
-    include/bgnn_features.h and include/bgnn_tilestore.h.  Needs no GPU."""
+    include/bgnn_features.h, include/bgnn_tilestore.h and include/bgnn_review.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -336,7 +352,7 @@ def load_library(path: Optional[str] = None):
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
                 list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
                 list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
-                list(_TILESTORE_SIGNATURES.items()):
+                list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,275 @@
+"""The review-region export on the device (include/bgnn_review.h, ``export_review_regions``) against the numpy / scipy restatement of
+the reference's ``scripts/export_for_review.py`` (_review_cpu.fast_regions) and against the fixture the reference's own code wrote.
+Every case: regions equal in count, order, ``size`` and ``bounds``; ``|mean_confidence - float64 mean| <= 2^-32`` (the fixed-point
+format: _review_cpu.MEAN_ATOL); the mask equal cell for cell; the four counts equal.  The tile of the labelling is 16 x 64: the shapes
+sit on it, one past it, and far from any multiple of it; the chains run through every tile."""
+import numpy as np
+import pytest
+import torch
+
+from _review_cpu import MEAN_ATOL, check_device_result, fast_regions, float32_mean_bound, load_fixture, same_regions
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+CASES = load_fixture()
+
+
+def export(conf, low=0.4, high=0.7, min_region_size=1, device=None, classification=None, **kw):
+    from bathymetric_gnn_amd.data import export_review_regions
+    return export_review_regions(classification, conf, low, high, min_region_size, device=device, **kw)
+
+
+def run(conf, low, high, min_region_size, device, **kw):
+    result = export(conf, low, high, min_region_size, device, **kw)
+    return result, check_device_result(result, conf, low, high, min_region_size)
+
+
+def field_from_mask(mask, rng):
+    """A confidence plane whose uncertain cells under [0.4, 0.7] are exactly ``mask``: values inside the band there, below or above
+    it elsewhere."""
+    inside = rng.uniform(0.41, 0.69, mask.shape)
+    outside = np.where(rng.random(mask.shape) < 0.5, rng.uniform(0.0, 0.39, mask.shape), rng.uniform(0.71, 1.0, mask.shape))
+    return np.where(mask, inside, outside).astype(F32)
+
+
+def smooth_field(rng, h, w, waves=4, nan_rate=0.005):
+    rr, cc = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    z = np.zeros((h, w))
+    for _ in range(waves):
+        fr, fc = rng.uniform(0.004, 0.05, 2) * rng.choice([-1, 1], 2)
+        z += rng.uniform(0.5, 1.5) * np.sin(2 * np.pi * (fr * rr + fc * cc) + rng.uniform(0, 2 * np.pi))
+    conf = (1.0 / (1.0 + np.exp(-z))).astype(F32)
+    conf[rng.random((h, w)) < nan_rate] = np.nan
+    return conf
+
+
+def serpentine(h, w):
+    m = np.zeros((h, w), bool)
+    m[0::2, :] = True
+    m[1::4, w - 1] = True
+    m[3::4, 0] = True
+    return m
+
+
+def comb(h, w):
+    m = np.zeros((h, w), bool)
+    m[:, 0::2] = True
+    m[h - 1, :] = True
+    return m
+
+
+def spiral(h, w):
+    """A one-cell-wide path from the corner inwards, one cell of gap between its turns."""
+    m = np.zeros((h, w), bool)
+    r = c = 0
+    dr, dc = 0, 1
+    m[0, 0] = True
+    while True:
+        for _ in range(2):
+            nr, nc, fr, fc = r + dr, c + dc, r + 2 * dr, c + 2 * dc
+            if 0 <= nr < h and 0 <= nc < w and not m[nr, nc] and not (0 <= fr < h and 0 <= fc < w and m[fr, fc]):
+                r, c = nr, nc
+                m[r, c] = True
+                break
+            dr, dc = dc, -dr
+        else:
+            return m
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (1, 200), (200, 1), (16, 64), (17, 65), (37, 150)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_smallest_shapes(shape, gpu_device):
+    rng = np.random.default_rng([20240903, *shape])
+    conf = rng.uniform(0.2, 0.9, shape).astype(F32)             # 60 % uncertain: past the site-percolation threshold, ragged regions
+    for min_size in (1, 4):
+        _, (want, _, counts) = run(conf, 0.4, 0.7, min_size, gpu_device)
+    assert counts["uncertain_cells"] > 0 or shape == (1, 1)
+    full = np.full(shape, 0.5, F32)                             # one region across every tile border of the shape
+    result, _ = run(full, 0.4, 0.7, 1, gpu_device)
+    assert [r["size"] for r in result.regions] == [shape[0] * shape[1]]
+
+
+@pytest.mark.parametrize("name,mask", [("serpentine_100x400", serpentine(100, 400)), ("comb_130x67", comb(130, 67)),
+                                       ("spiral_97x131", spiral(97, 131)), ("spiral_64x256", spiral(64, 256))],
+                         ids=lambda v: v if isinstance(v, str) else "")
+def test_long_union_chains(name, mask, gpu_device):
+    conf = field_from_mask(mask, np.random.default_rng(20240904))
+    result, (want, _, counts) = run(conf, 0.4, 0.7, 100, gpu_device)
+    assert counts["regions"] == 1 and len(result.regions) == 1 and result.regions[0]["size"] == int(mask.sum()) > 2000
+    if name.startswith("serpentine"):
+        assert result.regions[0]["bounds"] == {"min_row": 0, "max_row": 99, "min_col": 0, "max_col": 399}
+
+
+def test_checkerboard_overflows_the_first_table(gpu_device):
+    """Every cell its own region: 8192 records where the first table holds 7 -- the true count comes back and the call runs again."""
+    from bathymetric_gnn_amd.data.review_regions import review_regions_build, split_result
+    rr, cc = np.meshgrid(np.arange(64), np.arange(256), indexing="ij")
+    conf = field_from_mask((rr + cc) % 2 == 0, np.random.default_rng(20240905))
+    result, (want, _, counts) = run(conf, 0.4, 0.7, 1, gpu_device, first_capacity=7)
+    assert counts["kept_regions"] == len(result.regions) == 8192 and counts["kept_cells"] == 8192
+    # the short table itself: its seven records are the first seven, the counts are the true ones, nothing is written past it
+    t = torch.from_numpy(conf).to(gpu_device)
+    out = review_regions_build(t, F32(0.4), F32(0.7), 1, 7, None)
+    guard = review_regions_build(t, F32(0.4), F32(0.7), 1, 0, None).cpu().numpy()
+    short_counts, short = split_result(out.cpu().numpy())
+    assert short_counts == counts and split_result(guard)[0] == counts and len(guard) == 4
+    assert short.tobytes() == result.records[:7].tobytes()
+    # two cells and more: nothing
+    result, _ = run(conf, 0.4, 0.7, 2, gpu_device)
+    assert result.regions == [] and not result.review_mask.any().item() and result.counts["regions"] == 8192
+
+
+def test_diagonal_contact_does_not_join(gpu_device):
+    mask = np.zeros((40, 140), bool)
+    for k in range(6):                                          # blocks of 5 x 20 down a diagonal, across both tile borders
+        mask[5 * k:5 * k + 5, 20 * k:20 * k + 20] = True
+    result, (want, _, counts) = run(field_from_mask(mask, np.random.default_rng(20240906)), 0.4, 0.7, 100, gpu_device)
+    assert [r["size"] for r in result.regions] == [100] * 6 and counts["regions"] == 6
+
+
+def test_nested_boxes(gpu_device):
+    mask = np.zeros((50, 150), bool)
+    mask[5:45, 10:140] = True
+    mask[8:42, 13:137] = False                                  # a ring three cells wide ...
+    mask[20:30, 60:90] = True                                   # ... around a separate blob
+    result, _ = run(field_from_mask(mask, np.random.default_rng(20240907)), 0.4, 0.7, 100, gpu_device)
+    assert [r["bounds"] for r in result.regions] == [{"min_row": 5, "max_row": 44, "min_col": 10, "max_col": 139},
+                                                     {"min_row": 20, "max_row": 29, "min_col": 60, "max_col": 89}]
+
+
+def test_order_is_by_first_cell_not_by_column(gpu_device):
+    mask = np.zeros((40, 100), bool)
+    mask[2:6, 70:90] = True                                     # first cell (2, 70)
+    mask[3:30, 5:9] = True                                      # first cell (3, 5): later in raster order, further left
+    mask[3, 95:100] = True                                      # first cell (3, 95): the last of the three
+    result, _ = run(field_from_mask(mask, np.random.default_rng(20240908)), 0.4, 0.7, 5, gpu_device)
+    assert [(r["id"], r["bounds"]["min_row"], r["bounds"]["min_col"]) for r in result.regions] == [(1, 2, 70), (2, 3, 5), (3, 3, 95)]
+    assert [int(f) for f in result.records["first"]] == [2 * 100 + 70, 3 * 100 + 5, 3 * 100 + 95]
+
+
+def test_all_or_nothing(gpu_device):
+    rng = np.random.default_rng(20240909)
+    result, _ = run(rng.uniform(0.41, 0.69, (256, 256)).astype(F32), 0.4, 0.7, 100, gpu_device)
+    assert len(result.regions) == 1 and result.regions[0]["size"] == 65536
+    assert result.regions[0]["bounds"] == {"min_row": 0, "max_row": 255, "min_col": 0, "max_col": 255}
+    result, _ = run(rng.uniform(0.75, 1.0, (256, 256)).astype(F32), 0.4, 0.7, 1, gpu_device)
+    assert result.regions == [] and result.counts == {"uncertain_cells": 0, "regions": 0, "kept_regions": 0, "kept_cells": 0}
+
+
+def test_values_on_and_off_the_bounds(gpu_device):
+    low, high = F32(0.4), F32(0.7)                              # what the Python floats 0.4 / 0.7 round to
+    conf = np.full((20, 70), 0.9, F32)
+    row = [low, high, np.nextafter(low, F32(0)), np.nextafter(high, F32(1)), np.nan, np.inf, -np.inf, np.nextafter(low, F32(1)),
+           np.nextafter(high, F32(0)), F32(0.0), F32(1.0)]
+    for k, v in enumerate(row):
+        conf[3, 2 * k] = v                                      # isolated cells
+        conf[10:13, 5 * k:5 * k + 3] = v                        # 3 x 3 blocks
+    result, (want, mask, counts) = run(conf, 0.4, 0.7, 1, gpu_device)
+    included = [0, 1, 7, 8]
+    assert counts["uncertain_cells"] == 10 * len(included) and len(result.regions) == 2 * len(included)
+    assert [r["bounds"]["min_col"] for r in result.regions[:4]] == [2 * k for k in included]
+    # the whole unit interval, both ends included; NaN and the infinities stay out
+    result, (_, mask, _) = run(conf, 0.0, 1.0, 1, gpu_device)
+    assert int(mask.sum()) == conf.size - 3 * 10
+
+
+def test_size_threshold(gpu_device):
+    mask = np.zeros((30, 140), bool)
+    mask[2:12, 3:13] = True                                     # 100 cells
+    mask[2:12, 60:70] = True
+    mask[11, 69] = False                                        # 99 cells, across a tile border
+    mask[20:25, 100:120] = True
+    mask[25, 100] = True                                        # 101 cells
+    result, _ = run(field_from_mask(mask, np.random.default_rng(20240910)), 0.4, 0.7, 100, gpu_device)
+    assert [r["size"] for r in result.regions] == [100, 101] and result.counts["regions"] == 3
+
+
+@pytest.mark.parametrize("seed", range(3))
+def test_random_smooth_fields(seed, gpu_device):
+    conf = smooth_field(np.random.default_rng([20240911, seed]), 300, 500)
+    result, (want, _, counts) = run(conf, 0.4, 0.7, 100, gpu_device)
+    assert counts["kept_regions"] >= 2
+    run(conf, 0.45, 0.5, 3, gpu_device)
+
+
+def test_random_smooth_field_1024(gpu_device):
+    conf = smooth_field(np.random.default_rng(20240912), 1024, 1024, waves=6)
+    result, (want, _, counts) = run(conf, 0.4, 0.7, 100, gpu_device)
+    assert counts["kept_regions"] >= 5 and max(r["size"] for r in want) > 16 * 64 * 8
+
+
+@pytest.mark.parametrize("density", [0.3, 0.5, 0.593])
+def test_random_masks(density, gpu_device):
+    """Scattered cells up to the site-percolation threshold on 300 x 517: hundreds of tile-local roots in every 4096 cells (more than
+    one round of the flatten kernel's list), waves that see many roots at once, ragged regions across every tile border."""
+    rng = np.random.default_rng([20240916, int(density * 1000)])
+    conf = field_from_mask(rng.random((300, 517)) < density, rng)
+    for min_size in (1, 20):
+        _, (_, _, counts) = run(conf, 0.4, 0.7, min_size, gpu_device)
+    assert counts["regions"] > 10 * counts["kept_regions"] > 0
+
+
+def speckled_field(rng, h, w):
+    """A smooth field with 2 % of the cells set into the band: thousands of regions of one to a few cells beside the large ones."""
+    conf = smooth_field(rng, h, w)
+    return np.where(rng.random((h, w)) < 0.02, rng.uniform(0.41, 0.69, (h, w)), conf).astype(F32)
+
+
+@pytest.mark.parametrize("shape", [(2, 131073), (1030, 2049)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_past_one_grid(shape, gpu_device):
+    """2 x 131073: 2049 tiles, one workgroup of the 2048 labels a second tile.  1030 x 2049: 2145 tiles and 2061 steps of 1024 cells,
+    so the ranges of the ordered compaction are two steps long and records from both steps of a range follow each other."""
+    conf = speckled_field(np.random.default_rng([20240915, *shape]), *shape)
+    result, (want, _, counts) = run(conf, 0.4, 0.7, 1, gpu_device)
+    assert counts["kept_regions"] == counts["regions"] > 5000
+    result, (want, _, counts) = run(conf, 0.4, 0.7, 2, gpu_device)
+    assert counts["regions"] > counts["kept_regions"] > 500
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_golden_fixture(name, gpu_device):
+    c = CASES[name]
+    result, _ = run(c["confidence"], c["low"], c["high"], c["min_region_size"], gpu_device, classification=c["classification"])
+    same_regions(result.regions, c["regions"])
+    assert np.array_equal(result.review_mask.cpu().numpy(), c["review_mask"].astype(F32))
+    for got, ref in zip(result.regions, c["regions"]):          # the reference's float32 np.mean against the exact mean
+        assert abs(got["mean_confidence"] - ref["mean_confidence"]) <= float32_mean_bound(got["size"], got["mean_confidence"]) + MEAN_ATOL
+    mask, conf, cls = result.bands()
+    assert np.array_equal(mask, c["review_mask"].astype(F32)) and mask.dtype == F32
+    assert np.array_equal(conf, c["confidence"], equal_nan=True) and np.array_equal(cls, c["classification"], equal_nan=True)
+
+
+def test_two_calls_give_equal_bits(gpu_device):
+    conf = torch.from_numpy(smooth_field(np.random.default_rng(20240913), 300, 517)).to(gpu_device)
+    a, b = export(conf, 0.4, 0.7, 10), export(conf, 0.4, 0.7, 10)
+    assert len(a.regions) > 3 and a.records.tobytes() == b.records.tobytes() and a.counts == b.counts
+    assert a.review_mask.data_ptr() != b.review_mask.data_ptr() and torch.equal(a.review_mask, b.review_mask)
+    assert a.regions == b.regions
+
+
+def test_host_arrays_device_tensors_and_a_builder_agree(gpu_device):
+    from types import SimpleNamespace
+    from bathymetric_gnn_amd.data import RefinementGrid, SidecarBuilder, export_review_regions
+    h, w = 90, 210
+    rng = np.random.default_rng(20240914)
+    conf = smooth_field(rng, h, w)
+    cls = rng.integers(0, 3, (h, w)).astype(F32)
+    host = export_review_regions(cls, conf, 0.4, 0.7, 10, device=gpu_device)
+    check_device_result(host, conf, 0.4, 0.7, 10)
+    t_conf, t_cls = torch.from_numpy(conf).to(gpu_device), torch.from_numpy(cls).to(gpu_device)
+    dev = export_review_regions(t_cls, t_conf, 0.4, 0.7, 10)
+    assert dev.confidence.data_ptr() == t_conf.data_ptr() and dev.classification is t_cls        # used where they lie
+    # one refinement grid that covers the raster cell for cell (refinement row 0 is the southern one)
+    sb = SidecarBuilder.from_georef(SimpleNamespace(base_shape=(1, 1)), (h, w), (0.0, 1.0, 0.0, float(h), 0.0, -1.0))
+    grid = RefinementGrid(base_row=0, base_col=0, depth=np.zeros((h, w), F32), uncertainty=np.zeros((h, w), F32), resolution=(1.0, 1.0),
+                          dimensions=(h, w), sw_corner=(0.0, 0.0), start_index=0)
+    sb.add_refinement_results(grid, cls[::-1], conf[::-1], np.zeros((h, w), F32))
+    assert np.array_equal(sb.confidence, conf, equal_nan=True)
+    built = export_review_regions(sb, confidence_low=0.4, confidence_high=0.7, min_region_size=10, device=gpu_device)
+    assert len(host.regions) >= 3
+    for other in (dev, built):
+        assert other.records.tobytes() == host.records.tobytes() and other.counts == host.counts and other.regions == host.regions
+        assert torch.equal(other.review_mask, host.review_mask)
+        for a, b in zip(other.bands(), host.bands()):
+            assert np.array_equal(a, b, equal_nan=True)
+    # the defaults are the reference's
+    assert export_review_regions(cls, conf, device=gpu_device).regions == export_review_regions(cls, conf, 0.4, 0.7, 100, device=gpu_device).regions
