@@ -1,5 +1,5 @@
 """Mirror of the reference's ``data`` package for the hot path: graph construction, tiling, synthetic training
-noise, ground truth from a clean / noisy survey pair, feature labels from charted objects, low-confidence regions for review and the ``BathymetricGrid`` container (file-format I/O -- GDAL / h5py -- is outside the path; VR BAGs enter as their two HDF5 arrays)."""
+noise, ground truth from a clean / noisy survey pair, feature labels from charted objects and from the slope, low-confidence regions for review and the ``BathymetricGrid`` container (file-format I/O -- GDAL / h5py -- is outside the path; VR BAGs enter as their two HDF5 arrays)."""
 from .graph_construction import GraphBuilder, GraphData, Data
 from .grid import BathymetricGrid
 from .tiling import Tile, TileSpec, TileManager, TileMerger
@@ -10,6 +10,7 @@ from .noise_analysis import analyze_noise_patterns, print_analysis
 from .feature_labels import (FEATURE_CLASSES, FeatureLabels, S57Feature, create_feature_labels, feature_pixel_table, feature_plan,
                              rasterize_features)
 from .review_regions import ReviewRegions, export_review_regions
+from .slope_features import add_feature_labels, create_feature_mask_from_slope, slope_cut, wreck_pixel_table
 
 __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "TileSpec", "TileManager", "TileMerger",
            "RefinementGrid", "VRBagHandler", "VRBagWriter", "SRBagHandler", "SRBagWriter", "SidecarBuilder", "detect_bag_type",
@@ -17,4 +18,5 @@ __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "Tile
            "Alignment", "GroundTruth", "align_survey_pair", "compute_ground_truth", "ground_truth_stats",
            "analyze_noise_patterns", "print_analysis",
            "FEATURE_CLASSES", "FeatureLabels", "S57Feature", "create_feature_labels", "feature_pixel_table", "feature_plan",
-           "rasterize_features", "ReviewRegions", "export_review_regions"]
+           "rasterize_features", "ReviewRegions", "export_review_regions",
+           "add_feature_labels", "create_feature_mask_from_slope", "slope_cut", "wreck_pixel_table"]

@@ -177,6 +177,15 @@ class FeatureLabels:
     applied_features: int
     stats_block: torch.Tensor = None      # int64 [3] holding the BGNN_FL_STATS_BYTES of the block
     _host_stats: Any = None
+    slope_block: torch.Tensor = None      # set by slope_features.add_feature_labels: int64 [6], runtime.SL_STATS_NAMES
+
+    def slope_stats(self) -> Dict[str, int]:
+        """The counts of the slope step of ``add_feature_labels``: valid cells, steep cells, clusters, kept clusters, their cells
+        and the cells labelled 1 from the slope (the reference's "Slope-based features").  Synchronises."""
+        if self.slope_block is None:
+            raise ValueError("no slope step: these labels do not come from add_feature_labels")
+        from .slope_features import slope_stats
+        return slope_stats(self.slope_block)
 
     def stats(self) -> Dict[str, int]:
         """Applied features, cells labelled 1 (the reference's "Feature cells"), valid cells, painted cells.  The first call

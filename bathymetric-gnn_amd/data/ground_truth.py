@@ -122,6 +122,7 @@ class GroundTruth:
     _host_block: Any = None
     applied_features: Optional[int] = None          # set by with_features: the features that were applied ...
     feature_block: Optional[torch.Tensor] = None    # ... and the statistics block of that call (int64 [3], runtime.FL_STATS_DTYPE)
+    slope_block: Optional[torch.Tensor] = None      # set by with_slope_features: int64 [6], runtime.SL_STATS_NAMES
 
     def block(self):
         """The statistics block on the host (``runtime.GT_STATS_DTYPE``).  The first call synchronises; later ones do not."""
@@ -173,6 +174,26 @@ class GroundTruth:
             raise ValueError("no features were applied: this ground truth does not come from with_features")
         from .feature_labels import feature_stats
         return feature_stats(self.feature_block, self.applied_features)
+
+    def with_slope_features(self, slope_threshold: float = 15.0, min_cluster_size: int = 100,
+                            source: str = "clean_depth") -> "GroundTruth":
+        """This ground truth with steep terrain painted over its seafloor (``slope_features``, overlay mode): the slope comes from
+        the depth plane named by ``source`` (``"clean_depth"`` or ``"noisy_depth"``); a cell labelled 0 in a cluster of at least
+        ``min_cluster_size`` steep cells becomes class 1; noise (2) and no data (-1) stay what they are.  Only ``labels`` is new,
+        the other planes are shared, not copied.  The counts come from ``slope_stats()``."""
+        from .slope_features import slope_cut, slope_features_build
+        if source not in ("clean_depth", "noisy_depth"):
+            raise ValueError(f"source {source!r}: 'clean_depth' or 'noisy_depth' expected")
+        labels, _, block = slope_features_build(getattr(self, source), slope_cut(slope_threshold), min_cluster_size,
+                                                base_labels=self.labels, want_mask=False)
+        return dataclasses.replace(self, labels=labels, slope_block=block)
+
+    def slope_stats(self) -> Dict[str, int]:
+        """The counts of ``with_slope_features`` by name (``runtime.SL_STATS_NAMES``; synchronises)."""
+        if self.slope_block is None:
+            raise ValueError("no slope step: this ground truth does not come from with_slope_features")
+        from .slope_features import slope_stats
+        return slope_stats(self.slope_block)
 
     def analyze(self, **kw) -> Dict[str, Any]:
         """The reference's noise pattern analysis of this ground truth (``noise_analysis.analyze_noise_patterns``)."""

@@ -311,6 +311,19 @@ FL_STATS_BYTES = 24
 FL_STATS_DTYPE = [("valid", "<i8"), ("feature", "<i8"), ("painted", "<i8")]
 
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_slope.h declares (slope-based feature labels)
+_SLOPE_SIGNATURES = {
+    "bgnn_slope_features_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "bgnn_slope_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_float, C.c_int64,
+                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+# BGNN_SL_*: the limit and the statistics block of a slope-feature call
+SL_MAX_CELLS = 2 ** 31 - 1
+SL_STATS = 6
+SL_STATS_BYTES = 48
+SL_STATS_NAMES = ("valid_cells", "steep_cells", "clusters", "kept_clusters", "kept_cells", "slope_feature_cells")
+
+
 # symbol -> (restype, argtypes); every symbol include/bgnn_tilestore.h declares (training tiles cut from planes in HBM)
 _TILESTORE_SIGNATURES = {
     "bgnn_tile_workspace_bytes": (C.c_size_t, [C.c_int64]),
@@ -338,7 +351,7 @@ class BgnnError(RuntimeError):
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
-    include/bgnn_features.h, include/bgnn_tilestore.h and include/bgnn_review.h.  Needs no GPU."""
+    include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h and include/bgnn_slope.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -352,7 +365,7 @@ def load_library(path: Optional[str] = None):
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
                 list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
                 list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
-                list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()):
+                list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
