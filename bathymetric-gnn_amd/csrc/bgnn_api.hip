@@ -277,7 +277,7 @@ static int *option_slot(bgnn_ctx *ctx, const char *name) {
   BgnnOpts &o = ctx->opts;
   struct { const char *n; int *p; } tab[] = {
       {"matrix_path", &o.matrix_path}, {"fused", &o.fused}, {"fold_extractor", &o.fold_extractor}, {"ragged_atlas", &o.ragged_atlas}, {"features_tiled", &o.features_tiled}, {"fused_front", &o.fused_front}, {"bf16_two_phase", &o.bf16_two_phase}, {"bf16_layer0_af", &o.bf16_layer0_af}, {"stats_narrow", &o.stats_narrow},
-      {"diag_mask", &o.diag_mask}, {"diag_stamps", &o.diag_stamps}, {"gemm_diag", &o.gemm_diag}, {"gemm_pair_major", &o.gemm_pair_major}};
+      {"diag_mask", &o.diag_mask}, {"diag_stamps", &o.diag_stamps}, {"gemm_diag", &o.gemm_diag}, {"gemm_pair_major", &o.gemm_pair_major}, {"fused_light_form", &o.fused_light_form}};
   for (auto &t : tab) if (strcmp(t.n, name) == 0) return t.p;
   return nullptr;
 }

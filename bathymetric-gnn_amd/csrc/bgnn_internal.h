@@ -83,6 +83,8 @@ struct BgnnOpts {
   int gemm_diag = 0;
   int gemm_pair_major = 1;   // exact-f32 lin_0 GEMM with the extractor in front: tile-pair-major MFMA order, the epilogue of pair p (bias, attention
                              // dots, transposed row stores) issued between the MFMAs of pair p + 1 (0: tile-major, epilogue after; bit-identical)
+  int fused_light_form = 1;  // exact-f32 fused GAT launches with a narrow next stage (256 -> 64, heads, ...): half-slab image and head-pair
+                             // coefficient table, four workgroups per CU (0: full-slab instances, three per CU; bit-identical)
 };
 
 // Diagnostics (phase ablations, cycle stamps) are compiled in only with -DBGNN_DIAG=1 (python __graft_entry__.py --diag

@@ -450,11 +450,18 @@ __device__ __forceinline__ void agg_blocks(f32x16 &d, uint32_t tr0, uint32_t tr1
   }
 }
 
-template <int HC, int C, int K, int NT, int EPI, int SP>
+template <int HC, int C, int K, int NT, int EPI, int SP, int LF = 0>
 struct FusedLds {       // LDS budget of one workgroup, in floats (kernel and launcher agree through this)
   static constexpr int H = HC / C, NC = NT * 32, HR = FusedGeom<K>::HR;
   static constexpr int XB = SP == 3 ? 2 : 4;             // bytes per stored activation
-  static constexpr int SLAB1 = HR * 32 * XB / 4;         // one slab image: [HR][32 channels]
+  // LF ("light form", exact GAT instances with a narrow next stage; context option fused_light_form): the slab image holds HALF a
+  // slab -- [HR][16 channels], 64-byte rows -- and the coefficient table the heads of one head PAIR, so that four workgroups fit a CU
+  // (<= 40 KB of LDS and <= 128 VGPRs each).  See the half-step loop in the kernel.
+  static constexpr bool HS = LF != 0;
+  static_assert(!HS || (SP == 0 && K <= 8 && NT <= 3), "light form: exact f32, halo of one cell, narrow next stage");
+  static constexpr int AW = HS && H > 2 ? 2 : H;         // heads whose coefficients the table holds at a time
+  static_assert(H <= 2 * AW, "light form: two head pairs at the most");
+  static constexpr int SLAB1 = HS ? HR * 16 : HR * 32 * XB / 4;   // one slab image: [HR][32 channels] (HS: [HR][16])
   // bf16 storage, 256 -> 256 instance (two workgroups per CU whatever the LDS, its 128 accumulator registers decide): the slab image is
   // DOUBLE-BUFFERED -- slab s + 1 is requested as soon as slab s is visible, a whole slab period ahead, instead of after slab s has
   // been gathered (half a period ahead: with no matrix work to hide under, ~17 % of that instance's lifetime was spent waiting
@@ -487,7 +494,7 @@ struct FusedLds {       // LDS budget of one workgroup, in floats (kernel and la
   static constexpr int RSZ = RA > RB ? RA : RB;
   // ODD pitch (in dwords): the gather reads one coefficient per cell with ds_read_b32, whose 32-lane groups bank on (a / 4) mod 32 --
   // with the round-2 pitch of 36 dwords the 32 cells of a group fell on 8 banks (4-way conflict on every coefficient read)
-  static constexpr int APITCH = (H * (K + 1)) | 1;
+  static constexpr int APITCH = (AW * (K + 1)) | 1;
   // attention coefficients: [128 cells][APITCH] f32 (sparse, every head); bf16 storage path: the CURRENT head's coefficients as
   // four wave-private dense [32 cells][window rows] bf16 matrices (the aggregation's MFMA B operand) -- see AggWindow
   static constexpr int ALPHA = SP == 3 ? 4 * 32 * AggWindow<K>::PITCH / 4 : 128 * APITCH;
@@ -504,7 +511,7 @@ struct FusedLds {       // LDS budget of one workgroup, in floats (kernel and la
   //  more than the 170 registers a third workgroup leaves (46 spills, and a spill reload shares vmcnt with the slab DMAs): two
   //  workgroups per CU.  The bf16 instance has half the slab pieces and stays at three: measured 1.08 ms against 1.27 ms at two.)
   static constexpr bool WIDE_PHASE_A = K == 16 && EPI == EPI_HEADS && SP == 0;
-  static constexpr int PER_CU = FLOATS * 4 * 3 <= 160 * 1024 && NT <= 3 && !WIDE_PHASE_A ? 3 : FLOATS * 4 * 2 <= 160 * 1024 ? 2 : 1;
+  static constexpr int PER_CU = HS && FLOATS * 4 * 4 <= 160 * 1024 ? 4 : FLOATS * 4 * 3 <= 160 * 1024 && NT <= 3 && !WIDE_PHASE_A ? 3 : FLOATS * 4 * 2 <= 160 * 1024 ? 2 : 1;
 };
 
 // AGG (exact path, EPI_NEXT only): what phase A puts into the coefficient table, and what the epilogue does with the product --
@@ -515,11 +522,12 @@ struct FusedLds {       // LDS budget of one workgroup, in floats (kernel and la
 //   3  GINConv (eps = 0): 1 on every in-edge, 1 on the node itself (2 with an explicit self loop)
 // and for 1 .. 3 the layer is aggregate -> GEMM -> per-column scale / shift (+ ReLU) -> h_{l+1}: the post-op vectors ride where the
 // attention vectors ride (a.att_src = scale, a.att_dst = shift), the pre-GEMM scale / shift are the identity.  (GCN: A (X W) = (A X) W.)
-template <int HC, int C, int K, int NT, int EPI, int SP = 0, int AGG = 0>     // SP: 0 exact f32, 1 bf16x3, 2 fp16x3, 3 bf16 storage + MFMA
+template <int HC, int C, int K, int NT, int EPI, int SP = 0, int AGG = 0, int LF = 0>     // SP: 0 exact f32, 1 bf16x3, 2 fp16x3, 3 bf16 storage + MFMA; LF: FusedLds
 // (register budget: what the LDS footprint allows per CU -- except the plain backbones on the 16-slot stencil, whose aggregate
 //  coefficients (GCN's degree products / GIN's ones over 17 sources, in full float32) do not fit three workgroups' 168 registers:
 //  they spilled 140 bytes per lane there and run two per CU instead)
-__global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, NT, EPI, SP>::PER_CU)) void gat_layer_fused_kernel(FusedArgs a) {
+__global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, NT, EPI, SP, LF>::PER_CU)) void gat_layer_fused_kernel(FusedArgs a) {
+  static_assert(LF == 0 || AGG == 0, "light form: GAT instances");
   static_assert(AGG == 0 || (SP == 0 && EPI == EPI_NEXT), "the plain backbones run on the exact path, layer form");
   static_assert(AGG != 2 || HC == 2 * C, "GraphSAGE: two virtual heads");
   constexpr int SRCW = AGG == 2 ? C : HC;                // channels of a SOURCE row (GraphSAGE: both virtual heads read the same C)
@@ -534,10 +542,11 @@ __global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, 
   // the heads instances, k = 16 and the plain backbones would lose a resident workgroup to it)
   constexpr bool GATHER_PIPE = SP == 0 && K <= 8 && EPI == EPI_NEXT && AGG == 0;
   using Geo = FusedGeom<K>;
-  using Lds = FusedLds<HC, C, K, NT, EPI, SP>;
+  using Lds = FusedLds<HC, C, K, NT, EPI, SP, LF>;
+  constexpr bool HS = Lds::HS;                           // light form: half-slab image, half-steps (below)
   constexpr int HR = Geo::HR, HW_ = Geo::HW, RAD = Geo::R;
   constexpr int XB = Lds::XB;                            // bytes per stored activation
-  constexpr int ROWB = 32 * XB;                          // bytes of one halo row's slab (128 / 64)
+  constexpr int ROWB = HS ? 64 : 32 * XB;                // bytes of one halo row's (half-)slab (128 / 64)
   constexpr int CPR = ROWB / 16;                         // 16-byte chunks per row slab (8 / 4)
   using Off = StencilOffsets<K>;
   extern __shared__ __attribute__((aligned(128))) float lds[];
@@ -663,7 +672,12 @@ __global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, 
   for (int i = 0; i < NHL; ++i) {
     const int hh = hl + i * 2;
 #pragma unroll
-    for (int f = 0; f < 3; ++f) vpre[i][f] = (AGG == 0 && hh < H) ? a.V[hh * 3 + f] : 0.0f;
+    for (int f = 0; f < 3; ++f) {
+      // (light form, one head: only the hl = 0 lanes run phase A's arithmetic -- the edge vector stays a uniform value in scalar
+      //  registers instead of three vector registers held from here to phase A)
+      if constexpr (HS && H == 1) vpre[i][f] = a.V[f];
+      else vpre[i][f] = (AGG == 0 && hh < H) ? a.V[hh * 3 + f] : 0.0f;
+    }
   }
   // (heads: the small second-stage weight table -- 296 floats, packed on the host in its LDS layout -- is one LDS-DMA piece
   //  issued where its LDS region falls free, see stage_head_table below.  Read straight from global memory in the final epilogue
@@ -750,7 +764,13 @@ __global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, 
   // Round 2's (row >> 1) & 7 shifted the second block row's slots by one against the first: two 2-way conflicts per group, i.e.
   // every gather read took twice its LDS cycles (SQ_LDS_BANK_CONFLICT: 37-47 % of the exact instances' LDS-active cycles).
   static_assert(HW_ % 2 == 0, "row parity follows the halo column");
-  auto swz = [](int row) { return XB == 4 ? ((row % HW_) >> 1) & 7 : (row >> 2) & 3; };
+  // Light form, 64-byte rows of f32 (four chunks; row * 64 mod 256 puts halo row `row` into quarter row & 3 of a 256-byte bank line):
+  // swz = bit 2 of the halo column | parity of the halo line << 1.  The eight columns a group takes from one line are two runs of
+  // four, twelve apart: a run covers the four quarters, the two runs differ in bit 2 of the column, and the group's other line
+  // differs in parity -- 16 distinct (quarter, chunk) slots.
+  auto swz = [](int row) {
+    return HS ? (((row % HW_) >> 2) & 1) | (((row / HW_) & 1) << 1) : XB == 4 ? ((row % HW_) >> 1) & 7 : (row >> 2) & 3;
+  };
   // Per piece ONE 64-bit source base for the whole block (a single 32 x 32 -> 64-bit multiply-add off the table's base; an earlier
   // version kept 32-bit offsets relative to the smallest id of the wave, which cost a six-step wave reduction per block): rows
   // without a node read the context's zero page, which holds more than NSLAB * ROWB zero bytes, so that they can advance by ROWB
@@ -760,13 +780,19 @@ __global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, 
   const char *xbase = reinterpret_cast<const char *>(a.xw);
   const char *zp = reinterpret_cast<const char *>(a.zero_page);
   const char *dbase[NPIECE];
+  // light form, one-head sources (the heads launch): the bases as 32-bit offsets in 16-byte units (64-channel rows: 2^28 nodes), ~0 = the
+  // zero page, widened at each request -- three registers less across the whole block, which is what keeps this instance free of
+  // scratch at 128 registers; a few vector instructions per half-step, and it has four of them
+  constexpr bool DB32 = HS && H == 1;
+  uint32_t doff[NPIECE];
   {
     const int cc = tid % CPR;
 #pragma unroll
     for (int p = 0; p < NPIECE; ++p) {
       const int row = prow_r[p] * HW_ + prow_c[p];
-      const int c = cc ^ swz(row);
+      const int c = cc ^ (HS ? ((prow_c[p] >> 2) & 1) | ((prow_r[p] & 1) << 1) : swz(row));   // (HS: swz(row) without the division)
       dbase[p] = drow[p] >= 0 ? xbase + ((uint64_t)(uint32_t)drow[p] * (uint32_t)(SRCW * XB) + (uint32_t)(c * 16)) : zp;
+      doff[p] = drow[p] >= 0 ? (uint32_t)drow[p] * (uint32_t)(SRCW * XB / 16) + (uint32_t)c : ~0u;
     }
   }
   int npc = 0;
@@ -782,11 +808,14 @@ __global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, 
     }
   };
   auto issue_slab = [&](int s) {
-    const int sb = (AGG == 2 ? s % SPH : s) * ROWB;    // wave-uniform (GraphSAGE: the second virtual head re-reads the same channels)
+    const int sb = (AGG == 2 ? s % SPH : s) * ROWB;    // wave-uniform (GraphSAGE: the second virtual head re-reads the same channels; HS: s counts half-slabs)
 #pragma unroll
     for (int p = 0; p < NPIECE; ++p) {
       if ((p + 1) * NTH <= HR * CPR || p * NTH + tid < HR * CPR) {        // (only the last piece is partial: compile-time true before)
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(dbase[p] + sb),
+        uint32_t dof = doff[p];
+        if constexpr (DB32) asm volatile("" : "+v"(dof));    // (opaque: the widened base must not be hoisted back out of the loop)
+        const char *src = DB32 ? (dof != ~0u ? xbase + ((uint64_t)dof << 4) : zp) : dbase[p];
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(src + sb),
                                          (__attribute__((address_space(3))) void *)(slab + (DBUF && !(s & 1) ? Lds::SLAB1 : 0) + (p * NTH + wave * 64) * 4), 16, 0, 0);
       }
     }
@@ -826,6 +855,10 @@ __global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, 
   for (int i = 0; i < NHL; ++i)
 #pragma unroll
     for (int b = 0; b < (K + 2) / 2; ++b) apk[i][b] = 0u;
+  static_assert(!HS || NHL <= 2, "light form: a lane holds at most one head beside the one in the table");
+  float keep[K + 1];                                    // light form, H > 2: the coefficients of this lane's second head
+#pragma unroll
+  for (int b = 0; b <= K; ++b) keep[b] = 0.0f;
   {
     const uint32_t hid0 = lds_addr(hid), has0 = lds_addr(has);
     // (k = 16 bf16 heads instance, which runs at its register limit: the cell's halo index is recomputed from the thread id here --
@@ -899,9 +932,14 @@ __global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, 
         if constexpr (SP == 3) {      // kept in registers as bf16 pairs until this head's slabs come up (densified there)
 #pragma unroll
           for (int b = 0; b <= K; b += 2) apk[i][b / 2] = pack_bf16x2(part[i][b], b + 1 <= K ? part[i][b + 1] : 0.0f);
+        } else if (HS && H > Lds::AW && i > 0) {
+          // light form: the table holds one head pair; the lane's second head waits in registers until the first pair's last
+          // slab has been gathered (the rows of a cell are written and read by the cell's own two lanes only)
+#pragma unroll
+          for (int b = 0; b <= K; ++b) keep[b] = part[i][b];
         } else {
           // (asm writes: with slab 0's DMA in flight hipcc would wait vmcnt(0) in front of a visible ds_write too)
-          lds_write_coefficients<K>(lds_addr(alx + cell * APITCH + hh * (K + 1)), part[i], std::make_integer_sequence<int, K + 1>{});
+          lds_write_coefficients<K>(lds_addr(alx + cell * APITCH + (HS && H > Lds::AW ? hl : hh) * (K + 1)), part[i], std::make_integer_sequence<int, K + 1>{});
         }
       }
     }
@@ -945,7 +983,109 @@ __global__ __launch_bounds__(256, (AGG != 0 && K == 16 ? 2 : FusedLds<HC, C, K, 
 
   // ---- slabs.  Lane (r, hl) gathers exactly the 16 values it feeds to the MFMA as B operand -- no LDS round trip, no
   // lane exchange.
-  {
+  if constexpr (HS) {
+    // ---- light form: a slab is two HALF-STEPS over one [HR][16 channels] image.  Half-step hs = 2 s + h:
+    //   wait for everything | barrier A | DMA W half hs + 1 | gather channels 16 h .. 16 h + 15 of slab s + BN/ReLU (g[2h], g[2h+1]) |
+    //   barrier B | DMA half-slab hs + 1 | 16 x NT MFMAs out of W half h
+    // Barrier A publishes half-slab hs and W half hs (requested a whole half-step ago) and says that every wave has left the MFMAs of
+    // half-step hs - 1, whose W half the DMA behind it refills; barrier B says that every wave has gathered, so the image can be
+    // refilled under the MFMAs.  The same four barriers per slab as the full-slab form, no counted wait (a wave never has more in
+    // flight than what the next barrier A needs), and per accumulator the same k rows in the same order: bit-identical.
+    // The image is single because two of them would not fit four workgroups per CU; what the shorter lead exposes, the fourth
+    // workgroup is there to cover.
+    constexpr int AW = Lds::AW;
+    auto half_step = [&](auto hc_, int s, uint32_t ap, f32x4 (&g)[4]) {
+      constexpr int h = decltype(hc_)::value;
+      const int hs = 2 * s + h;
+      wait_vm_lgkm<0>();
+      __builtin_amdgcn_s_barrier();                     // A
+      if (h == 0 && s == 0) {
+        // phase A is over on every wave: R changes hands (as in the full-slab form below)
+#pragma unroll
+        for (int i = 0; i < NSC; ++i) {
+          const int c = tid + i * NTH;
+          if (c < HC) { scsh[c] = scv[i]; scsh[HC + c] = shv[i]; }
+        }
+        if constexpr (EPI == EPI_HEADS) stage_head_table();
+        if (EPI == EPI_NEXT && wave < 2 && lane * 4 < NC)
+          __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>((wave == 0 ? a.att_src : a.att_dst) + lane * 4),
+                                           (__attribute__((address_space(3))) void *)(attr + wave * NC), 16, 0, 0);
+        wait_lgkm0();
+        __builtin_amdgcn_s_barrier();                   // scale / shift visible
+      }
+      if (hs >= 1 && hs + 1 < 2 * NSLAB) stage_w_half<NT, SP>(a.Wt, wbuf, hs + 1, wave, lane);   // (halves 0 and 1 went in the prologue)
+      constexpr int jA = 2 * h, jB = 2 * h + 1;
+      g[jA] = (f32x4){0.f, 0.f, 0.f, 0.f}; g[jB] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      auto row_addr = [&](int b) -> uint32_t {          // chunk hl of source b's row; chunk 2 + hl sits at (addr ^ 32)
+        const int dr_ = b < K ? Off::dr[b < K ? b : 0] : 0, dc_ = b < K ? Off::dc[b < K ? b : 0] : 0;
+        const int nidx = self_idx - dr_ * HW_ - dc_;
+        const int hcol = tc + RAD - dc_, hline = tr + RAD - dr_;
+        return slab0 + nidx * 64 + ((((((hcol >> 2) & 1) | ((hline & 1) << 1))) ^ hl) << 4);
+      };
+      if constexpr (GATHER_PIPE) {
+        f32x4 xb[2][2];
+        float al[2];
+        auto issue = [&](int b, int q) {
+          const uint32_t rb = row_addr(b);
+          al[q] = lds_read1<0>(ap + 4 * b);
+          xb[q][0] = lds_read4<0>(rb); xb[q][1] = lds_read4<0>(rb ^ 32);
+        };
+        issue(0, 0);
+#pragma unroll
+        for (int b = 0; b <= K; ++b) {
+          const int q = b & 1;
+          if (b + 1 <= K) { issue(b + 1, q ^ 1); lds_reads_wait<3>(); } else lds_reads_done();
+          g[jA] += al[q] * xb[q][0]; g[jB] += al[q] * xb[q][1];
+        }
+      } else {
+#pragma unroll
+        for (int b = 0; b <= K; ++b) {
+          const uint32_t rb = row_addr(b);
+          const float alpha = lds_read1<0>(ap + 4 * b);
+          const f32x4 x0 = lds_read4<0>(rb), x1 = lds_read4<0>(rb ^ 32);
+          lds_reads_done();
+          g[jA] += alpha * x0; g[jB] += alpha * x1;
+        }
+      }
+      {
+        const uint32_t cp = scsh0 + s * 128 + h * 64;
+        const f32x4 sc0 = lds_read4<0>(cp), sc1 = lds_read4<32>(cp), sh0 = lds_read4<HC * 4>(cp), sh1 = lds_read4<HC * 4 + 32>(cp);
+        lds_reads_done();
+        g[jA] = g[jA] * sc0 + sh0;
+        g[jB] = g[jB] * sc1 + sh1;
+        if (a.relu) {
+#pragma unroll
+          for (int j = jA; j <= jB; ++j) {
+            asm("v_max_f32 %0, 0, %0" : "+v"(g[j].x)); asm("v_max_f32 %0, 0, %0" : "+v"(g[j].y));
+            asm("v_max_f32 %0, 0, %0" : "+v"(g[j].z)); asm("v_max_f32 %0, 0, %0" : "+v"(g[j].w));
+          }
+        }
+      }
+      wait_lgkm0();
+      __builtin_amdgcn_s_barrier();                     // B
+      if (hs + 1 < 2 * NSLAB) issue_slab(hs + 1);
+      if constexpr (h == 0) {
+        if (s == 0) MfmaGroups<NT, NC, 0, 4, true>::run(acc, g, wbuf0);
+        else MfmaGroups<NT, NC, 0, 4>::run(acc, g, wbuf0);
+      } else {
+        MfmaGroups<NT, NC, 4, 8>::run(acc, g, wbuf0);
+      }
+    };
+#pragma unroll 1
+    for (int s = 0; s < NSLAB; ++s) {
+      const int hd = s / SPH;
+      if constexpr (H > AW) {
+        // the second head pair's coefficients take the first pair's place: this wave's reads of them are complete (every gather ends
+        // with lgkmcnt(0)) and nobody else reads a cell's rows
+        if (s == AW * SPH && hl + AW < H)
+          lds_write_coefficients<K>(alx0 + hl * ((K + 1) * 4), keep, std::make_integer_sequence<int, K + 1>{});
+      }
+      const uint32_t ap = alx0 + (H > AW ? (hd & (AW - 1)) : hd) * ((K + 1) * 4);
+      f32x4 g[4];
+      half_step(std::integral_constant<int, 0>{}, s, ap, g);
+      half_step(std::integral_constant<int, 1>{}, s, ap, g);
+    }
+  } else {
 #pragma unroll 1
     for (int s = 0; s < NSLAB; ++s) {
       const uint32_t slabs = slab0;
@@ -1985,12 +2125,12 @@ static int launch_two_phase(bgnn_ctx *ctx, const FusedArgs &a) {
   return BGNN_OK;
 }
 
-template <int HC, int C, int K, int NT, int EPI, int SP = 0, int AGG = 0>
+template <int HC, int C, int K, int NT, int EPI, int SP = 0, int AGG = 0, int LF = 0>
 static int launch_inst(bgnn_ctx *ctx, const FusedArgs &a) {
-  constexpr size_t lds_bytes = (size_t)FusedLds<HC, C, K, NT, EPI, SP>::FLOATS * 4;
+  constexpr size_t lds_bytes = (size_t)FusedLds<HC, C, K, NT, EPI, SP, LF>::FLOATS * 4;
   static_assert(lds_bytes <= 160 * 1024, "one workgroup fits the CU's LDS");
   static std::atomic<uint64_t> configured{0};   // per instantiation: one bit per device (the attribute is per device)
-  auto kern = gat_layer_fused_kernel<HC, C, K, NT, EPI, SP, AGG>;
+  auto kern = gat_layer_fused_kernel<HC, C, K, NT, EPI, SP, AGG, LF>;
   if (!(configured.load(std::memory_order_relaxed) >> (ctx->device & 63) & 1)) {
     BGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     configured.fetch_or(1ull << (ctx->device & 63), std::memory_order_relaxed);
@@ -2000,14 +2140,23 @@ static int launch_inst(bgnn_ctx *ctx, const FusedArgs &a) {
   return BGNN_OK;
 }
 
+// exact-f32 GAT instance: the light form (FusedLds, four workgroups per CU) where it exists and the context asks for it
+template <int HC, int K, int NT, int EPI>
+static int launch_exact(bgnn_ctx *ctx, const FusedArgs &a) {
+  if constexpr (K <= 8 && NT <= 3) {
+    if (ctx->opts.fused_light_form) return launch_inst<HC, 64, K, NT, EPI, 0, 0, 1>(ctx, a);
+  }
+  return launch_inst<HC, 64, K, NT, EPI, 0>(ctx, a);
+}
+
 // stencil dispatch: K = 8 and 4 (reference connectivities) on every matrix path; K = 16 ("16-dilated") on the exact-f32
 // path (the parity instance, one workgroup per CU) and on the bf16 path (BASELINE config 3)
 template <int HC, int NT, int EPI>
 static int launch_by_stencil(bgnn_ctx *ctx, const bgnn_graph *g, int sp, const FusedArgs &a) {
   switch (sp) {
     case 0:
-      return g->K == 8 ? launch_inst<HC, 64, 8, NT, EPI, 0>(ctx, a) : g->K == 4 ? launch_inst<HC, 64, 4, NT, EPI, 0>(ctx, a)
-                                                                                 : launch_inst<HC, 64, 16, NT, EPI, 0>(ctx, a);
+      return g->K == 8 ? launch_exact<HC, 8, NT, EPI>(ctx, a) : g->K == 4 ? launch_exact<HC, 4, NT, EPI>(ctx, a)
+                                                                           : launch_exact<HC, 16, NT, EPI>(ctx, a);
     case 3:
       return g->K == 8 ? launch_inst<HC, 64, 8, NT, EPI, 3>(ctx, a) : g->K == 4 ? launch_inst<HC, 64, 4, NT, EPI, 3>(ctx, a)
                                                                                  : launch_inst<HC, 64, 16, NT, EPI, 3>(ctx, a);
@@ -2016,6 +2165,25 @@ static int launch_by_stencil(bgnn_ctx *ctx, const bgnn_graph *g, int sp, const F
   if (g->K == 16) return BGNN_ERR_UNSUPPORTED;
   if (sp == 1) return g->K == 8 ? launch_inst<HC, 64, 8, NT, EPI, 1>(ctx, a) : launch_inst<HC, 64, 4, NT, EPI, 1>(ctx, a);
   return g->K == 8 ? launch_inst<HC, 64, 8, NT, EPI, 2>(ctx, a) : launch_inst<HC, 64, 4, NT, EPI, 2>(ctx, a);
+}
+
+// Dynamic LDS (bytes per workgroup) of an exact-f32 GAT instance gat_layer_fused_kernel<hc, 64, k, nt, epi, 0, 0, lf>, or -1: for
+// tools/kernel_resources.py -- the compiler's resource remarks only know static LDS, and these kernels have none.  Not part of the API.
+template <int HC, int K, int NT, int EPI>
+static int exact_lds_bytes(int lf) {
+  if constexpr (K <= 8 && NT <= 3) {
+    if (lf) return FusedLds<HC, 64, K, NT, EPI, 0, 1>::FLOATS * 4;
+  }
+  return lf ? -1 : FusedLds<HC, 64, K, NT, EPI, 0, 0>::FLOATS * 4;
+}
+extern "C" int bgnn_internal_fused_lds_bytes(int hc, int k, int nt, int epi, int lf) {
+#define BGNN_LDS_CASE(HCV, KV, NTV, EPIV) if (hc == HCV && k == KV && nt == NTV && epi == EPIV) return exact_lds_bytes<HCV, KV, NTV, EPIV>(lf);
+#define BGNN_LDS_STENCILS(HCV, NTV, EPIV) BGNN_LDS_CASE(HCV, 4, NTV, EPIV) BGNN_LDS_CASE(HCV, 8, NTV, EPIV) BGNN_LDS_CASE(HCV, 16, NTV, EPIV)
+  BGNN_LDS_STENCILS(256, 8, EPI_NEXT) BGNN_LDS_STENCILS(256, 2, EPI_NEXT) BGNN_LDS_STENCILS(128, 4, EPI_NEXT)
+  BGNN_LDS_STENCILS(128, 2, EPI_NEXT) BGNN_LDS_STENCILS(64, 2, EPI_NEXT) BGNN_LDS_STENCILS(64, 3, EPI_HEADS)
+#undef BGNN_LDS_STENCILS
+#undef BGNN_LDS_CASE
+  return -1;
 }
 
 static bool fused_supported(const bgnn_graph *g, int C) {
@@ -2068,7 +2236,7 @@ int launch_fused_layer_next(bgnn_ctx *ctx, const bgnn_graph *g, const BgnnLayer 
   if (g->K == 16) return BGNN_ERR_UNSUPPORTED;
 #define BGNN_FUSED_CASE(hc, nt)                                                                         \
   if (HC == hc && NC == nt * 32)                                                                        \
-    return g->K == 8 ? launch_inst<hc, 64, 8, nt, EPI_NEXT>(ctx, a) : launch_inst<hc, 64, 4, nt, EPI_NEXT>(ctx, a);
+    return g->K == 8 ? launch_exact<hc, 8, nt, EPI_NEXT>(ctx, a) : launch_exact<hc, 4, nt, EPI_NEXT>(ctx, a);
   BGNN_FUSED_CASE(128, 4) BGNN_FUSED_CASE(128, 2) BGNN_FUSED_CASE(64, 2)
 #undef BGNN_FUSED_CASE
   return BGNN_ERR_UNSUPPORTED;

@@ -32,7 +32,7 @@ MATRIX_PATHS = {"exact_f32": 0, "bf16x3": 1, "fp16x3": 2, "bf16": 3}
 # the diagnostic build)
 OPTION_NAMES = ("matrix_path", "fused", "fold_extractor", "ragged_atlas", "features_tiled", "fused_front",
                 "bf16_two_phase", "bf16_layer0_af", "stats_narrow", "diag_mask", "diag_stamps",
-                "gemm_diag", "gemm_pair_major")
+                "gemm_diag", "gemm_pair_major", "fused_light_form")
 
 
 GNN_TYPES = {"GAT": 0, "GCN": 1, "GraphSAGE": 2, "GIN": 3}      # BGNN_GNN_*

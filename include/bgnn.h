@@ -93,6 +93,9 @@ void *bgnn_ctx_stream(bgnn_ctx *ctx);
  *   "bf16_layer0_af"  1 (default): matrix_path 3, default model shape: layer 0 aggregates the extractor's 64-channel output and applies the
  *                     folded lin_0 weight per head afterwards, inside the fused launch (GATConv's sum is linear; no lin_0 GEMM launch, no
  *                     256-channel lin_0 rows in HBM; needs bf16_two_phase = 1); 0: lin_0 GEMM first (another rounding sequence)   [BGNN_NO_LAYER0_AF]
+ *   "fused_light_form" 1 (default): the exact-f32 fused GAT launches with a narrow next stage (256 -> 64, the heads) keep half a slab
+ *                     and one head pair's coefficients in LDS and run four workgroups per CU; 0: the full-slab instances, three per CU
+ *                     (bit-identical; the form it is tested against)
  *   "stats_narrow"    -1 (default): 16-wide box-statistics workgroups when the 64-wide launch would leave CUs idle; 0 / 1 force
  * plus diagnostic knobs ("diag_mask", "diag_stamps", "gemm_diag": exist only in the diagnostic build of the library).
  * Unknown names -> BGNN_ERR_INVALID. */
