@@ -11,6 +11,7 @@ from .feature_labels import (FEATURE_CLASSES, FeatureLabels, S57Feature, create_
                              rasterize_features)
 from .review_regions import ReviewRegions, export_review_regions
 from .slope_features import add_feature_labels, create_feature_mask_from_slope, slope_cut, wreck_pixel_table
+from .vr_ground_truth import NativeGroundTruth, VRPairTable, compute_ground_truth_native, vr_pair_table
 
 __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "TileSpec", "TileManager", "TileMerger",
            "RefinementGrid", "VRBagHandler", "VRBagWriter", "SRBagHandler", "SRBagWriter", "SidecarBuilder", "detect_bag_type",
@@ -19,4 +20,5 @@ __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "Tile
            "analyze_noise_patterns", "print_analysis",
            "FEATURE_CLASSES", "FeatureLabels", "S57Feature", "create_feature_labels", "feature_pixel_table", "feature_plan",
            "rasterize_features", "ReviewRegions", "export_review_regions",
-           "add_feature_labels", "create_feature_mask_from_slope", "slope_cut", "wreck_pixel_table"]
+           "add_feature_labels", "create_feature_mask_from_slope", "slope_cut", "wreck_pixel_table",
+           "NativeGroundTruth", "VRPairTable", "compute_ground_truth_native", "vr_pair_table"]

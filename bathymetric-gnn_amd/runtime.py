@@ -340,6 +340,24 @@ TILE_COUNTS = 4                                    # BGNN_TILE_COUNTS: valid, cl
 TILE_BOX_DTYPE = np.dtype([("row0", "<i8"), ("col0", "<i8"), ("h", "<i4"), ("w", "<i4"), ("dst", "<i8")])
 TILE_BOX_BYTES = TILE_BOX_DTYPE.itemsize
 
+
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_vrtruth.h declares (native-resolution ground truth from a VR BAG pair)
+_VRTRUTH_SIGNATURES = {
+    "bgnn_vr_ground_truth_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "bgnn_vr_ground_truth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                       C.c_double, C.c_double, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7),
+}
+VT_TILE_CELLS = 1024                               # BGNN_VT_TILE_CELLS
+VT_COUNTS = 4                                      # BGNN_VT_COUNTS: valid, class 0, class 1, class 2
+# bgnn_vr_pair (BGNN_VT_PAIR_BYTES = 32)
+VT_PAIR_DTYPE = np.dtype([("out_offset", "<i8"), ("cells", "<i8"), ("noisy_start", "<i8"), ("clean_start", "<i8")])
+VT_PAIR_BYTES = VT_PAIR_DTYPE.itemsize
+# BGNN_VT_STATS_*: int64 valid, noise, seafloor | float64 noise_abs_sum, noise_abs_median | float32 noise_abs_max, pad
+VT_STATS_BYTES = 48
+VT_STATS_DTYPE = [("valid", "<i8"), ("noise", "<i8"), ("seafloor", "<i8"), ("noise_abs_sum", "<f8"), ("noise_abs_median", "<f8"),
+                  ("noise_abs_max", "<f4"), ("pad", "<i4")]
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -351,7 +369,8 @@ class BgnnError(RuntimeError):
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
-    include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h and include/bgnn_slope.h.  Needs no GPU."""
+    include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h and include/bgnn_vrtruth.h.  Needs no
+    GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -365,7 +384,8 @@ def load_library(path: Optional[str] = None):
         for name, (res, args) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + list(_SIDECAR_SIGNATURES.items()) + \
                 list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
                 list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
-                list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()):
+                list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()) + \
+                list(_VRTRUTH_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

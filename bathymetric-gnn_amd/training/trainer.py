@@ -218,6 +218,15 @@ def _plane_to_device(plane, dtype: torch.dtype, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(np.asarray(plane).astype(npdt, copy=False))).to(device)
 
 
+def ragged_cell_index(offsets: np.ndarray, idx: np.ndarray) -> np.ndarray:
+    """The cells ``offsets[i] .. offsets[i + 1] - 1`` of every tile ``i`` of ``idx``, in that order, as one int64 index -- without
+    a loop over tiles (a batch of refinement grids holds thousands)."""
+    idx = np.asarray(idx, dtype=np.int64)
+    first, cells = offsets[idx], offsets[idx + 1] - offsets[idx]
+    run0 = np.cumsum(cells) - cells                      # where tile k's run starts in the index
+    return np.repeat(first - run0, cells) + np.arange(int(cells.sum()), dtype=np.int64)
+
+
 def dropout_seed(seed: int, global_step: int) -> int:
     """The dropout seed of training step ``global_step`` (epoch * steps per epoch + step) of a run seeded ``seed``:
     ``(seed mod 2^31) * 2^32 + (global_step mod 2^32)``."""
@@ -446,6 +455,66 @@ class TileStore:
         store.boxes = boxes
         return store
 
+    @classmethod
+    def from_refinement_pairs(cls, truths, min_valid_ratio: float = 0.0, device=None, **kw) -> "TileStore":
+        """A ``"ground_truth"`` store whose tiles are the refinement grids of clean / noisy VR BAG pairs at their native resolution
+        (docs/TRAINING_PLAN.md step 4.1).  ``truths``: one ``data.NativeGroundTruth`` (``compute_ground_truth_native``) or a
+        sequence of them; either all carry an uncertainty or none does.
+
+        A grid is kept when it is paired, has at least one valid cell, and ``valid / cells >= min_valid_ratio`` in float64 -- and
+        when it has at least two cells a side: a narrower grid has no gradient features and ``batch`` would refuse it with
+        numpy.gradient's message, as the reference's graph construction does.  The only thing read back is every truth's ``grid_counts`` (32 bytes per grid); the kept grids are compacted on the device, one
+        ``bgnn_tile_cut`` per truth over its flat planes viewed as ``[1][T]`` with one-row boxes: ``depth`` is the noisy depth,
+        ``hw`` / ``res`` are the grids' own, the mask is ``labels >= 0`` (the truth's own mask), the class counts are summed over the
+        kept grids.  ``store.grids``: per truth the indices of its kept grids (int64), ``store.sources`` (int32) the truth of every
+        tile.  No grid kept at all raises ``ValueError``."""
+        from ..data.vr_ground_truth import NativeGroundTruth
+        device = rt.resolve_device(device)
+        ctx = rt.get_context(device)
+        truths = [truths] if isinstance(truths, NativeGroundTruth) else list(truths)
+        for k, t in enumerate(truths):
+            if not isinstance(t, NativeGroundTruth):
+                raise TypeError(f"truths[{k}] is a {type(t).__name__}: NativeGroundTruth expected (compute_ground_truth_native)")
+            if t.labels.device != device:
+                raise ValueError(f"truths[{k}] lies on {t.labels.device}, the store on {device}")
+        if len({t.uncertainty is None for t in truths}) > 1:
+            raise ValueError("some truths carry an uncertainty and some carry none: the graphs would differ in in_channels")
+        host_counts = [t.grid_counts.cpu().numpy().reshape(-1, rt.TILE_COUNTS) for t in truths]      # (the only read-back)
+        kept, class_counts = [], {0: 0, 1: 0, 2: 0}
+        for t, cnt in zip(truths, host_counts):
+            cells = np.diff(t.offsets)
+            valid = cnt[:, 0]
+            keep = np.asarray(t.paired, bool) & (valid >= 1) & (valid / np.maximum(cells, 1) >= min_valid_ratio) & \
+                (t.hw.min(axis=1) >= 2)
+            kept.append(np.nonzero(keep)[0].astype(np.int64))
+            for c in class_counts:
+                class_counts[c] += int(cnt[keep, 1 + c].sum())
+        if sum(len(k) for k in kept) == 0:
+            raise ValueError("the refinement pairs yield no grid to train on")
+        hw = np.concatenate([t.hw[k] for t, k in zip(truths, kept)]).astype(np.int32).reshape(-1, 2)
+        res = np.concatenate([t.res[k] for t, k in zip(truths, kept)]).astype(np.float64).reshape(-1, 2)
+        offsets = np.concatenate([[0], np.cumsum(hw[:, 0].astype(np.int64) * hw[:, 1])])
+        cells = int(offsets[-1])
+        with_unc = truths[0].uncertainty is not None
+        stores = [torch.empty(cells, dtype=torch.int32, device=device), torch.empty(cells, dtype=torch.float32, device=device),
+                  torch.empty(cells, dtype=torch.float32, device=device),
+                  torch.empty(cells, dtype=torch.float32, device=device) if with_unc else None]
+        mask = torch.empty(cells, dtype=torch.uint8, device=device)
+        first = 0
+        for t, k in zip(truths, kept):                   # one gather per truth at its running offset
+            if len(k) == 0:
+                continue
+            src = t.offsets[k]
+            boxes = np.stack([np.zeros_like(src), src, np.ones_like(src), t.offsets[k + 1]], axis=1)
+            planes = [p if p is None else p.view(1, -1) for p in (t.labels, t.difference, t.noisy_depth, t.uncertainty)]
+            cut_tile_boxes(planes, stores, boxes, offsets[first:first + len(k)], mask=mask, mask_plane=0, ctx=ctx)
+            first += len(k)
+        store = cls("ground_truth", hw, res, stores[2], mask, stores[3], labels=stores[0], difference=stores[1],
+                    class_counts=class_counts, device=device, **kw)
+        store.grids = kept
+        store.sources = np.concatenate([np.full(len(k), i, np.int32) for i, k in enumerate(kept)])
+        return store
+
     # ---- access ----------------------------------------------------------------------------------------------------------
     def __len__(self) -> int:
         return int(self.hw.shape[0])
@@ -462,8 +531,7 @@ class TileStore:
             sel = torch.as_tensor(idx, dtype=torch.int64).to(self.device)
             out = {k: None if p is None else p.view(len(self), cells).index_select(0, sel).reshape(-1) for k, p in planes.items()}
         else:
-            cell_idx = np.concatenate([np.arange(self.offsets[i], self.offsets[i + 1], dtype=np.int64) for i in idx])
-            sel = torch.from_numpy(cell_idx).to(self.device)
+            sel = torch.from_numpy(ragged_cell_index(self.offsets, idx)).to(self.device)
             out = {k: None if p is None else p.index_select(0, sel) for k, p in planes.items()}
         return np.ascontiguousarray(self.hw[idx]), np.ascontiguousarray(self.res[idx]), out
 
@@ -629,10 +697,17 @@ class Trainer:
 
     ``config``: a ``Config`` of this package (``training`` a plain dict) or of the reference; the training settings are read
     through ``training_settings``.  The model is moved to the store's GPU.  A model the backward pass refuses (GCN, a
-    zero-padded shape, layers wider than 256 columns) raises here, with the backward's message."""
+    zero-padded shape, layers wider than 256 columns) raises here, with the backward's message.
+
+    ``batch_nodes`` (None: steps of ``batch_size`` tiles, as the reference cuts them): steps cut by cell count instead, for stores
+    whose tiles differ widely in size (``TileStore.from_refinement_pairs``: refinement grids of 9 to 2500 cells); see
+    ``step_plan``."""
 
     def __init__(self, config, model, train_store: TileStore, val_store: Optional[TileStore] = None, output_dir=None,
-                 seed: int = 0):
+                 seed: int = 0, batch_nodes: Optional[int] = None):
+        if batch_nodes is not None and int(batch_nodes) < 1:
+            raise ValueError(f"batch_nodes {batch_nodes}: a positive number of cells, or None")
+        self.batch_nodes = None if batch_nodes is None else int(batch_nodes)
         self.config = config
         self.model = model
         self.train_dataset = self.train_store = train_store
@@ -711,9 +786,8 @@ class Trainer:
                 sample_indices = [int(i) for i in np.linspace(0, len(store) - 1, num_samples, dtype=int)]
             else:
                 sample_indices = list(range(min(len(store), 50)))
-            bs = max(1, int(self.settings.batch_size))
-            for k in range(0, len(sample_indices), bs):
-                _, t = store.batch(sample_indices[k:k + bs], epoch=0)
+            for piece in self._pieces(store, np.asarray(sample_indices, dtype=np.int64)):
+                _, t = store.batch(piece, epoch=0)
                 y, mask, target = t["class_labels"], t["noise_mask"], t["correction_targets"]
                 if not scanned and y.numel() > 0:
                     ok = (y >= 0) & (y < num_classes)
@@ -745,19 +819,38 @@ class Trainer:
             return None, 1.0
 
     # ---- the plan of an epoch --------------------------------------------------------------------------------------------
+    def _pieces(self, store, order: np.ndarray) -> List[np.ndarray]:
+        """``order`` cut into the tile lists of consecutive steps: ``batch_size`` tiles each, or, with ``batch_nodes``, greedily by
+        the tiles' cell counts."""
+        limit = getattr(self, "batch_nodes", None)
+        if limit is None:
+            bs = max(1, int(self.settings.batch_size))
+            return [order[k:k + bs] for k in range(0, len(order), bs)]
+        cells = np.diff(np.asarray(store.offsets, dtype=np.int64))[order].tolist()
+        cuts, run = [0], 0
+        for k, c in enumerate(cells):
+            if k > cuts[-1] and run + c > limit:
+                cuts.append(k); run = 0
+            run += c
+        cuts.append(len(cells))
+        return [order[a:b] for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+
     def step_plan(self, epoch: int, validation: bool = False) -> List[Tuple[np.ndarray, Optional[int]]]:
         """``(tile indices, dropout seed)`` of every step of epoch ``epoch``.  Training: the tiles in the order
         ``np.random.default_rng([seed, epoch]).permutation(len(train_store))``, cut into pieces of ``batch_size``; the dropout
         seed of step ``k`` is ``dropout_seed(seed, epoch * steps_per_epoch + k)`` and is written to ``model.dropout_seed``
         before the step's forward.  ``validation=True``: the validation store in its own order, seed None (no dropout in
         ``eval()``).  This method, with the stores' noise (a function of (seed, epoch, tile)), is the whole source of randomness
-        of an epoch."""
+        of an epoch.
+
+        With ``batch_nodes`` set the same order is cut greedily by cell count instead: a piece closes before the tile that would
+        take its cells (``store.offsets`` differences) above ``batch_nodes``; a tile larger than that forms a piece alone.  Seeds
+        are numbered by piece, as above."""
         store = self.val_store if validation else self.train_store
-        bs = max(1, int(self.settings.batch_size))
         n = len(store)
         order = np.arange(n, dtype=np.int64) if validation else \
             np.random.default_rng([self.seed, int(epoch)]).permutation(n).astype(np.int64)
-        pieces = [order[k:k + bs] for k in range(0, n, bs)]
+        pieces = self._pieces(store, order)
         if validation:
             return [(p, None) for p in pieces]
         return [(p, dropout_seed(self.seed, int(epoch) * len(pieces) + k)) for k, p in enumerate(pieces)]

@@ -1,0 +1,313 @@
+"""Native-resolution ground truth from a clean / noisy VR BAG pair on the device (data/vr_ground_truth.py over
+``bgnn_vr_ground_truth``), the training store cut from it (``TileStore.from_refinement_pairs``), a training epoch with steps cut by
+cell count (``Trainer(batch_nodes=)``) and the evaluation of a classified BAG against it -- all against the host restatement of the
+reference's plan (tests/_vr_truth_cpu.py).
+
+Bit equality of ``difference``: where the restatement's difference is a number, infinities included, the bits are compared; where
+it is NaN (a NaN depth, inf - inf) the device's value must be NaN too -- IEEE 754 leaves sign and payload of an arithmetic NaN to
+the implementation, and the host's and the device's subtractions need not agree on them."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from _vr_truth_cpu import make_pair, make_scale_pair, native_truth_cpu
+
+pytestmark = pytest.mark.gpu
+
+VARIANTS = ("odd", "even", "none", "ties")
+
+
+@pytest.fixture(scope="module")
+def pairs():
+    """{variant: (clean handler, noisy handler, cases, restatement)}, each asserted to hold the cases it is meant to."""
+    out = {}
+    for v in VARIANTS:
+        clean, noisy, cases = make_pair(v)
+        ref = native_truth_cpu(clean, noisy)
+        place = {k: i for i, k in enumerate(ref["order"])}
+        span = lambda k: slice(int(ref["offsets"][place[k]]), int(ref["offsets"][place[k] + 1]))
+        n = ref["stats"]["noise_cells"]
+        assert {"odd": n % 2 == 1 and n > 20, "even": n % 2 == 0 and n > 20, "none": n == 0, "ties": n > 20}[v], n
+        assert ("median_noise_magnitude" in ref["stats"]) == (n > 0)
+        big = span(cases["big"])
+        assert tuple(ref["hw"][place[cases["big"]]]) == (50, 53) and big.stop - big.start > 2 * 1024
+        assert big.start % 1024 != 0                                             # the grid starts inside a workgroup's tile
+        assert cases["drop_noisy"] not in place                                  # a grid of the clean file alone
+        for k in ("drop_clean", "transposed"):                                   # no twin / other dimensions: not paired
+            assert not ref["paired"][place[cases[k]]] and (ref["labels"][span(cases[k])] == -1).all()
+            assert np.isnan(ref["difference"][span(cases[k])]).all() and not ref["mask"][span(cases[k])].any()
+        assert ref["paired"].sum() == len(ref["order"]) - 2
+        for k, n_valid in (("sparse", 1), ("empty", 0)):                          # paired grids the stores drop
+            assert ref["paired"][place[cases[k]]] and ref["grid_counts"][place[cases[k]], 0] == n_valid
+            assert ref["offsets"][place[cases[k]] + 1] - ref["offsets"][place[cases[k]]] >= 4
+        # nodata, NaN and inf cells in either file, inf - inf
+        d, lab = ref["difference"][big].reshape(50, 53), ref["labels"][big].reshape(50, 53)
+        assert (lab[3, 5:8] == -1).all() and (lab[9, 5:8] == -1).all() and np.isnan(d[9, 7]) and np.isposinf(d[3, 7])
+        assert np.isnan(d[3, 6]) and np.isnan(d[9, 6]) and abs(d[3, 5]) > 1e5 and abs(d[9, 5]) > 1e5
+        # |difference| exactly float32(0.15) is seafloor, an ulp above is noise
+        e = span(cases["exact"])
+        t015 = np.float32(0.15)
+        assert ref["difference"][e][:2].tolist() == [t015, -t015] and ref["labels"][e][:2].tolist() == [0, 0]
+        if v != "none":
+            assert ref["difference"][e][2] == np.nextafter(t015, np.float32(1)) and ref["labels"][e][2] == 2
+            mags = np.abs(ref["difference"][ref["labels"] == 2])
+            assert (mags < 0.35).any() and (mags > 1.0).any() if v != "ties" else set(mags.tolist()) >= {0.5, 1.0}
+        # the clean file's records lie in another order than the noisy file's
+        assert clean.refinement_table()["index"][0] > clean.refinement_table()["index"][-1]
+        assert noisy.refinement_table()["contiguous"] and not clean.refinement_table()["contiguous"]
+        out[v] = (clean, noisy, cases, ref)
+    return out
+
+
+@pytest.fixture(scope="module")
+def truths(pairs, gpu_device):
+    from bathymetric_gnn_amd.data import compute_ground_truth_native
+    return {v: compute_ground_truth_native(c, n, device=gpu_device) for v, (c, n, _, _) in pairs.items()}
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+def _same_difference(got, want):
+    nan = np.isnan(want)
+    return np.array_equal(np.isnan(got), nan) and np.array_equal(_bits(got)[~nan], _bits(want)[~nan])
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_planes_and_counts_equal_the_restatement(variant, pairs, truths):
+    ref, t = pairs[variant][3], truths[variant]
+    assert t.labels.dtype == torch.int32 and t.mask.dtype == torch.uint8 and t.grid_counts.dtype == torch.int64
+    assert np.array_equal(t.labels.cpu().numpy(), ref["labels"])
+    assert np.array_equal(t.mask.cpu().numpy(), ref["mask"])
+    assert np.array_equal(_bits(t.noisy_depth.cpu().numpy()), _bits(ref["noisy_depth"]))
+    assert np.array_equal(_bits(t.uncertainty.cpu().numpy()), _bits(ref["uncertainty"]))
+    assert np.array_equal(t.grid_counts.cpu().numpy(), ref["grid_counts"])
+    diff = t.difference.cpu().numpy()
+    assert _same_difference(diff, ref["difference"])
+    unpaired = np.repeat(~ref["paired"], np.diff(ref["offsets"]))
+    assert (_bits(diff)[unpaired] == 0x7FC00000).all()
+    assert np.array_equal(t.hw, ref["hw"]) and np.array_equal(t.res, ref["res"]) and np.array_equal(t.offsets, ref["offsets"])
+    assert np.array_equal(t.paired, ref["paired"])
+    assert list(zip(t.base_row.tolist(), t.base_col.tolist())) == ref["order"]
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_statistics_equal_the_restatement(variant, pairs, truths):
+    ref, t = pairs[variant][3]["stats"], truths[variant]
+    got = t.stats()
+    print(variant, got, ref)
+    for k in ("noise_threshold", "processing_mode", "base_shape", "grids_processed", "valid_cells", "noise_cells", "noise_percentage",
+              "seafloor_cells"):
+        assert got[k] == ref[k] and type(got[k]) is type(ref[k]), k
+    assert got["clean_survey"] == "None" and "resampled_shape" not in got and "resolution" not in got
+    b = t.block()
+    assert int(b["valid"]) == int(b["noise"]) + int(b["seafloor"])
+    if ref["noise_cells"] == 0:
+        assert "median_noise_magnitude" not in got and "mean_noise_magnitude" not in got and "max_noise_magnitude" not in got
+        assert math.isnan(float(b["noise_abs_median"])) and float(b["noise_abs_max"]) == 0.0 and float(b["noise_abs_sum"]) == 0.0
+        return
+    assert got["max_noise_magnitude"] == ref["max_noise_magnitude"]
+    assert got["median_noise_magnitude"] == ref["median_noise_magnitude"]
+    n = ref["noise_cells"]
+    bound = n * 2.0 ** -52 * ref["abs_sum"]                    # any float64 summation order of n terms against the exact sum
+    print(f"{variant}: n {n}, |sum - fsum| {abs(float(b['noise_abs_sum']) - ref['abs_sum']):.3e}, bound {bound:.3e}")
+    assert abs(float(b["noise_abs_sum"]) - ref["abs_sum"]) <= bound
+    assert abs(got["mean_noise_magnitude"] - ref["fsum_mean"]) <= bound / n + 2.0 ** -52 * ref["fsum_mean"]
+
+
+def test_labels_by_grid_is_the_plans_dictionary(pairs, truths):
+    ref, t = pairs["odd"][3], truths["odd"]
+    got = list(t.labels_by_grid())
+    assert [k for k, _ in got] == list(ref["labels_by_grid"])
+    for k, g in got:
+        w = ref["labels_by_grid"][k]
+        assert np.array_equal(g["labels"], w["labels"]) and _same_difference(g["difference"], w["difference"])
+        assert g["resolution"] == w["resolution"] and g["dimensions"] == w["dimensions"]
+
+
+def test_two_calls_give_equal_bits(pairs, truths, gpu_device):
+    from bathymetric_gnn_amd.data import compute_ground_truth_native
+    clean, noisy = pairs["even"][:2]
+    a, b = truths["even"], compute_ground_truth_native(clean, noisy, device=gpu_device)
+    for name in ("labels", "difference", "noisy_depth", "uncertainty", "mask", "grid_counts", "stats_block"):
+        x, y = getattr(a, name).cpu().numpy(), getattr(b, name).cpu().numpy()
+        assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), name
+
+
+def test_past_one_tile_per_workgroup(gpu_device):
+    """More than 2048 tiles: a workgroup owns a run of several and carries its place in the table from one to the next; a run of
+    one- and two-cell grids puts more than 256 grids into one tile."""
+    from bathymetric_gnn_amd import runtime
+    from bathymetric_gnn_amd.data import compute_ground_truth_native
+    clean, noisy = make_scale_pair()
+    ref = native_truth_cpu(clean, noisy)
+    total = int(ref["offsets"][-1])
+    tile = runtime.VT_TILE_CELLS
+    assert total > 2048 * tile and total % tile != 0
+    per_tile = np.bincount(ref["offsets"][:-1] // tile)
+    assert per_tile.max() > 256 and (~ref["paired"]).sum() > 20 and ref["stats"]["noise_cells"] > 10 ** 4
+    t = compute_ground_truth_native(clean, noisy, device=gpu_device)
+    assert np.array_equal(t.labels.cpu().numpy(), ref["labels"]) and np.array_equal(t.mask.cpu().numpy(), ref["mask"])
+    assert _same_difference(t.difference.cpu().numpy(), ref["difference"])
+    assert np.array_equal(_bits(t.noisy_depth.cpu().numpy()), _bits(ref["noisy_depth"]))
+    assert np.array_equal(_bits(t.uncertainty.cpu().numpy()), _bits(ref["uncertainty"]))
+    assert np.array_equal(t.grid_counts.cpu().numpy(), ref["grid_counts"])
+    got, want = t.stats(), ref["stats"]
+    for k in ("grids_processed", "valid_cells", "noise_cells", "seafloor_cells", "max_noise_magnitude", "median_noise_magnitude"):
+        assert got[k] == want[k], k
+    assert abs(float(t.block()["noise_abs_sum"]) - want["abs_sum"]) <= want["noise_cells"] * 2.0 ** -52 * want["abs_sum"]
+
+
+def test_a_pair_of_empty_files(gpu_device):
+    from bathymetric_gnn_amd.data import VRBagHandler, compute_ground_truth_native
+    from bathymetric_gnn_amd.data.vr_bag import VARRES_METADATA_DTYPE, VARRES_REFINEMENT_DTYPE
+    md = np.zeros((2, 2), VARRES_METADATA_DTYPE)
+    empty = VRBagHandler.from_arrays(md, np.empty((1, 0), VARRES_REFINEMENT_DTYPE))
+    t = compute_ground_truth_native(empty, empty, device=gpu_device)
+    assert t.labels.numel() == 0 and t.grid_counts.shape == (0, 4) and len(t) == 0 and t.offsets.tolist() == [0]
+    s = t.stats()
+    assert s["valid_cells"] == 0 and s["noise_cells"] == 0 and s["grids_processed"] == 0 and s["noise_percentage"] == 0.0
+    assert "median_noise_magnitude" not in s and math.isnan(float(t.block()["noise_abs_median"]))
+    assert list(t.labels_by_grid()) == []
+
+
+# ---- the training store ------------------------------------------------------------------------------------------------------
+def _host_store(refs, ratio, device):
+    """``TileStore("ground_truth", ...)`` of the kept grids, assembled on the host from restatements."""
+    from bathymetric_gnn_amd.training import TileStore
+    planes = {k: [] for k in ("noisy_depth", "mask", "uncertainty", "labels", "difference")}
+    hw, res, kept, counts = [], [], [], {0: 0, 1: 0, 2: 0}
+    for ref in refs:
+        cells = np.diff(ref["offsets"])
+        keep = ref["paired"] & (ref["grid_counts"][:, 0] >= 1) & (ref["grid_counts"][:, 0] / cells >= ratio)
+        keep &= ref["hw"].min(axis=1) >= 2            # (a grid of one cell a side has no gradient features: no graph)
+        kept.append(np.nonzero(keep)[0])
+        for g in kept[-1]:
+            a, b = ref["offsets"][g], ref["offsets"][g + 1]
+            for k in planes:
+                planes[k].append(ref[k][a:b])
+            hw.append(ref["hw"][g]); res.append(ref["res"][g])
+            for c in counts:
+                counts[c] += int(ref["grid_counts"][g, 1 + c])
+    dev = {k: torch.from_numpy(np.concatenate(v)).to(device) for k, v in planes.items()}
+    store = TileStore("ground_truth", np.array(hw), np.array(res), dev["noisy_depth"], dev["mask"], dev["uncertainty"],
+                      labels=dev["labels"], difference=dev["difference"], class_counts=counts, device=device)
+    return store, kept
+
+
+def _same_store(a, b):
+    assert np.array_equal(a.hw, b.hw) and np.array_equal(a.res, b.res) and np.array_equal(a.offsets, b.offsets)
+    assert a.kind == b.kind == "ground_truth" and a.uniform == b.uniform and a._class_counts == b._class_counts
+    for name in ("depth", "mask", "unc", "labels"):
+        x, y = getattr(a, name).cpu().numpy(), getattr(b, name).cpu().numpy()
+        assert x.dtype == y.dtype and np.array_equal(x.view(np.uint8), y.view(np.uint8)), name
+    assert _same_difference(a.difference.cpu().numpy(), b.difference.cpu().numpy())
+
+
+@pytest.mark.parametrize("ratio", [0.0, 0.5])
+def test_store_from_refinement_pairs_equals_the_host_store(ratio, pairs, truths, gpu_device):
+    from bathymetric_gnn_amd.training import TileStore
+    ref, t = pairs["odd"][3], truths["odd"]
+    got = TileStore.from_refinement_pairs(t, min_valid_ratio=ratio, device=gpu_device)
+    want, kept = _host_store([ref], ratio, gpu_device)
+    _same_store(got, want)
+    assert len(got.grids) == 1 and np.array_equal(got.grids[0], kept[0]) and (got.sources == 0).all()
+    cells = np.diff(ref["offsets"])
+    dropped_by_ratio = ref["paired"] & (ref["grid_counts"][:, 0] >= 1) & (ref["grid_counts"][:, 0] / cells < 0.5)
+    empty = ref["paired"] & (ref["grid_counts"][:, 0] == 0)
+    assert dropped_by_ratio.any() and empty.any()                               # the two ratios keep different grids
+    narrow = ref["paired"] & ~empty & (ref["hw"].min(axis=1) < 2)
+    assert narrow.any() and not (narrow & dropped_by_ratio).any()
+    assert len(got) == len(kept[0]) == ref["paired"].sum() - empty.sum() - narrow.sum() - (dropped_by_ratio.sum() if ratio == 0.5 else 0)
+    assert got.in_channels == 8
+    graph, targets = got.batch([0, len(got) - 1, 1])
+    assert graph.num_nodes == int(got.mask[got.offsets[0]:got.offsets[1]].sum() + got.mask[got.offsets[-2]:].sum()
+                                  + got.mask[got.offsets[1]:got.offsets[2]].sum())
+
+
+def test_store_from_two_truths_and_from_nothing(pairs, truths, gpu_device):
+    from bathymetric_gnn_amd.data import VRBagHandler, compute_ground_truth_native
+    from bathymetric_gnn_amd.training import TileStore
+    got = TileStore.from_refinement_pairs([truths["odd"], truths["ties"]], min_valid_ratio=0.5, device=gpu_device)
+    want, kept = _host_store([pairs["odd"][3], pairs["ties"][3]], 0.5, gpu_device)
+    _same_store(got, want)
+    assert [g.tolist() for g in got.grids] == [k.tolist() for k in kept]
+    assert got.sources.tolist() == [0] * len(kept[0]) + [1] * len(kept[1])
+    with pytest.raises(ValueError, match="no grid"):
+        TileStore.from_refinement_pairs(truths["odd"], min_valid_ratio=1.5, device=gpu_device)
+    # a pair without a single twin: nothing is kept either
+    clean, noisy = pairs["odd"][:2]
+    md = clean.varres_metadata.copy()
+    md["dimensions_x"] = 0; md["dimensions_y"] = 0
+    lonely = compute_ground_truth_native(VRBagHandler.from_arrays(md, clean.varres_refinements), noisy, device=gpu_device)
+    assert not lonely.paired.any() and int(lonely.grid_counts.sum()) == 0 and lonely.stats()["grids_processed"] == 0
+    assert np.array_equal(_bits(lonely.noisy_depth.cpu().numpy()), _bits(pairs["odd"][3]["noisy_depth"]))
+    with pytest.raises(ValueError, match="no grid"):
+        TileStore.from_refinement_pairs(lonely, device=gpu_device)
+    with pytest.raises(TypeError, match="NativeGroundTruth"):
+        TileStore.from_refinement_pairs([object()], device=gpu_device)
+
+
+# ---- training and evaluation -------------------------------------------------------------------------------------------------
+def _model(in_channels):
+    from bathymetric_gnn_amd import synthetic
+    from bathymetric_gnn_amd.models import BathymetricGNN
+    sd = synthetic.synthetic_state_dict(in_channels=in_channels, hidden=32, num_layers=2, heads=2, seed=3)
+    m = BathymetricGNN(in_channels=in_channels, hidden_channels=32, num_gnn_layers=2, heads=2, dropout=0.1, edge_dim=3)
+    m.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
+    return m.cuda()
+
+
+def _one_epoch(truths, out_dir, gpu_device):
+    from bathymetric_gnn_amd.config import Config
+    from bathymetric_gnn_amd.training import TileStore, Trainer
+    train = TileStore.from_refinement_pairs(truths["odd"], device=gpu_device)
+    val = TileStore.from_refinement_pairs(truths["even"], min_valid_ratio=0.5, device=gpu_device)
+    cfg = Config()
+    cfg.training = {"batch_size": 2, "epochs": 1, "scheduler": "cosine"}
+    model = _model(train.in_channels)
+    t = Trainer(cfg, model, train, val, output_dir=out_dir, seed=11, batch_nodes=2000)
+    return t, model, t.train()
+
+
+def test_one_epoch_with_batch_nodes(truths, tmp_path, gpu_device):
+    t, model, hist = _one_epoch(truths, tmp_path / "a", gpu_device)
+    plan = t.step_plan(0)
+    cells = np.diff(t.train_store.offsets)
+    assert 1 < len(plan) < len(t.train_store) and all(cells[p].sum() <= 2000 or len(p) == 1 for p, _ in plan)
+    assert any(len(p) == 1 and cells[p[0]] > 2000 for p, _ in plan)               # the 50 x 53 grid trains alone
+    assert sorted(i for p, _ in plan for i in p.tolist()) == list(range(len(t.train_store)))
+    assert [len(hist[k]) for k in ("train_loss", "val_loss", "train_acc", "val_acc")] == [1, 1, 1, 1]
+    assert all(math.isfinite(hist[k][0]) for k in hist)
+    for name, p in model.named_parameters():
+        assert p.grad is not None and bool(torch.isfinite(p.grad).all()), name
+    _, _, again = _one_epoch(truths, tmp_path / "b", gpu_device)
+    assert {k: [np.float64(v).tobytes() for v in vs] for k, vs in again.items()} == \
+        {k: [np.float64(v).tobytes() for v in vs] for k, vs in hist.items()}
+
+
+def test_evaluate_against_a_classified_bag(gpu_device):
+    """On the pair with grids of at least two cells a side: a narrower grid cannot be classified."""
+    from bathymetric_gnn_amd import synthetic
+    from bathymetric_gnn_amd.data import GraphBuilder, compute_ground_truth_native
+    from bathymetric_gnn_amd.models import BathymetricGNN
+    from bathymetric_gnn_amd.scripts.inference_native import NativeVRProcessor
+    from bathymetric_gnn_amd.training.evaluation import compute_metrics
+    clean, noisy, _ = make_pair("odd", lo=2)
+    ref, t = native_truth_cpu(clean, noisy), compute_ground_truth_native(clean, noisy, device=gpu_device)
+    assert ref["hw"].min() >= 2 and np.array_equal(t.labels.cpu().numpy(), ref["labels"]) and (ref["labels"] == 2).sum() > 20
+    sd = synthetic.synthetic_state_dict(in_channels=8, num_layers=2, seed=5)
+    model = BathymetricGNN(in_channels=8, num_gnn_layers=2, edge_dim=3)
+    model.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
+    proc = NativeVRProcessor(model.to(gpu_device).eval(), GraphBuilder(device=gpu_device), gpu_device)
+    _, res = proc.process_refinements(noisy, return_results=True)
+    assert res.shape == (3, t.labels.numel()) == (3, len(ref["labels"]))
+    got = t.evaluate(res[0], res[1])
+    want = compute_metrics(ref["labels"], res[0], res[1], device=gpu_device)
+    assert got == want and got["total_samples"] > 0 and "confidence" in got
+    assert t.evaluate(torch.from_numpy(res[0]).to(gpu_device)) == compute_metrics(ref["labels"], res[0], device=gpu_device)
+    with pytest.raises(ValueError, match="number of cells"):
+        t.evaluate(res[0][:-1])
