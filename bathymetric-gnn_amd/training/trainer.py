@@ -239,10 +239,14 @@ class TileStore:
     and of its ``GroundTruthDataset`` (label / difference / noisy-depth planes).  ``batch`` turns a list of tile indices into the
     batch's graph and the target dict of ``BathymetricGNNLoss``, without leaving the device.  ``from_ground_truths`` and
     ``from_survey`` build the store from planes that already lie in HBM (include/bgnn_tilestore.h: a scan of the candidate boxes, a
-    gather of the kept ones); the other constructors plan on the host."""
+    gather of the kept ones); the other constructors plan on the host.
+
+    ``node_counts`` (host int64, one per tile): the valid cells of every tile, which are its graph's nodes.  Every constructor
+    fills it from counts it has on the host anyway (the masks of ``from_tiles``, the scan counts, a truth's ``grid_counts``); a
+    store assembled by hand may leave it None.  ``Trainer`` plans its steps with it (``step_plan``)."""
 
     def __init__(self, kind: str, hw, res, depth, mask, unc=None, labels=None, difference=None, class_counts=None,
-                 graph_builder=None, noise_generator=None, augment: bool = True, seed: int = 0, device=None):
+                 graph_builder=None, noise_generator=None, augment: bool = True, seed: int = 0, device=None, node_counts=None):
         from ..data import GraphBuilder, NoiseAugmentor, SyntheticNoiseGenerator
         assert kind in ("synthetic", "ground_truth")
         self.kind = kind
@@ -256,6 +260,10 @@ class TileStore:
             if t is not None and t.numel() != int(self.offsets[-1]):
                 raise ValueError("tile table and planes disagree on the number of cells")
         self.uniform = len(self.hw) > 0 and bool((self.hw == self.hw[0]).all())
+        # the valid cells (= graph nodes) of every tile, on the host: what the constructors counted anyway (None: not known)
+        self.node_counts = None if node_counts is None else np.ascontiguousarray(node_counts, np.int64).reshape(-1)
+        if self.node_counts is not None and len(self.node_counts) != len(self.hw):
+            raise ValueError("tile table and node counts disagree on the number of tiles")
         self.seed = int(seed)
         self.graph_builder = graph_builder if graph_builder is not None else GraphBuilder(device=self.device)
         self.augment = bool(augment)
@@ -282,7 +290,11 @@ class TileStore:
             raise ValueError("a TileStore needs at least one tile")
         resolutions = [(1.0, 1.0)] * n if resolutions is None else list(resolutions)
         hw, res, d, m, u = gb.upload_tiles(list(depths), None if valid_masks is None else list(valid_masks), uncertainties, resolutions)
-        return cls("synthetic", hw, res, d.to(device), m.to(device), None if u is None else u.to(device), device=device, **kw)
+        masks = [None] * n if valid_masks is None else list(valid_masks)
+        nodes = [int(np.count_nonzero(np.isfinite(np.asarray(t, dtype=np.float32)) if v is None else np.asarray(v, dtype=bool)))
+                 for t, v in zip(depths, masks)]                               # (the masks upload_tiles stores)
+        return cls("synthetic", hw, res, d.to(device), m.to(device), None if u is None else u.to(device), device=device,
+                   node_counts=nodes, **kw)
 
     @classmethod
     def from_grid(cls, grid, tile_manager, device=None, **kw) -> "TileStore":
@@ -330,7 +342,8 @@ class TileStore:
         hw = np.array([(r1 - r0, c1 - c0) for r0, c0, r1, c1 in boxes], np.int32)
         res = np.array([(float(resolution[0]), float(resolution[1]))] * len(boxes), np.float64)
         store = cls("ground_truth", hw, res, flat["depth"], (flat["labels"] >= 0).view(torch.uint8), flat.get("unc"),
-                    labels=flat["labels"], difference=flat["difference"], class_counts=counts, device=device, **kw)
+                    labels=flat["labels"], difference=flat["difference"], class_counts=counts, device=device,
+                    node_counts=[int(np.count_nonzero(labels[r0:r1, c0:c1] >= 0)) for r0, c0, r1, c1 in boxes], **kw)
         store.boxes = boxes
         return store
 
@@ -383,7 +396,10 @@ class TileStore:
             r["counts"] = scan_tile_boxes(r["planes"][0], r["candidates"], ctx=ctx)
         class_counts = {0: 0, 1: 0, 2: 0}
         for r in scanned:
-            r["boxes"], counts = keep_ground_truth_boxes(r["candidates"], r["counts"].cpu().numpy(), min_valid_ratio)
+            scan = r["counts"].cpu().numpy()
+            r["boxes"], counts = keep_ground_truth_boxes(r["candidates"], scan, min_valid_ratio)
+            r["nodes"] = [int(row[0]) for (r0, c0, r1, c1), row in zip(r["candidates"], scan)      # (the keep rule, on the same rows)
+                          if int(row[0]) / ((r1 - r0) * (c1 - c0)) >= min_valid_ratio]
             for c in class_counts:
                 class_counts[c] += counts[c]
             if not r["boxes"]:
@@ -406,7 +422,7 @@ class TileStore:
             first += n
         res = np.array([r["res"] for r in scanned for _ in r["boxes"]], np.float64)
         store = cls("ground_truth", hw, res, stores[2], mask, stores[3], labels=stores[0], difference=stores[1],
-                    class_counts=class_counts, device=device, **kw)
+                    class_counts=class_counts, device=device, node_counts=[v for r in scanned for v in r["nodes"]], **kw)
         store.boxes = boxes
         store.sources = np.array([r["index"] for r in scanned for _ in r["boxes"]], np.int32)
         return store
@@ -439,8 +455,9 @@ class TileStore:
         _, _, specs = tile_manager.compute_tile_grid(tuple(planes[0].shape))
         candidates = [(s.row_start, s.col_start, s.row_end, s.col_end) for s in specs]
         counts = scan_tile_boxes(planes[0], candidates, nodata=nodata_value, ctx=ctx).cpu().numpy()
-        boxes = [b for b, row in zip(candidates, counts)
-                 if not int(row[0]) / ((b[2] - b[0]) * (b[3] - b[1])) < tile_manager.min_valid_ratio]
+        kept = [(b, int(row[0])) for b, row in zip(candidates, counts)
+                if not int(row[0]) / ((b[2] - b[0]) * (b[3] - b[1])) < tile_manager.min_valid_ratio]
+        boxes = [b for b, _ in kept]
         if not boxes:
             raise ValueError("a TileStore needs at least one tile")
         hw = np.array([(r1 - r0, c1 - c0) for r0, c0, r1, c1 in boxes], np.int32)
@@ -451,7 +468,7 @@ class TileStore:
         mask = torch.empty(cells, dtype=torch.uint8, device=device)
         cut_tile_boxes(planes, stores, boxes, offsets[:-1], mask=mask, mask_plane=0, nodata=nodata_value, ctx=ctx)
         res = np.array([(float(resolution[0]), float(resolution[1]))] * len(boxes), np.float64)
-        store = cls("synthetic", hw, res, stores[0], mask, stores[1], device=device, **kw)
+        store = cls("synthetic", hw, res, stores[0], mask, stores[1], device=device, node_counts=[v for _, v in kept], **kw)
         store.boxes = boxes
         return store
 
@@ -480,13 +497,14 @@ class TileStore:
         if len({t.uncertainty is None for t in truths}) > 1:
             raise ValueError("some truths carry an uncertainty and some carry none: the graphs would differ in in_channels")
         host_counts = [t.grid_counts.cpu().numpy().reshape(-1, rt.TILE_COUNTS) for t in truths]      # (the only read-back)
-        kept, class_counts = [], {0: 0, 1: 0, 2: 0}
+        kept, nodes, class_counts = [], [], {0: 0, 1: 0, 2: 0}
         for t, cnt in zip(truths, host_counts):
             cells = np.diff(t.offsets)
             valid = cnt[:, 0]
             keep = np.asarray(t.paired, bool) & (valid >= 1) & (valid / np.maximum(cells, 1) >= min_valid_ratio) & \
                 (t.hw.min(axis=1) >= 2)
             kept.append(np.nonzero(keep)[0].astype(np.int64))
+            nodes.append(valid[keep])
             for c in class_counts:
                 class_counts[c] += int(cnt[keep, 1 + c].sum())
         if sum(len(k) for k in kept) == 0:
@@ -510,7 +528,7 @@ class TileStore:
             cut_tile_boxes(planes, stores, boxes, offsets[first:first + len(k)], mask=mask, mask_plane=0, ctx=ctx)
             first += len(k)
         store = cls("ground_truth", hw, res, stores[2], mask, stores[3], labels=stores[0], difference=stores[1],
-                    class_counts=class_counts, device=device, **kw)
+                    class_counts=class_counts, device=device, node_counts=np.concatenate(nodes), **kw)
         store.grids = kept
         store.sources = np.concatenate([np.full(len(k), i, np.int32) for i, k in enumerate(kept)])
         return store
@@ -701,12 +719,18 @@ class Trainer:
 
     ``batch_nodes`` (None: steps of ``batch_size`` tiles, as the reference cuts them): steps cut by cell count instead, for stores
     whose tiles differ widely in size (``TileStore.from_refinement_pairs``: refinement grids of 9 to 2500 cells); see
-    ``step_plan``."""
+    ``step_plan``.  Under either rule a step whose tiles would hold fewer than two nodes is joined to a neighbouring step, which
+    may then pass ``batch_nodes`` by that tile's cells; a training store whose tiles hold fewer than two nodes altogether raises
+    ``ValueError`` here."""
 
     def __init__(self, config, model, train_store: TileStore, val_store: Optional[TileStore] = None, output_dir=None,
                  seed: int = 0, batch_nodes: Optional[int] = None):
         if batch_nodes is not None and int(batch_nodes) < 1:
             raise ValueError(f"batch_nodes {batch_nodes}: a positive number of cells, or None")
+        nodes = getattr(train_store, "node_counts", None)
+        if nodes is not None and int(np.sum(nodes)) < 2:
+            raise ValueError(f"the training store's {len(train_store)} tiles hold {int(np.sum(nodes))} node(s) altogether: a training "
+                             "step needs at least 2 (BatchNorm's batch statistics)")
         self.batch_nodes = None if batch_nodes is None else int(batch_nodes)
         self.config = config
         self.model = model
@@ -819,21 +843,38 @@ class Trainer:
             return None, 1.0
 
     # ---- the plan of an epoch --------------------------------------------------------------------------------------------
-    def _pieces(self, store, order: np.ndarray) -> List[np.ndarray]:
+    def _pieces(self, store, order: np.ndarray, trainable: bool = False) -> List[np.ndarray]:
         """``order`` cut into the tile lists of consecutive steps: ``batch_size`` tiles each, or, with ``batch_nodes``, greedily by
-        the tiles' cell counts."""
+        the tiles' cell counts.  ``trainable``: no piece may hold fewer than two nodes (BatchNorm's batch statistics need two
+        rows, and ``train()`` refuses one); such a piece is joined to the piece before it, the first one to the piece after
+        it, and every other piece stays as it was cut.  Needs ``store.node_counts``; without them the cut stands."""
         limit = getattr(self, "batch_nodes", None)
         if limit is None:
             bs = max(1, int(self.settings.batch_size))
-            return [order[k:k + bs] for k in range(0, len(order), bs)]
-        cells = np.diff(np.asarray(store.offsets, dtype=np.int64))[order].tolist()
-        cuts, run = [0], 0
-        for k, c in enumerate(cells):
-            if k > cuts[-1] and run + c > limit:
-                cuts.append(k); run = 0
-            run += c
-        cuts.append(len(cells))
-        return [order[a:b] for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+            pieces = [order[k:k + bs] for k in range(0, len(order), bs)]
+        else:
+            cells = np.diff(np.asarray(store.offsets, dtype=np.int64))[order].tolist()
+            cuts, run = [0], 0
+            for k, c in enumerate(cells):
+                if k > cuts[-1] and run + c > limit:
+                    cuts.append(k); run = 0
+                run += c
+            cuts.append(len(cells))
+            pieces = [order[a:b] for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+        nodes = getattr(store, "node_counts", None) if trainable else None
+        if nodes is None or len(pieces) < 2:
+            return pieces
+        nodes = np.asarray(nodes, dtype=np.int64)
+        joined: List[np.ndarray] = []
+        for p in pieces:
+            if joined and int(nodes[p].sum()) < 2:
+                joined[-1] = np.concatenate([joined[-1], p])
+            else:
+                joined.append(p)
+        if len(joined) > 1 and int(nodes[joined[0]].sum()) < 2:
+            joined[1] = np.concatenate([joined[0], joined[1]])
+            del joined[0]
+        return joined
 
     def step_plan(self, epoch: int, validation: bool = False) -> List[Tuple[np.ndarray, Optional[int]]]:
         """``(tile indices, dropout seed)`` of every step of epoch ``epoch``.  Training: the tiles in the order
@@ -845,12 +886,19 @@ class Trainer:
 
         With ``batch_nodes`` set the same order is cut greedily by cell count instead: a piece closes before the tile that would
         take its cells (``store.offsets`` differences) above ``batch_nodes``; a tile larger than that forms a piece alone.  Seeds
-        are numbered by piece, as above."""
+        are numbered by piece, as above.
+
+        Under either rule a training piece whose tiles hold fewer than two nodes in total (``store.node_counts``: a refinement
+        grid with one valid cell, a last piece of one such tile) cannot train -- ``train()`` needs two rows for BatchNorm's batch
+        statistics -- and is joined to the piece before it, or, when it is the first, to the piece after it.  A joined piece may
+        therefore pass ``batch_size`` by those tiles and ``batch_nodes`` by their cells; every other piece is as the rule cut it,
+        and the seeds are numbered over the pieces that remain.  Validation plans are not joined (``eval()`` takes one node), and
+        neither is the plan over a store that carries no node counts."""
         store = self.val_store if validation else self.train_store
         n = len(store)
         order = np.arange(n, dtype=np.int64) if validation else \
             np.random.default_rng([self.seed, int(epoch)]).permutation(n).astype(np.int64)
-        pieces = self._pieces(store, order)
+        pieces = self._pieces(store, order, trainable=not validation)
         if validation:
             return [(p, None) for p in pieces]
         return [(p, dropout_seed(self.seed, int(epoch) * len(pieces) + k)) for k, p in enumerate(pieces)]

@@ -181,6 +181,111 @@ def make_pair(variant="odd", seed=7, lo=1):
     return clean_h, noisy_h, cases
 
 
+TRAINING_RESOLUTIONS = [(0.5, 0.5), (1.0, 2.0), (3.7, 0.25), (2.0, 2.0), (0.25, 4.0)]
+
+
+def make_training_pair(seed=0):
+    """A clean / noisy pair shaped like a VR training batch, both files with an uncertainty, and the base cells of its cases.
+    From ``synthetic_vr_bag(4, 5, lo=2, hi=9)``, with these grids set by hand:
+
+    ``big``         24 x 31 cells, spikes of +-0.3 .. 2 m on about 5 % of them, nodata on about 1 % (in either file)
+    ``g22``         2 x 2: the noisy file constant, the clean file 0.75 m deeper (local_std 0, every quotient below -cap)
+    ``g29``, ``g92``  2 x 9 and 9 x 2: every gradient feature along the short side is one-sided
+    ``sparse``      3 x 4 with one valid cell, 0.75 m off its twin: an isolated node, local_std 0, the quotient above +cap
+    ``flat``        7 x 7 of constant depth with one spike at a corner of the noisy file: local_std 0 three cells away from it
+    ``no_twin``     dropped from the clean file; ``transposed``: other dimensions in the noisy file -- neither reaches a store
+    Of the remaining grids those are kept, in index order, whose cells add up to at most 150, so that every grid but ``big``
+    holds fewer than 256 cells together; they get jitter of +-0.05 m on about 20 % of their cells and spikes on about 10 %.
+    Resolutions: ``TRAINING_RESOLUTIONS`` round-robin over the grids a store keeps, in the noisy file's order."""
+    rng = np.random.default_rng([seed, 77])
+    md, ref = synthetic.synthetic_vr_bag(4, 5, seed=1000 + seed, lo=2, hi=9, empty_fraction=0.0, sparse_fraction=0.0)
+    clean = bag_grids(md, ref)
+    keys = sorted(clean)
+    assert len(keys) >= 11, len(keys)
+    names = ("g29", "flat", "big", "no_twin", "sparse", "g22", "transposed", "g92")
+    cases = dict(zip(names, keys[:len(names)]))
+    budget, extras = 150, []
+    for k in keys[len(names):]:
+        if clean[k][0].size <= budget:
+            extras.append(k); budget -= clean[k][0].size
+        else:
+            del clean[k]
+    assert len(extras) >= 3, extras
+
+    def put(name, depth, unc=None):
+        k = cases[name]
+        depth = np.ascontiguousarray(depth, np.float32)
+        unc = np.full(depth.shape, 0.25, np.float32) if unc is None else unc
+        clean[k] = [depth, unc, clean[k][2], clean[k][3]]
+    put("big", 20.0 + rng.random((24, 31)) * 5, (0.05 + 0.25 * rng.random((24, 31))).astype(np.float32))
+    put("g22", np.full((2, 2), 10.25))
+    put("g29", 14.0 + rng.random((2, 9)))
+    put("g92", 16.0 + rng.random((9, 2)))
+    put("sparse", np.full((3, 4), NODATA))
+    clean[cases["sparse"]][0][1, 2] = 15.0
+    put("flat", np.full((7, 7), 12.0))
+    if clean[cases["transposed"]][0].shape[0] == clean[cases["transposed"]][0].shape[1]:
+        put("transposed", 18.0 + rng.random((3, 5)))
+    noisy = {k: [v[0].copy(), v[1] + np.float32(0.125), v[2], v[3]] for k, v in clean.items()}
+    for k in [cases["big"], cases["g29"], cases["g92"]] + extras:
+        d = noisy[k][0]
+        valid = d != NODATA
+        jitter = (rng.random(d.shape) < 0.2) & valid
+        d[jitter] += rng.uniform(-0.05, 0.05, int(jitter.sum())).astype(np.float32)
+        spike = (rng.random(d.shape) < (0.05 if k == cases["big"] else 0.1)) & valid & ~jitter
+        d[spike] += (rng.choice([-1.0, 1.0], int(spike.sum())) * rng.uniform(0.3, 2.0, int(spike.sum()))).astype(np.float32)
+    for file in (clean, noisy):                                                # nodata on about 1 % of the big grid, in either file
+        file[cases["big"]][0][rng.random((24, 31)) < 0.005] = NODATA
+    noisy[cases["g22"]][0][:] = 9.5
+    noisy[cases["sparse"]][0][1, 2] = 15.75
+    noisy[cases["flat"]][0][0, 0] = 13.0
+    del clean[cases["no_twin"]]
+    d, u, res, sw = noisy[cases["transposed"]]
+    noisy[cases["transposed"]] = [np.ascontiguousarray(d.T), np.ascontiguousarray(u.T), res, sw]
+    kept = [k for k in sorted(noisy) if k not in (cases["no_twin"], cases["transposed"])]
+    for i, k in enumerate(kept):
+        res = TRAINING_RESOLUTIONS[i % len(TRAINING_RESOLUTIONS)]
+        clean[k][2] = noisy[k][2] = res
+    return assemble_bag((4, 5), clean, reverse_records=True), assemble_bag((4, 5), noisy), cases
+
+
+def make_isolated_pair():
+    """Two grids with one valid cell each, at different anisotropic resolutions: the smallest batch ``train()`` takes.  One
+    cell is noise (0.75 m off its twin), the other seafloor."""
+    clean, noisy = {}, {}
+    for key, shape, at, depth, off, res in (((0, 0), (3, 4), (1, 2), 15.0, 0.75, (1.0, 2.0)), ((0, 1), (5, 2), (4, 0), 22.5, 0.0, (3.7, 0.25))):
+        d = np.full(shape, NODATA, np.float32)
+        d[at] = depth
+        z = d.copy()
+        z[at] = depth + off
+        u = np.full(shape, 0.25, np.float32)
+        clean[key] = [d, u, res, (0.5, 0.5)]
+        noisy[key] = [z, u + np.float32(0.125 * (1 + key[1])), res, (0.5, 0.5)]
+    return assemble_bag((1, 2), clean), assemble_bag((1, 2), noisy)
+
+
+def store_batch_cpu(ref, kept, indices, resolutions):
+    """The oracle's batch of the store tiles ``indices`` (``kept[i]``: the grid of ``native_truth_cpu``'s planes behind store tile
+    ``i``; ``resolutions[i]`` its resolution): one ``graph_cpu.build_graph(noisy_depth, labels >= 0, uncertainty, res)`` per tile in
+    that order, then ``graph_cpu.batch_graphs``.  ``labels`` / ``difference``: per node, the valid cells row-major, grid after
+    grid; ``nodes``: the node count of every tile."""
+    from oracle import graph_cpu
+    graphs, labels, difference = [], [], []
+    for i in indices:
+        g = int(kept[int(i)])
+        a, b = int(ref["offsets"][g]), int(ref["offsets"][g + 1])
+        shape = tuple(int(v) for v in ref["hw"][g])
+        lab = ref["labels"][a:b].reshape(shape)
+        valid = lab >= 0
+        res = (float(resolutions[int(i)][0]), float(resolutions[int(i)][1]))
+        graphs.append(graph_cpu.build_graph(ref["noisy_depth"][a:b].reshape(shape), valid, ref["uncertainty"][a:b].reshape(shape), res))
+        labels.append(lab[valid]); difference.append(ref["difference"][a:b].reshape(shape)[valid])
+    x, ei, ea, ls, batch = graph_cpu.batch_graphs(graphs)
+    return {"x": x, "edge_index": ei, "edge_attr": ea, "local_std": ls, "batch": batch,
+            "pos": np.concatenate([g.pos for g in graphs], 0), "nodes": np.array([g.num_nodes for g in graphs], np.int64),
+            "labels": np.concatenate(labels), "difference": np.concatenate(difference)}
+
+
 def make_scale_pair(seed=3):
     """A pair past 2 * 2048 tiles of 1024 cells, so that a workgroup of the label pass walks from tile to tile: a 45 x 60 base
     grid, every cell refined, 20 .. 60 cells a side, except a run of 700 base cells of 1 x 1 and 1 x 2 grids (more than 256 grids

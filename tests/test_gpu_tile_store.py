@@ -63,9 +63,18 @@ def _assert_planes_equal(store, want):
         assert torch.equal(_bits(got), _bits(ref)), k
 
 
+def _assert_node_counts(store):
+    """``node_counts``: the valid cells of every tile, as the store's own mask holds them; host int64."""
+    csum = np.concatenate([[0], np.cumsum(store.mask.cpu().numpy().astype(np.int64))])
+    assert isinstance(store.node_counts, np.ndarray) and store.node_counts.dtype == np.int64
+    assert np.array_equal(store.node_counts, csum[store.offsets[1:]] - csum[store.offsets[:-1]])
+
+
 def _assert_store_is(store, hosts):
     """``store`` is the concatenation of the host-built stores ``hosts``."""
     assert len(store) == sum(len(h) for h in hosts)
+    for s in [store] + list(hosts):
+        _assert_node_counts(s)
     assert np.array_equal(store.hw, np.concatenate([h.hw for h in hosts])) and store.hw.dtype == np.int32
     assert np.array_equal(store.res, np.concatenate([h.res for h in hosts])) and store.res.dtype == np.float64
     cells = np.concatenate([[0]] + [np.diff(h.offsets) for h in hosts]).cumsum()
@@ -267,6 +276,7 @@ def _assert_survey_store_is(store, ref):
     assert np.array_equal(store.hw, ref.hw) and store.hw.dtype == ref.hw.dtype
     assert np.array_equal(store.res, ref.res) and np.array_equal(store.offsets, ref.offsets) and store.uniform == ref.uniform
     _assert_planes_equal(store, {k: [getattr(ref, k)] for k in PLANES})
+    _assert_node_counts(store); _assert_node_counts(ref)
 
 
 @pytest.mark.parametrize("with_unc", [False, True])

@@ -261,7 +261,7 @@ def _model(in_channels):
     return m.cuda()
 
 
-def _one_epoch(truths, out_dir, gpu_device):
+def _one_epoch(truths, out_dir, gpu_device, seed=11):
     from bathymetric_gnn_amd.config import Config
     from bathymetric_gnn_amd.training import TileStore, Trainer
     train = TileStore.from_refinement_pairs(truths["odd"], device=gpu_device)
@@ -269,7 +269,7 @@ def _one_epoch(truths, out_dir, gpu_device):
     cfg = Config()
     cfg.training = {"batch_size": 2, "epochs": 1, "scheduler": "cosine"}
     model = _model(train.in_channels)
-    t = Trainer(cfg, model, train, val, output_dir=out_dir, seed=11, batch_nodes=2000)
+    t = Trainer(cfg, model, train, val, output_dir=out_dir, seed=seed, batch_nodes=2000)
     return t, model, t.train()
 
 
@@ -287,6 +287,23 @@ def test_one_epoch_with_batch_nodes(truths, tmp_path, gpu_device):
     _, _, again = _one_epoch(truths, tmp_path / "b", gpu_device)
     assert {k: [np.float64(v).tobytes() for v in vs] for k, vs in again.items()} == \
         {k: [np.float64(v).tobytes() for v in vs] for k, vs in hist.items()}
+    # seed 8: the cut by cells alone leaves the grid with one valid cell in a step of its own, which train() refuses; the plan
+    # joins it to a neighbouring step
+    t8, model8, hist8 = _one_epoch(truths, tmp_path / "c", gpu_device, seed=8)
+    nodes = t8.train_store.node_counts
+    one = int(np.nonzero(nodes == 1)[0][0])
+    order = np.random.default_rng([8, 0]).permutation(len(nodes)).tolist()
+    cut, run = [[]], 0
+    for i in order:
+        if cut[-1] and run + cells[i] > 2000:
+            cut.append([]); run = 0
+        cut[-1].append(i); run += cells[i]
+    assert [one] in cut                                                          # alone, by cells
+    plan8 = [p.tolist() for p, _ in t8.step_plan(0)]
+    assert [one] not in plan8 and all(nodes[p].sum() >= 2 for p in plan8) and [i for p in plan8 for i in p] == order
+    assert all(math.isfinite(hist8[k][0]) for k in hist8)
+    for name, p in model8.named_parameters():
+        assert p.grad is not None and bool(torch.isfinite(p.grad).all()), name
 
 
 def test_evaluate_against_a_classified_bag(gpu_device):

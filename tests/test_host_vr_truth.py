@@ -138,6 +138,143 @@ def test_step_plan_without_batch_nodes_is_todays(batch_nodes):
     assert [p.tolist() for p, _ in t.step_plan(3, validation=True)] == [[0, 1], [2, 3], [4, 5], [6]]
 
 
+class _CountedStore(_Store):
+    """A store that also carries its tiles' node counts, as every ``TileStore`` constructor leaves them."""
+
+    def __init__(self, cells, nodes):
+        super().__init__(cells)
+        self.node_counts = np.asarray(nodes, np.int64)
+
+
+def _counted_trainer(cells, nodes, batch_nodes, seed, batch_size=2):
+    t = _stub_trainer(cells, batch_nodes, seed=seed, batch_size=batch_size)
+    t.train_store = t.val_store = _CountedStore(cells, nodes)
+    return t
+
+
+# make_pair("odd", lo=1) as TileStore.from_refinement_pairs keeps it: cells and valid cells of its 9 grids
+PAIR_CELLS = [45, 12, 2650, 25, 56, 9, 24, 72, 16]
+PAIR_NODES = [41, 12, 2644, 23, 1, 9, 23, 71, 16]
+ISOLATING = [(1, 1), (8, 0), (19, 1), (31, 2)]        # (seed, epoch) whose cut by 2000 cells leaves tile 4 (one node) alone
+
+
+def _joined_by_hand(old, nodes):
+    """The rule, restated on a list of pieces: a piece below two nodes goes to the piece before it, a first one to the next."""
+    out = []
+    for p in old:
+        if out and sum(nodes[i] for i in p) < 2:
+            out[-1] = out[-1] + p
+        else:
+            out.append(list(p))
+    if len(out) > 1 and sum(nodes[i] for i in out[0]) < 2:
+        out[1] = out[0] + out[1]
+        del out[0]
+    return out
+
+
+def test_the_listed_node_counts_are_the_pairs():
+    clean, noisy, _ = make_pair("odd", lo=1)
+    ref = native_truth_cpu(clean, noisy)
+    keep = ref["paired"] & (ref["grid_counts"][:, 0] >= 1) & (ref["hw"].min(axis=1) >= 2)
+    assert np.diff(ref["offsets"])[keep].tolist() == PAIR_CELLS and ref["grid_counts"][keep, 0].tolist() == PAIR_NODES
+
+
+@pytest.mark.parametrize("seed,epoch", [(s, e) for s in range(40) for e in range(3)])
+def test_no_training_step_of_one_node(seed, epoch):
+    """Over 40 seeds x 3 epochs: the cut of today isolates the one-node tile at exactly the four listed pairs; the plan never
+    does, is still the permutation, and differs from the cut only where a piece was joined to its neighbour."""
+    from bathymetric_gnn_amd.training.trainer import dropout_seed
+    old = [p.tolist() for p, _ in _stub_trainer(PAIR_CELLS, 2000, seed=seed).step_plan(epoch)]
+    t = _counted_trainer(PAIR_CELLS, PAIR_NODES, 2000, seed)
+    plan = t.step_plan(epoch)
+    new = [p.tolist() for p, _ in plan]
+    assert ([4] in old) == ((seed, epoch) in ISOLATING)
+    assert all(sum(PAIR_NODES[i] for i in p) >= 2 for p in new)
+    assert [i for p in new for i in p] == np.random.default_rng([seed, epoch]).permutation(9).tolist()
+    assert all(p.dtype == np.int64 for p, _ in plan)
+    assert [s for _, s in plan] == [dropout_seed(seed, epoch * len(new) + k) for k in range(len(new))]
+    if (seed, epoch) not in ISOLATING:
+        assert new == old
+        return
+    at = old.index([4])
+    if at > 0:                                            # to the piece before it ...
+        assert new == old[:at - 1] + [old[at - 1] + [4]] + old[at + 1:]
+    else:                                                 # ... a first piece to the one after it
+        assert new == [[4] + old[1]] + old[2:]
+    assert new == _joined_by_hand(old, PAIR_NODES) and len(new) == len(old) - 1
+    # validation keeps the cut: eval() takes one node
+    assert [p.tolist() for p, _ in t.step_plan(epoch, validation=True)] == \
+        [p.tolist() for p, _ in _stub_trainer(PAIR_CELLS, 2000, seed=seed).step_plan(epoch, validation=True)]
+
+
+def test_a_first_piece_of_one_node_joins_forward():
+    cells, nodes = [56, 1990, 30, 1990, 40], [1, 1900, 30, 1800, 0]
+    hit = None
+    for seed in range(200):
+        t = _counted_trainer(cells, nodes, 2000, seed)
+        old = [p.tolist() for p, _ in _stub_trainer(cells, 2000, seed=seed).step_plan(0)]
+        new = [p.tolist() for p, _ in t.step_plan(0)]
+        assert new == _joined_by_hand(old, nodes) and all(sum(nodes[i] for i in p) >= 2 for p in new)
+        if old[0] in ([0], [4], [0, 4], [4, 0]) and hit is None:
+            hit = seed
+            assert new[0] == old[0] + old[1] and new[1:] == old[2:]
+    assert hit is not None
+    # a one-node piece in the middle and an empty tile at the end, in store order
+    t = _counted_trainer([1990, 56, 1990, 40], [1900, 1, 1800, 0], 2000, 0)
+    assert [p.tolist() for p in t._pieces(t.train_store, np.arange(4), trainable=True)] == [[0, 1], [2, 3]]
+    assert [p.tolist() for p in t._pieces(t.train_store, np.arange(4))] == [[0], [1], [2], [3]]
+    # two pieces below two nodes in a row at the start: together they still cannot train, and go on to the next
+    t = _counted_trainer([1990, 1990, 1990], [1, 0, 50], 2000, 0)
+    assert [p.tolist() for p in t._pieces(t.train_store, np.arange(3), trainable=True)] == [[0, 1, 2]]
+
+
+def test_batch_size_rule_with_a_one_node_last_tile():
+    cells, nodes = [30] * 7, [20, 20, 20, 20, 20, 20, 1]
+    seen = 0
+    for seed in range(40):
+        t = _counted_trainer(cells, nodes, None, seed, batch_size=2)
+        order = np.random.default_rng([seed, 0]).permutation(7).tolist()
+        old = [order[k:k + 2] for k in range(0, 7, 2)]
+        new = [p.tolist() for p, _ in t.step_plan(0)]
+        if order[-1] == 6:
+            seen += 1
+            assert old[-1] == [6] and new == old[:2] + [old[2] + [6]]
+        else:
+            assert new == old
+    assert seen > 0
+
+
+def test_a_store_below_two_nodes_is_refused():
+    from bathymetric_gnn_amd.training.trainer import Trainer
+    with pytest.raises(ValueError, match=r"hold 1 node\(s\) altogether"):
+        Trainer(None, None, _CountedStore([56, 9, 16], [1, 0, 0]), batch_nodes=2000)
+    with pytest.raises(ValueError, match=r"hold 0 node\(s\) altogether"):
+        Trainer(None, None, _CountedStore([56], [0]))
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_training_pair_holds_its_cases(seed):
+    """``make_training_pair`` from the input alone: what the GPU tests of the VR training step rely on."""
+    from _vr_truth_cpu import TRAINING_RESOLUTIONS, make_training_pair
+    clean, noisy, cases = make_training_pair(seed)
+    ref = native_truth_cpu(clean, noisy)
+    place = {k: i for i, k in enumerate(ref["order"])}
+    hw = lambda name: tuple(ref["hw"][place[cases[name]]])
+    assert (hw("big"), hw("g22"), hw("g29"), hw("g92"), hw("flat")) == ((24, 31), (2, 2), (2, 9), (9, 2), (7, 7))
+    assert ref["grid_counts"][place[cases["sparse"]], 0] == 1 and ref["paired"][place[cases["sparse"]]]
+    assert not ref["paired"][place[cases["no_twin"]]] and not ref["paired"][place[cases["transposed"]]]
+    assert ref["paired"].sum() == len(ref["order"]) - 2 >= 9
+    keep = ref["paired"] & (ref["grid_counts"][:, 0] >= 1) & (ref["hw"].min(axis=1) >= 2)
+    assert keep.sum() == ref["paired"].sum()
+    want = [TRAINING_RESOLUTIONS[i % 5] for i in range(int(keep.sum()))]
+    assert np.array_equal(ref["res"][keep], np.array(want, np.float32).astype(np.float64))
+    small = keep.copy(); small[place[cases["big"]]] = False
+    assert 100 <= ref["grid_counts"][small, 0].sum() < 256
+    big = slice(int(ref["offsets"][place[cases["big"]]]), int(ref["offsets"][place[cases["big"]] + 1]))
+    lab = ref["labels"][big]
+    assert 0.03 < (lab == 2).mean() < 0.08 and 0.002 < (lab == -1).mean() < 0.03
+
+
 def test_ragged_gather_index_is_the_loop_it_replaced():
     """``TileStore._gather`` builds the cell index of a ragged batch without a loop over tiles: the same index."""
     rng = np.random.default_rng(0)
