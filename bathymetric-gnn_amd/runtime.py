@@ -341,6 +341,19 @@ TILE_BOX_DTYPE = np.dtype([("row0", "<i8"), ("col0", "<i8"), ("h", "<i4"), ("w",
 TILE_BOX_BYTES = TILE_BOX_DTYPE.itemsize
 
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_augment.h declares (tiles gathered under the symmetries of the square)
+_AUGMENT_SIGNATURES = {
+    "bgnn_tile_gather_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "bgnn_tile_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t]),
+}
+AUG_OPS = 8                                        # BGNN_AUG_OPS: op = k + 4 * f
+AUG_MAX_PLANES = 4                                 # BGNN_AUG_MAX_PLANES
+AUG_BLOCK = 64                                     # BGNN_AUG_BLOCK
+# bgnn_tile_entry (BGNN_AUG_ENTRY_BYTES = 32); h, w: the SOURCE tile
+TILE_ENTRY_DTYPE = np.dtype([("src", "<i8"), ("dst", "<i8"), ("h", "<i4"), ("w", "<i4"), ("op", "<i4"), ("pad", "<i4")])
+AUG_ENTRY_BYTES = TILE_ENTRY_DTYPE.itemsize
+
 
 # symbol -> (restype, argtypes); every symbol include/bgnn_vrtruth.h declares (native-resolution ground truth from a VR BAG pair)
 _VRTRUTH_SIGNATURES = {
@@ -369,8 +382,8 @@ class BgnnError(RuntimeError):
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
-    include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h and include/bgnn_vrtruth.h.  Needs no
-    GPU."""
+    include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h, include/bgnn_vrtruth.h and
+    include/bgnn_augment.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -385,7 +398,7 @@ def load_library(path: Optional[str] = None):
                 list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
                 list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
                 list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()) + \
-                list(_VRTRUTH_SIGNATURES.items()):
+                list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -9,8 +9,8 @@ from .losses import (BathymetricGNNLoss, ClassificationLoss, ConfidenceCalibrati
                      ShoalSafetyLoss, compute_class_weights, compute_correction_delta)
 from .evaluation import Evaluator, compute_metrics, metrics_from_block
 from .optim import FusedAdamW
-from .trainer import (EpochMetrics, StopRule, TileStore, Trainer, cut_tile_boxes, keep_ground_truth_boxes, plan_ground_truth_tiles,
-                      plan_tile_boxes, scan_tile_boxes, training_settings)
+from .trainer import (EpochMetrics, StopRule, TileStore, Trainer, cut_tile_boxes, dihedral_ops, keep_ground_truth_boxes,
+                      plan_ground_truth_tiles, plan_tile_boxes, scan_tile_boxes, training_settings, transformed_tile_table)
 
 # (the names the reference's ``training`` package exports on its loss side; ``FusedAdamW``, the trainer's classes and the evaluation are importable from here without being listed)
 __all__ = ["BathymetricGNNLoss", "ClassificationLoss", "CorrectionLoss", "ConfidenceCalibrationLoss", "FeaturePreservationLoss",

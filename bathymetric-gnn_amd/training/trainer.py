@@ -3,13 +3,19 @@ per-node targets gathered by one kernel (``bgnn_training_targets``), the step's 
 (``EpochMetrics`` over ``bgnn_epoch_accumulate``), and the reference's epoch loop with validation, scheduler, early stopping
 (``StopRule``) and checkpoints around the taped forward, ``BathymetricGNNLoss`` and ``FusedAdamW``.
 
-What stays out: GDAL / survey file reading, torch_geometric loaders (``num_workers``, ``pin_memory``), progress bars, the unused
-``augment_rotations`` / ``augment_flips`` flags, wandb, multi-GPU training, and the models the backward refuses (GCN, zero-padded
-shapes, layers wider than 256 columns: ``Trainer`` raises at construction).
+What stays out: GDAL / survey file reading, torch_geometric loaders (``num_workers``, ``pin_memory``), progress bars, wandb,
+multi-GPU training, and the models the backward refuses (GCN, zero-padded shapes, layers wider than 256 columns: ``Trainer``
+raises at construction).
 
-Determinism.  An epoch draws from two places only: ``Trainer.step_plan(epoch)`` (the shuffle and the dropout seed of every step)
-and the noise of a synthetic store, a function of ``(seed, epoch, tile)``.  Two runs with equal seeds give equal bits, whatever
-ran before, and a resumed run continues the run it was saved from bit for bit."""
+Geometric augmentation.  The reference's ``augment_rotations`` / ``augment_flips`` flags, which it never reads, are honoured by
+``Trainer(augment_geometry=True)``: every training tile is gathered from the store under one of the eight symmetries of the square
+(``dihedral_ops``, ``TileStore.gather`` over ``bgnn_tile_gather``, include/bgnn_augment.h) before its graph is built, all planes
+alike, so features and targets are those of the turned tile.  Off by default; validation and the training statistics never turn.
+
+Determinism.  An epoch draws from three places only: ``Trainer.step_plan(epoch)`` (the shuffle and the dropout seed of every
+step), ``Trainer.augment_plan(epoch)`` (the op of every tile, when ``augment_geometry`` is on) and the noise of a synthetic store,
+a function of ``(seed, epoch, tile)``.  Two runs with equal seeds give equal bits, whatever ran before, and a resumed run continues
+the run it was saved from bit for bit."""
 from __future__ import annotations
 
 import ctypes as C
@@ -225,6 +231,52 @@ def ragged_cell_index(offsets: np.ndarray, idx: np.ndarray) -> np.ndarray:
     first, cells = offsets[idx], offsets[idx + 1] - offsets[idx]
     run0 = np.cumsum(cells) - cells                      # where tile k's run starts in the index
     return np.repeat(first - run0, cells) + np.arange(int(cells.sum()), dtype=np.int64)
+
+
+def dihedral_ops(n: int, rotations: bool, flips: bool, rng: np.random.Generator) -> np.ndarray:
+    """``n`` ops of include/bgnn_augment.h (``op = k + 4 * f``: ``np.rot90(np.fliplr(t) if f else t, k)``) as int8, drawn from
+    ``rng`` as the two flags of the training settings ask:
+
+    both        ``k = rng.integers(0, 4, n)``, ``f = rng.integers(0, 2, n)``: uniform over the eight symmetries of the square
+    rotations   ``op = k``
+    flips       ``fh = rng.integers(0, 2, n)``, ``fv = rng.integers(0, 2, n)``, a horizontal and a vertical mirror drawn
+                independently: ``fh`` alone is op 4 (``fliplr``), ``fv`` alone op 6 (``flipud``), both op 2 (their product, the
+                turn by 180 degrees), neither op 0
+    neither     all zeros; nothing is drawn from ``rng``"""
+    n = int(n)
+    if rotations and flips:
+        k = rng.integers(0, 4, n)
+        f = rng.integers(0, 2, n)
+        return (k + 4 * f).astype(np.int8)
+    if rotations:
+        return rng.integers(0, 4, n).astype(np.int8)
+    if flips:
+        fh = rng.integers(0, 2, n)
+        fv = rng.integers(0, 2, n)
+        return np.array([0, 4, 6, 2], np.int8)[fh + 2 * fv]
+    return np.zeros(n, np.int8)
+
+
+def _ops_array(ops, n: int) -> np.ndarray:
+    ops = np.asarray(ops).reshape(-1)
+    if ops.size != n or (ops.size and not np.issubdtype(ops.dtype, np.integer)):
+        raise ValueError(f"ops must hold one integer op per tile ({n}), got {ops.size} of dtype {ops.dtype}")
+    ops = ops.astype(np.int32)
+    if ops.size and (ops.min() < 0 or ops.max() >= rt.AUG_OPS):
+        raise ValueError(f"ops {ops.tolist()} outside 0 .. {rt.AUG_OPS - 1}")
+    return ops
+
+
+def transformed_tile_table(hw, res, ops) -> Tuple[np.ndarray, np.ndarray]:
+    """``hw`` (int32 ``[n, 2]``) and ``res`` (float64 ``[n, 2]``) of a batch after ``ops``: an op with odd ``k`` (``op & 1``)
+    swaps the tile's extent and its resolution pair, every other op leaves both."""
+    hw = np.ascontiguousarray(hw, np.int32).reshape(-1, 2)
+    res = np.ascontiguousarray(res, np.float64).reshape(-1, 2)
+    if len(hw) != len(res):
+        raise ValueError("hw and res disagree on the number of tiles")
+    odd = (_ops_array(ops, len(hw)) & 1).astype(bool)
+    return (np.ascontiguousarray(np.where(odd[:, None], hw[:, ::-1], hw)),
+            np.ascontiguousarray(np.where(odd[:, None], res[:, ::-1], res)))
 
 
 def dropout_seed(seed: int, global_step: int) -> int:
@@ -553,17 +605,57 @@ class TileStore:
             out = {k: None if p is None else p.index_select(0, sel) for k, p in planes.items()}
         return np.ascontiguousarray(self.hw[idx]), np.ascontiguousarray(self.res[idx]), out
 
-    def batch(self, indices: Sequence[int], epoch: int = 0, noise=None):
+    def gather(self, indices: Sequence[int], ops):
+        """``(hw, res, planes)`` of the tiles ``indices``, tile ``k`` of them under ``ops[k]`` (``dihedral_ops``;
+        include/bgnn_augment.h): ``hw`` / ``res`` as ``transformed_tile_table`` gives them, ``planes`` the dict ``depth``,
+        ``mask``, ``unc``, ``labels``, ``difference`` (None where the store has none), every plane's tiles concatenated in the
+        order of ``indices``.  One ``bgnn_tile_gather`` launch for all planes, from a table of one entry per tile; a tile may be
+        named more than once.  Asynchronous on the context's stream, ordered against the caller's current stream."""
+        idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
+        if idx.size == 0 or idx.min() < 0 or idx.max() >= len(self):
+            raise IndexError(f"tile indices {idx.tolist()} outside a store of {len(self)} tiles")
+        ops = _ops_array(ops, idx.size)
+        words = {"depth": self.depth, "unc": self.unc, "labels": self.labels, "difference": self.difference}
+        for k, t in list(words.items()) + [("mask", self.mask)]:
+            if t is None:
+                continue
+            want = (torch.uint8, torch.bool) if k == "mask" else (torch.float32, torch.int32)
+            if t.dtype not in want or not t.is_contiguous() or t.device != self.device:
+                raise TypeError(f"the store's {k} plane must be a contiguous tensor of {' or '.join(str(w) for w in want)} on {self.device}")
+        table = np.zeros(idx.size, dtype=rt.TILE_ENTRY_DTYPE)
+        cells = self.offsets[idx + 1] - self.offsets[idx]
+        table["src"], table["dst"] = self.offsets[idx], np.cumsum(cells) - cells
+        table["h"], table["w"], table["op"] = self.hw[idx, 0], self.hw[idx, 1], ops
+        total, store_cells = int(cells.sum()), int(self.offsets[-1])
+        out = {k: None if t is None else torch.empty(total, dtype=t.dtype, device=self.device)
+               for k, t in list(words.items()) + [("mask", self.mask)]}
+        ctx = rt.get_context(self.device)
+        ws_bytes = int(ctx.lib.bgnn_tile_gather_workspace_bytes(idx.size))
+        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=self.device)
+        src = (C.c_void_p * len(words))(*[None if t is None else t.data_ptr() for t in words.values()])
+        dst = (C.c_void_p * len(words))(*[None if out[k] is None else out[k].data_ptr() for k in words])
+        ctx.begin()
+        rt.check(ctx.lib.bgnn_tile_gather(ctx.handle, src, dst, len(words), rt.ptr(self.mask), rt.ptr(out["mask"]), store_cells, total,
+                                          C.c_void_p(table.ctypes.data), idx.size, rt.ptr(ws), C.c_size_t(ws_bytes)))
+        ctx.end()
+        hw, res = transformed_tile_table(self.hw[idx], self.res[idx], ops)
+        return hw, res, out
+
+    def batch(self, indices: Sequence[int], epoch: int = 0, noise=None, ops=None):
         """``(graph, targets)`` of the tiles ``indices`` in epoch ``epoch``.  A synthetic store adds noise first
         (``NoiseAugmentor.augment_batch``, or ``generate_batch`` with ``augment=False``; ``noise``: another augmentor or
         generator for this call) with the sample index ``epoch * len(store) + i`` for tile ``i``, so the noise is a function of
         (seed, epoch, tile) alone; the graph is built from the noisy depth.  ``targets``: ``class_labels`` (int64),
-        ``correction_targets`` (float32), ``noise_mask`` (bool), one row per node."""
+        ``correction_targets`` (float32), ``noise_mask`` (bool), one row per node.
+
+        ``ops`` (None: the tiles as they are stored): one op of ``dihedral_ops`` per tile of ``indices``.  The planes then come
+        from ``gather``, turned; everything after is the same code, so the noise of a synthetic store is added AFTER the transform
+        (with the same sample indices), and gradients, slopes, ``local_std`` and the targets are those of the turned tile."""
         idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
         if idx.size == 0 or idx.min() < 0 or idx.max() >= len(self):
             raise IndexError(f"tile indices {idx.tolist()} outside a store of {len(self)} tiles")
         ctx = rt.get_context(self.device)
-        hw, res, p = self._gather(idx)
+        hw, res, p = self._gather(idx) if ops is None else self.gather(idx, ops)
         if self.kind == "synthetic":
             source = noise if noise is not None else (self.noise_augmentor if self.noise_augmentor is not None else self.noise_generator)
             samples = [int(epoch) * len(self) + int(i) for i in idx]
@@ -721,10 +813,14 @@ class Trainer:
     whose tiles differ widely in size (``TileStore.from_refinement_pairs``: refinement grids of 9 to 2500 cells); see
     ``step_plan``.  Under either rule a step whose tiles would hold fewer than two nodes is joined to a neighbouring step, which
     may then pass ``batch_nodes`` by that tile's cells; a training store whose tiles hold fewer than two nodes altogether raises
-    ``ValueError`` here."""
+    ``ValueError`` here.
+
+    ``augment_geometry`` (None or False: off, the tiles train as they are stored): True turns every training tile by one of the
+    eight symmetries of the square per epoch, as the settings' ``augment_rotations`` / ``augment_flips`` allow (``augment_plan``;
+    both flags False: every op is the identity, through the same path)."""
 
     def __init__(self, config, model, train_store: TileStore, val_store: Optional[TileStore] = None, output_dir=None,
-                 seed: int = 0, batch_nodes: Optional[int] = None):
+                 seed: int = 0, batch_nodes: Optional[int] = None, augment_geometry: Optional[bool] = None):
         if batch_nodes is not None and int(batch_nodes) < 1:
             raise ValueError(f"batch_nodes {batch_nodes}: a positive number of cells, or None")
         nodes = getattr(train_store, "node_counts", None)
@@ -732,6 +828,7 @@ class Trainer:
             raise ValueError(f"the training store's {len(train_store)} tiles hold {int(np.sum(nodes))} node(s) altogether: a training "
                              "step needs at least 2 (BatchNorm's batch statistics)")
         self.batch_nodes = None if batch_nodes is None else int(batch_nodes)
+        self.augment_geometry = bool(augment_geometry)
         self.config = config
         self.model = model
         self.train_dataset = self.train_store = train_store
@@ -903,14 +1000,25 @@ class Trainer:
             return [(p, None) for p in pieces]
         return [(p, dropout_seed(self.seed, int(epoch) * len(pieces) + k)) for k, p in enumerate(pieces)]
 
+    def augment_plan(self, epoch: int) -> np.ndarray:
+        """The geometric op (``dihedral_ops``, int8) of every tile of the training store in epoch ``epoch``, as the settings'
+        ``augment_rotations`` / ``augment_flips`` ask, drawn from ``np.random.default_rng([seed, epoch, 0xA6])``.  With
+        ``augment_geometry`` on, the training step over the tiles ``indices`` passes ``ops[indices]`` to ``TileStore.batch``: the op
+        of a tile is a function of (seed, epoch, tile) and does not depend on how the epoch is cut into steps.  Validation, the
+        training statistics and the construction-time probe never turn a tile."""
+        s = self.settings
+        return dihedral_ops(len(self.train_store), bool(s.augment_rotations), bool(s.augment_flips),
+                            np.random.default_rng([self.seed, int(epoch), 0xA6]))
+
     # ---- epochs ------------------------------------------------------------------------------------------------------------
     def _train_epoch(self) -> Dict[str, float]:
         """Run one training epoch."""
         self.model.train()
         metrics = self.train_metrics
         metrics.reset()
+        ops = self.augment_plan(self.current_epoch) if getattr(self, "augment_geometry", False) else None
         for indices, drop_seed in self.step_plan(self.current_epoch):
-            graph, targets = self.train_store.batch(indices, self.current_epoch)
+            graph, targets = self.train_store.batch(indices, self.current_epoch, ops=None if ops is None else ops[indices])
             self.model.dropout_seed = drop_seed
             self.optimizer.zero_grad()
             outputs = self.model(graph)
