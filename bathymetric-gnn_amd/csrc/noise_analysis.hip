@@ -17,24 +17,17 @@
 // and uint32 counts (cells are below 2^31).  This file keeps the streaming loops, the rule that sets each selection's ranks from the
 // first level's totals, and what is written to the block after the last level.
 //
-// Connected components (4-connectivity, scipy.ndimage.label's default structure): label equivalence by union-find over int32
-// cell indices, parent[i] = -1 off the noise mask.
-//   ccl_local    a 16 x 64 tile in LDS: every noise cell unites with its left and upper neighbour inside the tile; then the cell's
-//                parent becomes the global index of its tile-local root, and that root's size counter gets the cells of the
-//                component inside the tile.  Also the per-column noise / valid counts of the tile (64 x 2 global integer adds)
-//   ccl_merge    every noise cell in the first row / column of a tile unites with its neighbour across the border (global atomics)
-//   ccl_flatten  every tile-local root that is not a global root finds its root, points at it, and adds its counter to the root's
-//                (integer atomicAdd: order-independent).  Roots are stable here: the merges ended with the previous kernel
+// Connected components of the noise mask (4-connectivity, scipy.ndimage.label's default structure): component_label.h, with its
+// invariant parent[i] <= i and the termination argument; no thread waits for another.
+//   ccl_local    a 16 x 64 tile in LDS: the tile-local labelling of the noise cells.  Also the per-column noise / valid counts of
+//                the tile (64 x 2 global integer adds)
+//   label_merge, label_flatten<SizeOnly>   the unions across the tile borders; the sizes summed at the roots
 //   ccl_stats    over the global roots (parent[i] == i): count, size sum, maximum, size bins, the top size bits
-//
-// load_parent / find_root / unite, the invariant parent[i] <= i and the termination argument: union_find.h (shared with
-// review_regions.hip).  No thread waits for another: there is no spin-wait on a flag or a workgroup, no grid-wide barrier and no
-// persistent kernel; a workgroup's progress never depends on another workgroup being scheduled.
 //
 // Compiled with -ffp-contract=off: the float32 rank arithmetic of numpy's percentile and the float64 squares round as written.
 #include "bgnn_internal.h"
+#include "component_label.h"
 #include "radix_select.h"
-#include "union_find.h"
 #include "../../include/bgnn_analysis.h"
 
 namespace bgnn {
@@ -43,9 +36,7 @@ namespace {
 constexpr int NA_THREADS = BLOCK_THREADS;
 constexpr int NA_ITEMS = 4;                           // cells per thread and step of a streaming pass (each load coalesced)
 constexpr int NA_CHUNK = NA_THREADS * NA_ITEMS;
-constexpr int NA_MAX_GRID = 2048;                     // 256 CUs x 8 workgroups
 constexpr int NA_RANKS = 6;
-constexpr int TILE_R = 16, TILE_C = 64;               // tile of ccl_local / na_rough: 1024 cells
 constexpr int HALO_R = TILE_R + 4, HALO_C = TILE_C + 4;
 constexpr int ROW_WORDS = 40;                         // a partial row: 8-byte words
 
@@ -74,7 +65,7 @@ constexpr size_t WS_SEL_WORDS = (size_t)NA_LEVELS * WS_LEVEL_WORDS;
 constexpr size_t WS_STATE = (size_t)SEL_COUNT * WS_SEL_WORDS * 4;
 constexpr size_t WS_CLEAR_BYTES = WS_STATE + (size_t)SEL_COUNT * 256;
 constexpr size_t WS_ROWS = WS_CLEAR_BYTES;
-constexpr size_t WS_PLANES = WS_ROWS + (size_t)NA_MAX_GRID * ROW_WORDS * 8;
+constexpr size_t WS_PLANES = WS_ROWS + (size_t)PLANE_MAX_GRID * ROW_WORDS * 8;
 static_assert(WS_PLANES % 256 == 0, "planes are 256-byte aligned");
 
 __device__ __forceinline__ int64_t block_sum_i(uint32_t v, void *s) { return block_reduce((int64_t)v, s, SumOp()); }
@@ -283,10 +274,6 @@ __global__ __launch_bounds__(NA_THREADS) void na_select(const uint32_t *__restri
 }
 
 // ---- 5. roughness ------------------------------------------------------------------------------------------------------------
-struct TileGrid {
-  int32_t rows, cols, tiles_r, tiles_c;
-};
-
 // partial row: int64 noise cells, seafloor cells with a roughness; float64 their sums
 __global__ __launch_bounds__(NA_THREADS) void na_rough(const float *__restrict__ clean, const int32_t *__restrict__ labels, TileGrid tg,
                                                        uint64_t *__restrict__ plane, uint32_t *__restrict__ hist,
@@ -300,7 +287,7 @@ __global__ __launch_bounds__(NA_THREADS) void na_rough(const float *__restrict__
   const uint64_t nan64 = 0x7FF8000000000000ull;
   uint32_t cnt[2] = {0, 0};
   double sum[2] = {0.0, 0.0};
-  const int64_t tiles = (int64_t)tg.tiles_r * tg.tiles_c;
+  const int64_t tiles = tg.tiles();
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int r0 = (int)(tile / tg.tiles_c) * TILE_R, c0 = (int)(tile % tg.tiles_c) * TILE_C;
     __syncthreads();                                            // (the previous tile's readers of halo[] are done; lds[] is cleared)
@@ -356,90 +343,34 @@ __global__ __launch_bounds__(NA_THREADS) void na_rough(const float *__restrict__
 }
 
 // ---- 3. clusters -------------------------------------------------------------------------------------------------------------
-// load_parent<GLOBAL> / find_root<GLOBAL> / unite<GLOBAL>: union_find.h (GLOBAL: the parent array in global memory; else LDS)
 __global__ __launch_bounds__(NA_THREADS) void ccl_local(const int32_t *__restrict__ labels, TileGrid tg, int32_t *__restrict__ parent,
                                                         int32_t *__restrict__ size, int32_t *__restrict__ col_noise,
                                                         int32_t *__restrict__ col_valid) {
-  constexpr int CELLS = TILE_R * TILE_C, PER = CELLS / NA_THREADS;
-  __shared__ int32_t lp[CELLS], lsize[CELLS], cn[TILE_C], cv[TILE_C];
+  __shared__ int32_t lp[TILE_CELLS], lsize[TILE_CELLS], cn[TILE_C], cv[TILE_C];
   const int t = threadIdx.x;
-  const int64_t tiles = (int64_t)tg.tiles_r * tg.tiles_c;
+  const int64_t tiles = tg.tiles();
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int r0 = (int)(tile / tg.tiles_c) * TILE_R, c0 = (int)(tile % tg.tiles_c) * TILE_C;
     __syncthreads();                                            // (the previous tile is written out)
     if (t < TILE_C) { cn[t] = 0; cv[t] = 0; }
     __syncthreads();
-    bool noise[PER];
+    bool noise[TILE_PER];
 #pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      const int l = k * NA_THREADS + t, gr = r0 + l / TILE_C, gc = c0 + l % TILE_C;
+    for (int k = 0; k < TILE_PER; ++k) {
+      const int l = tile_cell(k), gr = r0 + l / TILE_C, gc = c0 + l % TILE_C;
       const bool in = gr < tg.rows && gc < tg.cols;
       const int32_t lab = in ? labels[(int64_t)gr * tg.cols + gc] : -1;
       noise[k] = lab == 2;
-      lp[l] = noise[k] ? l : -1;
-      lsize[l] = 0;
       if (lab >= 0) atomicAdd(&cv[l % TILE_C], 1);
       if (noise[k]) atomicAdd(&cn[l % TILE_C], 1);
     }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      const int l = k * NA_THREADS + t;
-      if (!noise[k]) continue;
-      if (l % TILE_C > 0 && load_parent<false>(lp, l - 1) >= 0) unite<false>(lp, l, l - 1);
-      if (l >= TILE_C && load_parent<false>(lp, l - TILE_C) >= 0) unite<false>(lp, l, l - TILE_C);
-    }
-    __syncthreads();
-    int32_t root[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      root[k] = noise[k] ? find_root<false>(lp, k * NA_THREADS + t) : -1;
-      if (noise[k]) atomicAdd(&lsize[root[k]], 1);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      const int l = k * NA_THREADS + t, gr = r0 + l / TILE_C, gc = c0 + l % TILE_C;
-      if (gr >= tg.rows || gc >= tg.cols) continue;
-      const int64_t i = (int64_t)gr * tg.cols + gc;
-      const int rl = root[k];
-      parent[i] = noise[k] ? (int32_t)((int64_t)(r0 + rl / TILE_C) * tg.cols + c0 + rl % TILE_C) : -1;
-      size[i] = (noise[k] && rl == l) ? lsize[l] : 0;
-    }
+    int32_t root[TILE_PER];
+    tile_label(noise, lp, lsize, root);
+    tile_write(tg, r0, c0, noise, root, lsize, parent, size);
     if (t < TILE_C && c0 + t < tg.cols) {
       if (cn[t] != 0) atomicAdd(col_noise + c0 + t, cn[t]);
       if (cv[t] != 0) atomicAdd(col_valid + c0 + t, cv[t]);
     }
-  }
-}
-
-// The cells that have a neighbour across a tile border: (tiles_r - 1) * cols in the first rows of the lower tiles (upper
-// neighbour), then (tiles_c - 1) * rows in the first columns of the right-hand tiles (left neighbour).
-__global__ __launch_bounds__(NA_THREADS) void ccl_merge(TileGrid tg, int32_t *parent) {
-  const int64_t nh = (int64_t)(tg.tiles_r - 1) * tg.cols, total = nh + (int64_t)(tg.tiles_c - 1) * tg.rows;
-  for (int64_t j = (int64_t)blockIdx.x * NA_THREADS + threadIdx.x; j < total; j += (int64_t)gridDim.x * NA_THREADS) {
-    int64_t i, other;
-    if (j < nh) {
-      const int64_t r = (j / tg.cols + 1) * TILE_R, c = j % tg.cols;
-      i = r * tg.cols + c;
-      other = i - tg.cols;
-    } else {
-      const int64_t k = j - nh, c = (k / tg.rows + 1) * TILE_C, r = k % tg.rows;
-      i = r * tg.cols + c;
-      other = i - 1;
-    }
-    if (load_parent<true>(parent, (int32_t)i) >= 0 && load_parent<true>(parent, (int32_t)other) >= 0) unite<true>(parent, (int32_t)i, (int32_t)other);
-  }
-}
-
-__global__ __launch_bounds__(NA_THREADS) void ccl_flatten(int64_t cells, int32_t *parent, int32_t *size) {
-  for (int64_t i = (int64_t)blockIdx.x * NA_THREADS + threadIdx.x; i < cells; i += (int64_t)gridDim.x * NA_THREADS) {
-    const int32_t s = size[i];                                  // (> 0: a tile-local root; only global roots' counters change here)
-    if (s <= 0) continue;
-    const int32_t root = find_root<true>(parent, (int32_t)i);
-    if (root == (int32_t)i) continue;
-    __hip_atomic_store(parent + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    atomicAdd(size + root, s);
   }
 }
 
@@ -543,14 +474,8 @@ extern "C" int bgnn_noise_analysis(bgnn_ctx *ctx, const int32_t *labels, const f
   int32_t *parent = reinterpret_cast<int32_t *>(w + WS_PLANES);
   int32_t *size = reinterpret_cast<int32_t *>(w + WS_PLANES + align256((size_t)cells * 4));
   uint64_t *rough = reinterpret_cast<uint64_t *>(w + WS_PLANES + 2 * align256((size_t)cells * 4));
-  TileGrid tg;
-  tg.rows = (int32_t)rows; tg.cols = (int32_t)cols;
-  tg.tiles_r = (int32_t)((rows + TILE_R - 1) / TILE_R); tg.tiles_c = (int32_t)((cols + TILE_C - 1) / TILE_C);
-  const int64_t tiles = (int64_t)tg.tiles_r * tg.tiles_c;
-  const int64_t borders = (int64_t)(tg.tiles_r - 1) * cols + (int64_t)(tg.tiles_c - 1) * rows;
-  const auto grid_of = [](int64_t work_items) { return capped_grid(work_items, NA_MAX_GRID); };
-  const int g_stream = grid_of((cells + NA_CHUNK - 1) / NA_CHUNK), g_tiles = grid_of(tiles);
-  const int g_cells = grid_of((cells + NA_THREADS - 1) / NA_THREADS), g_borders = grid_of((borders + NA_THREADS - 1) / NA_THREADS);
+  const TileGrid tg(rows, cols);
+  const int g_stream = capped_grid((cells + NA_CHUNK - 1) / NA_CHUNK, PLANE_MAX_GRID), g_tiles = tg.local_grid();
   const dim3 b(NA_THREADS), one(1), fin(64);
   hipStream_t s = ctx->stream;
   const SelLaunch sel{s, g_stream, Source{labels, difference, parent, size, rough}, cells, w, blk, part};
@@ -588,8 +513,7 @@ extern "C" int bgnn_noise_analysis(bgnn_ctx *ctx, const int32_t *labels, const f
 
   // 3, 4: clusters, the per-column counts, the median cluster size
   hipLaunchKernelGGL(ccl_local, dim3(g_tiles), b, 0, s, labels, tg, parent, size, col_noise, col_valid);
-  hipLaunchKernelGGL(ccl_merge, dim3(g_borders), b, 0, s, tg, parent);
-  hipLaunchKernelGGL(ccl_flatten, dim3(g_cells), b, 0, s, cells, parent, size);
+  launch_merge_flatten(s, tg, parent, SizeOnly{size});
   hipLaunchKernelGGL(ccl_stats, dim3(g_stream), b, 0, s, cells, parent, size, top_hist(SEL_SIZE), part);
   {
     FinishMap m{};

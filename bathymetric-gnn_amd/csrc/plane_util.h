@@ -8,6 +8,7 @@
 namespace bgnn {
 
 constexpr int BLOCK_THREADS = 256;                    // the workgroup of block_reduce and of radix_select.h
+constexpr int PLANE_MAX_GRID = 2048;                  // 256 CUs x 8 workgroups: the grid cap of the plane kernels that stride
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 

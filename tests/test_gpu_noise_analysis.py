@@ -13,6 +13,7 @@ from scipy import ndimage
 from _analysis_cpu import (ANALYSIS_CASES, MAGNITUDE_KEY_CASES, ROUGH_RTOL, STRICT_CASES, check_analysis, load_analysis_case,
                            magnitude_key_case, numpy_analysis, numpy_analysis_block, ulps_apart)
 from _eval_checks import grids_of, load_case, sum_tolerance
+from test_gpu_review import FLATTEN_MASKS, flatten_chunks
 
 pytestmark = pytest.mark.gpu
 INTEGER_FIELDS = ("valid", "noise", "seafloor", "positive", "negative", "nonfinite", "bin_noise", "bin_valid", "mag_rank", "mag_value",
@@ -87,6 +88,27 @@ def test_random_mask_past_the_fixtures(density, gpu_device):
     assert int((first != last).sum()) > 100
     want = analysis_from_block(want_block, want_cn, want_cv, (h, w), "random.tif")
     check_analysis(analysis_from_block(block, cn, cv, (h, w), "random.tif"), want, planes, strict=True, fixture=False)
+
+
+@pytest.mark.parametrize("name", sorted(FLATTEN_MASKS))
+def test_flatten_wave_groups(name, gpu_device):
+    """The two masks test_gpu_review.py builds for the wave-grouped flatten, as the noise cells of a ground truth: every integer of
+    the block and the per-column counts against the numpy / scipy restatement."""
+    from bathymetric_gnn_amd.data.noise_analysis import noise_analysis_build, split_result
+    mask, components, chunks = FLATTEN_MASKS[name]
+    h, w = mask.shape
+    rng = np.random.default_rng(20240819)
+    labels = np.where(mask, 2, 0).astype(np.int32)
+    assert flatten_chunks(labels == 2) == (components, chunks)
+    clean = (-40 + 0.1 * rng.standard_normal((h, w))).astype(np.float32)
+    difference = np.where(mask, (0.2 + rng.exponential(0.3, (h, w))) * rng.choice([-1.0, 1.0], (h, w)), 0.05 * rng.standard_normal((h, w))).astype(np.float32)
+    planes = (labels, difference, (clean + difference).astype(np.float32), clean)
+    want_block, want_cn, want_cv = numpy_analysis_block(*planes)
+    block, cn, cv = split_result(noise_analysis_build(*(torch.from_numpy(p).to(gpu_device) for p in planes)).cpu().numpy(), w)
+    assert np.array_equal(cn, want_cn) and np.array_equal(cv, want_cv)
+    for k in INTEGER_FIELDS + ("rough_count",):
+        assert np.array_equal(block[k], want_block[k]), (k, block[k], want_block[k])
+    assert (int(block["num_clusters"]), int(block["cluster_cells"]), int(block["max_cluster"])) == (components, components * w, w)
 
 
 @pytest.mark.parametrize("shape,with_roughness", [((2, 131073), True), ((1030, 2049), False)], ids=["2049_tiles", "2062_chunks_2145_tiles"])

@@ -6,6 +6,7 @@ sit on it, one past it, and far from any multiple of it; the chains run through 
 import numpy as np
 import pytest
 import torch
+from scipy import ndimage
 
 from _review_cpu import MEAN_ATOL, check_device_result, fast_regions, float32_mean_bound, load_fixture, same_regions
 
@@ -74,6 +75,53 @@ def spiral(h, w):
             dr, dc = dc, -dr
         else:
             return m
+
+
+def rows_on(h, w, rows):
+    m = np.zeros((h, w), bool)
+    m[list(rows), :] = True
+    return m
+
+
+def flatten_chunks(mask):
+    """What the flatten kernel meets on ``mask``: the number of components, and per 4096 consecutive cells that hold a tile-local
+    root (the first cell of a component of a 16 x 64 tile) ``(tile-local roots, those that are not their component's first cell,
+    distinct components among those)``."""
+    h, w = mask.shape
+    labeled, n = ndimage.label(mask)
+    flat = np.arange(h * w).reshape(h, w)
+    first = ndimage.minimum(flat, labeled, np.arange(1, n + 1)).astype(np.int64)
+    chunks = {}
+    for r0 in range(0, h, 16):
+        for c0 in range(0, w, 64):
+            tile, k = ndimage.label(mask[r0:r0 + 16, c0:c0 + 64])
+            for i in ndimage.minimum(flat[r0:r0 + 16, c0:c0 + 64], tile, np.arange(1, k + 1)).astype(np.int64):
+                chunk = chunks.setdefault(int(i) // 4096, [0, 0, set()])
+                component = int(labeled.flat[i])
+                chunk[0] += 1
+                if first[component - 1] != i:
+                    chunk[1] += 1
+                    chunk[2].add(component)
+    return n, [(c[0], c[1], len(c[2])) for _, c in sorted(chunks.items())]
+
+
+# Two masks for the wave-grouped flatten (csrc/component_label.h), with what ``flatten_chunks`` has to say of them:
+#   one line   3 x 4481, row 0: one component in 71 tiles.  The first 4096 cells hold 64 tile-local roots, 63 of them under the one
+#              root (a full wave behind a single leader); the other 7 fall into a second chunk
+#   six lines  11 x 321, every second row: six components in six tiles each.  All 36 tile-local roots in one chunk and one wave, 30
+#              of them under six roots: four go through the shuffle tree, the lanes of the last two add their own
+FLATTEN_MASKS = {"one_line": (rows_on(3, 4481, [0]), 1, [(64, 63, 1), (7, 7, 1)]),
+                 "six_lines": (rows_on(11, 321, range(0, 11, 2)), 6, [(36, 30, 6)])}
+
+
+@pytest.mark.parametrize("name", sorted(FLATTEN_MASKS))
+def test_flatten_wave_groups(name, gpu_device):
+    mask, components, chunks = FLATTEN_MASKS[name]
+    assert flatten_chunks(mask) == (components, chunks)
+    result, (_, _, counts) = run(field_from_mask(mask, np.random.default_rng(20240917)), 0.4, 0.7, 1, gpu_device)
+    assert counts["regions"] == components and [r["size"] for r in result.regions] == [mask.shape[1]] * components
+    assert [r["bounds"] for r in result.regions] == [{"min_row": r, "max_row": r, "min_col": 0, "max_col": mask.shape[1] - 1}
+                                                     for r in range(0, mask.shape[0], 2)][:components]
 
 
 @pytest.mark.parametrize("shape", [(1, 1), (1, 200), (200, 1), (16, 64), (17, 65), (37, 150)], ids=lambda s: f"{s[0]}x{s[1]}")

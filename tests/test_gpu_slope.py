@@ -15,7 +15,7 @@ from scipy import ndimage
 import _slope_cpu as cpu
 from bathymetric_gnn_amd.data import add_feature_labels, create_feature_mask_from_slope, slope_cut
 from bathymetric_gnn_amd.data.slope_features import slope_features_build, slope_stats
-from test_gpu_review import comb, serpentine, spiral
+from test_gpu_review import FLATTEN_MASKS, comb, flatten_chunks, serpentine, spiral
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -145,6 +145,34 @@ def test_long_union_chains(name, pattern, gpu_device):
     assert len(tiles) == -(-132 // TILE_R) * -(-400 // TILE_C), "one component runs through every tile"
     _, mask, stats = run(d, 15.0, int(sizes.max()), gpu_device)
     assert np.array_equal(mask, big) and stats["kept_clusters"] == 1 and stats["kept_cells"] == int(sizes.max()) > 5000
+
+
+def lines_relief(name):
+    """A depth plane whose steep cells at 15 degrees are FLATTEN_MASKS[name]: the rows are constant, so gx = 0.  One line: row 0
+    stands 0.375 above the rest (the one-sided difference 0.375 is steep, the central one of row 1, 0.1875, is not).  Six lines: the
+    even rows at one depth (no central difference across an odd row), the odd rows 0.75 apart (0.375 across every even row), and
+    1.5 from the first and the last odd row to the plane's border rows."""
+    h, w = FLATTEN_MASKS[name][0].shape
+    d = np.full((h, w), 21.0, F32)
+    if name == "one_line":
+        d[0] += F32(0.375)
+    else:
+        d[0::2] = F32(22.5)
+        d[1::2] = (F32(21.0) + F32(0.75) * np.arange(h // 2, dtype=F32))[:, None]
+    return d
+
+
+@pytest.mark.parametrize("name", sorted(FLATTEN_MASKS))
+def test_flatten_wave_groups(name, gpu_device):
+    """The two masks test_gpu_review.py builds for the wave-grouped flatten, as the steep cells of a depth plane."""
+    mask, components, chunks = FLATTEN_MASKS[name]
+    d = lines_relief(name)
+    steep = cpu.steep_mask(d, 15.0)
+    assert np.array_equal(steep, mask) and flatten_chunks(steep) == (components, chunks)
+    _, kept, stats = run(d, 15.0, mask.shape[1], gpu_device)
+    assert np.array_equal(kept, mask) and (stats["clusters"], stats["kept_clusters"], stats["kept_cells"]) == (components, components, mask.sum())
+    _, kept, stats = run(d, 15.0, mask.shape[1] + 1, gpu_device)
+    assert not kept.any() and stats["clusters"] == components
 
 
 def test_clusters_of_99_and_100_cells_across_a_tile_corner(gpu_device):
