@@ -2,15 +2,16 @@
 tensors, the same formulas as torch operations elsewhere), the two helpers that derive its class weights and Huber delta from the
 training data, the last two lines of a step -- ``clip_grad_norm_`` and ``optimizer.step()`` -- as ``FusedAdamW`` (HIP kernels over the
 flat weight blob, the packed model refreshed in place), and the reference's ``Trainer`` over device-resident ``TileStore`` s
-(``trainer.py``: per-node targets and per-step bookkeeping as kernels of ``include/bgnn_trainer.h``), and the metrics of
+(``tile_store.py``, ``trainer.py``: per-node targets and per-step bookkeeping as kernels of ``include/bgnn_trainer.h``), and the metrics of
 ``scripts/evaluate_model.py`` counted on the device (``evaluation.py``: ``Evaluator``, ``compute_metrics``).  The reference's dataset
 classes themselves (torch_geometric loaders, GDAL, tqdm) stay outside the path."""
 from .losses import (BathymetricGNNLoss, ClassificationLoss, ConfidenceCalibrationLoss, CorrectionLoss, FeaturePreservationLoss,
                      ShoalSafetyLoss, compute_class_weights, compute_correction_delta)
 from .evaluation import Evaluator, compute_metrics, metrics_from_block
 from .optim import FusedAdamW
-from .trainer import (EpochMetrics, StopRule, TileStore, Trainer, cut_tile_boxes, dihedral_ops, keep_ground_truth_boxes,
-                      plan_ground_truth_tiles, plan_tile_boxes, scan_tile_boxes, training_settings, transformed_tile_table)
+from .tile_store import (TileStore, cut_tile_boxes, dihedral_ops, keep_ground_truth_boxes, plan_ground_truth_tiles, plan_tile_boxes,
+                         scan_tile_boxes, transformed_tile_table)
+from .trainer import EpochMetrics, StopRule, Trainer, training_settings
 
 # (the names the reference's ``training`` package exports on its loss side; ``FusedAdamW``, the trainer's classes and the evaluation are importable from here without being listed)
 __all__ = ["BathymetricGNNLoss", "ClassificationLoss", "CorrectionLoss", "ConfidenceCalibrationLoss", "FeaturePreservationLoss",

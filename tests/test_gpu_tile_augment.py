@@ -307,6 +307,55 @@ def test_batch_with_ops_equals_a_store_turned_beforehand(kind, epoch, gpu_device
         A.batch([0], epoch, ops=[8])
 
 
+IDENTITY_CASES = {"ragged": ([(65, 63), (9, 40), (40, 40), (40, 40), (2, 2)], [[4, 0, 2, 1, 3], [1, 1], [3]]),
+                  "uniform": ([(40, 40)] * 3, [[2, 0]])}
+
+
+@pytest.mark.parametrize("with_unc", [True, False], ids=["unc", "no_unc"])
+@pytest.mark.parametrize("case", list(IDENTITY_CASES))
+def test_gather_without_ops_is_the_stored_cells_in_order(case, with_unc, gpu_device):
+    """``gather(idx, None)`` -- the path of every ``batch`` without ops -- against slices of a host copy of the store's planes, not
+    against the library: tile ``i`` of a batch is the cells ``offsets[i] .. offsets[i + 1] - 1`` of every plane, in the order of
+    ``idx``, bit for bit.  The float planes hold NaNs of distinct payloads and both infinities in invalid cells: the words are
+    moved, not interpreted.  The shapes reach every branch of the 64 x 64-block kernel (a tile wider and one narrower than a block,
+    partial blocks, a tile smaller than a wave) and both kinds of store (ragged, uniform)."""
+    from bathymetric_gnn_amd.training import TileStore
+    shapes, batches = IDENTITY_CASES[case]
+    tiles = [_planes(s, k + 1) for k, s in enumerate(shapes)]
+    for t in tiles:                                       # invalid where the depth is NaN or infinite; NaNs in the other planes too
+        flat = {k: v.reshape(-1) for k, v in t.items()}
+        bad = np.arange(0, flat["mask"].size, 7)
+        flat["mask"][bad], flat["mask"][[1, 3]] = 0, 0
+        flat["unc"].view(np.uint32)[bad] = 0xFFC00000 + bad
+        flat["difference"].view(np.uint32)[bad[::2]] = 0x7F800001 + bad[::2]
+        flat["difference"].view(np.uint32)[[1, 3]] = 0xFF800000, 0x7F800000
+    built = {k: np.concatenate([t[k].ravel() for t in tiles]) for k in WORDS + ("mask",) if with_unc or k != "unc"}
+    dev = {k: torch.from_numpy(v).cuda() for k, v in built.items()}
+    word = lambda k, dt: None if k not in dev else dev[k].view(dt)
+    store = TileStore("ground_truth", np.array(shapes, np.int32), np.ones((len(shapes), 2)), word("depth", torch.float32), dev["mask"],
+                      word("unc", torch.float32), labels=dev["labels"], difference=word("difference", torch.float32))
+    assert store.uniform == (case == "uniform") and (store.unc is None) == (not with_unc)
+    host = {k: None if getattr(store, k) is None else _bits(getattr(store, k)).cpu().numpy() for k in WORDS + ("mask",)}
+    off = store.offsets
+    assert off.tolist() == np.concatenate([[0], np.cumsum([h * w for h, w in shapes])]).tolist()
+    for k, v in built.items():
+        assert np.array_equal(host[k], v), k
+    depth, invalid = host["depth"].view(np.float32), host["mask"] == 0
+    assert np.isnan(depth[invalid]).sum() > 2 and np.isposinf(depth[invalid]).any() and np.isneginf(depth[invalid]).any()
+    assert len(np.unique(host["depth"][invalid])) > invalid.sum() // 2          # (the payloads differ)
+    for idx in batches:
+        hw, res, planes = store.gather(idx, None)
+        assert hw.tolist() == [list(shapes[i]) for i in idx] and res.tolist() == [[1.0, 1.0]] * len(idx)
+        assert sorted(planes) == sorted(WORDS + ("mask",))
+        for k in planes:
+            if host[k] is None:
+                assert planes[k] is None and k == "unc" and not with_unc
+                continue
+            want = np.concatenate([host[k][off[i]:off[i + 1]] for i in idx])
+            got = _bits(planes[k]).cpu().numpy()
+            assert got.dtype == want.dtype and np.array_equal(got, want), (k, idx)
+
+
 # ---- 6. the Trainer --------------------------------------------------------------------------------------------------------------
 def _run(tmp, name, epochs=2, seed=4, **kw):
     from bathymetric_gnn_amd.training import Trainer

@@ -84,6 +84,38 @@ def test_keep_rule_at_the_line():
     assert keep_ground_truth_boxes(boxes, counts, 0.1) == (boxes[:3], {0: 128, 1: 127, 2: 103})
 
 
+# ---- 3. assembling a store from several sources -------------------------------------------------------------------------------
+def test_cut_store_tables_and_running_offsets(monkeypatch):
+    """``_cut_store`` with ``cut_tile_boxes`` replaced by a recorder (host tensors, nothing launched): three sources of 2, 0 and 3
+    boxes of unequal extents.  One allocation per plane for all of them, one call per source that has boxes, at its running offset."""
+    import torch
+    from bathymetric_gnn_amd.training import tile_store
+    calls = []
+    monkeypatch.setattr(tile_store, "cut_tile_boxes", lambda planes, stores, boxes, offsets, **kw: calls.append(
+        (planes, stores, [tuple(int(v) for v in b) for b in boxes], np.asarray(offsets).tolist(), kw)))
+    shapes = [(20, 30), (8, 8), (50, 41)]
+    sources = [[torch.zeros(s, dtype=torch.int32), torch.zeros(s), None, torch.zeros(s)] for s in shapes]
+    boxes = [[(0, 0, 5, 7), (3, 2, 20, 30)], [], [(0, 0, 1, 41), (10, 1, 50, 2), (7, 7, 16, 16)]]
+    hw, stores, mask = tile_store._cut_store(list(zip(sources, boxes)), mask_plane=1, nodata=-5.0, ctx="the context")
+    want_hw = [[5, 7], [17, 28], [1, 41], [40, 1], [9, 9]]
+    cells = [35, 476, 41, 40, 81]
+    offsets = [0, 35, 511, 552, 592, 673]
+    assert hw.dtype == np.int32 and hw.tolist() == want_hw and offsets == np.concatenate([[0], np.cumsum(cells)]).tolist()
+    assert tile_store._tile_offsets(hw).dtype == np.int64 and tile_store._tile_offsets(hw).tolist() == offsets
+    assert [None if s is None else (s.dtype, tuple(s.shape)) for s in stores] == \
+        [(torch.int32, (673,)), (torch.float32, (673,)), None, (torch.float32, (673,))]
+    assert mask.dtype == torch.uint8 and tuple(mask.shape) == (673,)
+    assert len(calls) == 2                                                # the source without boxes: no call
+    for call, k, first in zip(calls, (0, 2), (0, 2)):
+        planes, dst, b, at, kw = call
+        assert planes is sources[k] and all(d is s for d, s in zip(dst, stores)) and b == boxes[k]
+        assert at == offsets[first:first + len(boxes[k])]
+        assert kw["mask"] is mask and kw["mask_plane"] == 1 and kw["nodata"] == -5.0 and kw["ctx"] == "the context"
+    # a tile table past 2^31 cells keeps its 64-bit offsets
+    big = np.array([[46341, 46341], [3, 5]], np.int32)
+    assert tile_store._tile_offsets(big).tolist() == [0, 46341 * 46341, 46341 * 46341 + 15] and 46341 * 46341 > 2 ** 31
+
+
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------
 def _declared(name):
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)

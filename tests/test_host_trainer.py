@@ -133,7 +133,7 @@ def test_ground_truth_scan():
     """A 70 x 90 label band at tile 32 / overlap 8 (stride 24): 2 x 3 full tiles on the stride grid, and -- 70 and 90 are no
     multiples of 24 -- the scan's single far-corner tile.  One stride tile is labelled below min_valid_ratio and is dropped; the
     class counts run over the labelled cells of the kept tiles, overlaps counted once per tile."""
-    from bathymetric_gnn_amd.training.trainer import plan_ground_truth_tiles
+    from bathymetric_gnn_amd.training.tile_store import plan_ground_truth_tiles
     rng = np.random.default_rng(3)
     labels = rng.choice(np.array([-1, 0, 1, 2], np.int32), size=(70, 90), p=(0.2, 0.6, 0.05, 0.15)).astype(np.int32)
     labels[0:32, 48:80] = -1
@@ -161,7 +161,8 @@ def test_ground_truth_scan():
 def test_training_package_exports():
     """``training.__all__`` stays the reference's loss names; the trainer's classes are importable beside them."""
     import bathymetric_gnn_amd.training as training
-    from bathymetric_gnn_amd.training.trainer import EpochMetrics, StopRule, TileStore, Trainer
+    from bathymetric_gnn_amd.training.tile_store import TileStore
+    from bathymetric_gnn_amd.training.trainer import EpochMetrics, StopRule, Trainer
     assert training.__all__ == ["BathymetricGNNLoss", "ClassificationLoss", "CorrectionLoss", "ConfidenceCalibrationLoss",
                                 "FeaturePreservationLoss", "ShoalSafetyLoss", "compute_class_weights", "compute_correction_delta"]
     for cls in (Trainer, TileStore, EpochMetrics, StopRule):

@@ -275,19 +275,6 @@ def test_training_pair_holds_its_cases(seed):
     assert 0.03 < (lab == 2).mean() < 0.08 and 0.002 < (lab == -1).mean() < 0.03
 
 
-def test_ragged_gather_index_is_the_loop_it_replaced():
-    """``TileStore._gather`` builds the cell index of a ragged batch without a loop over tiles: the same index."""
-    rng = np.random.default_rng(0)
-    cells = rng.integers(1, 60, 200)
-    offsets = np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
-    idx = rng.permutation(200)[:77].astype(np.int64)
-    want = np.concatenate([np.arange(offsets[i], offsets[i + 1], dtype=np.int64) for i in idx])
-    from bathymetric_gnn_amd.training.trainer import ragged_cell_index
-    got = ragged_cell_index(offsets, idx)
-    assert got.dtype == np.int64 and np.array_equal(got, want)
-    assert ragged_cell_index(offsets, idx[:1]).tolist() == list(range(offsets[idx[0]], offsets[idx[0] + 1]))
-
-
 # ---- 3. the C ABI ------------------------------------------------------------------------------------------------------------
 def _header():
     return open(os.path.join(ROOT, "include", "bgnn_vrtruth.h")).read()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The tile gather under the symmetries of the square (include/bgnn_augment.h) against the two other ways to assemble a step's planes.
+"""The tile gather under the symmetries of the square (include/bgnn_augment.h) against torch's way to assemble a step's planes.
 
     python tools/time_tile_augment.py                 # both cases, 30 repetitions after 5 warm-up rounds
     python tools/time_tile_augment.py --what ragged --reps 50
@@ -16,14 +16,11 @@ and per case
             with all-identity ops and with all-90-degree ops; from its bytes -- 2 x (4 x 4 + 1) per cell, read plus written, and 32
             per entry -- the rate and the share of the 8.0 TB/s HBM peak
   gather    ``TileStore.gather`` (the same call behind the allocation of the outputs and the workspace), identity and 90 degrees
-  _gather   ``TileStore._gather``, the path of ``batch(ops=None)``: a per-cell index built on the host for a ragged store, its
-            upload, one ``index_select`` per plane
-  torch     the transform restated with torch: ``rot90`` of every tile's view, ``cat`` per plane (90 degrees; the identity is
-            ``_gather``'s job)
+  torch     the transform restated with torch: ``rot90`` of every tile's view, ``cat`` per plane (90 degrees)
 
 Every figure: the median (and minimum) over ``--reps`` of HIP events on the caller's stream around one call, behind a matrix product
 that keeps the device busy while the host enqueues, and the median of a host clock around the call and a device synchronise (which
-is what a training step waits for when the host is the bottleneck).  The results of the three ways are compared as bits first.
+is what a training step waits for when the host is the bottleneck).  The results of the two ways are compared as bits first.
 
 The events around a call include the table's upload and the hand-over between the caller's stream and the context's.  For the
 kernel alone, run ``--kernel-only OP --what CASE`` under ``rocprofv3 --kernel-trace --stats``: it launches the gather ``--reps``
@@ -139,11 +136,10 @@ def run_case(args, what):
         out.update(op=args.kernel_only, batch_bytes=int(2 * 17 * cells + 32 * batch))
         print(json.dumps(out), flush=True)
         return 0
-    # the three ways agree first
+    # the two ways agree first
     idx = pick(0)
     mixed = (np.arange(batch) % 8).astype(np.int32)
-    got = store.gather(idx, mixed)[2]
-    out["equal_bits"] = same(torch, got, torch_turn(torch, store, idx, mixed)) and same(torch, store.gather(idx, ident)[2], store._gather(idx)[2])
+    out["equal_bits"] = all(same(torch, store.gather(idx, ops)[2], torch_turn(torch, store, idx, ops)) for ops in (mixed, ident))
     if not out["equal_bits"]:
         print(json.dumps(out), flush=True)
         return 1
@@ -159,7 +155,6 @@ def run_case(args, what):
         m["share_of_hbm_peak"] = round(nbytes / (m["device_us_median"] * 1e-6) / HBM_PEAK, 3)
         out[f"call_{name}"] = m
         out[f"gather_{name}"] = measure(torch, lambda r: store.gather(pick(r), ops), args.reps, args.warmup)
-    out["_gather"] = measure(torch, lambda r: store._gather(pick(r)), args.reps, args.warmup)
     out["torch_quarter_turn"] = measure(torch, lambda r: torch_turn(torch, store, pick(r), quarter), max(args.reps // 3, 3), 2)
     print(json.dumps(out), flush=True)
     return 0

@@ -91,7 +91,7 @@ def main():
         rec["loss"] = []
     if a.targets:
         from bathymetric_gnn_amd.data import SyntheticNoiseGenerator, training_targets
-        from bathymetric_gnn_amd.training.trainer import training_targets_fused
+        from bathymetric_gnn_amd.training.tile_store import training_targets_fused
         gb = GraphBuilder()
         hw, res_, clean_t, mask_t, _ = gb.upload_tiles([t[0] for t in tiles], [t[1] for t in tiles], None, [(0.5, 0.5)] * a.tiles)
         nb = SyntheticNoiseGenerator(seed=0).generate_batch(hw, clean_t, mask_t, sample_indices=list(range(a.tiles)))
