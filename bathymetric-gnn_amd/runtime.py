@@ -371,6 +371,27 @@ VT_STATS_BYTES = 48
 VT_STATS_DTYPE = [("valid", "<i8"), ("noise", "<i8"), ("seafloor", "<i8"), ("noise_abs_sum", "<f8"), ("noise_abs_median", "<f8"),
                   ("noise_abs_max", "<f4"), ("pad", "<i4")]
 
+
+# symbol -> (restype, argtypes); every symbol include/bgnn_curve.h declares (operating curves: threshold sweep, correction residuals)
+_CURVE_SIGNATURES = {
+    "bgnn_curve_block_bytes": (C.c_size_t, [C.c_int]),
+    "bgnn_curve_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "bgnn_curve_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
+}
+CURVE_MAX_THRESHOLDS = 128                         # BGNN_CURVE_MAX_THRESHOLDS
+CURVE_WG_CELLS = 1024                              # BGNN_CURVE_WG_CELLS: one workgroup's share of the cells
+CURVE_MAX_GRID = 1024                              # BGNN_CURVE_MAX_GRID
+CURVE_RES_CAP = 32768                              # BGNN_CURVE_RES_CAP
+CURVE_RES_SCALE = 65536                            # BGNN_CURVE_RES_SCALE
+
+
+def curve_block_dtype(n_thresholds: int):
+    """The record of the block of a table of ``n_thresholds`` entries (BGNN_CURVE_*(T)): int64 throughout, B = 2T + 2 codes."""
+    b = 2 * int(n_thresholds) + 2
+    return [("counts", "<i8", (b, 4, 4)), ("res_cells", "<i8", (b, 4)), ("abs_before", "<i8", (b, 4)), ("abs_after", "<i8", (b, 4)),
+            ("base_cells", "<i8", (4,)), ("base_abs", "<i8", (4,)), ("res_skipped", "<i8")]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -382,8 +403,8 @@ class BgnnError(RuntimeError):
 def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
-    include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h, include/bgnn_vrtruth.h and
-    include/bgnn_augment.h.  Needs no GPU."""
+    include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h, include/bgnn_vrtruth.h,
+    include/bgnn_augment.h and include/bgnn_curve.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -398,7 +419,7 @@ def load_library(path: Optional[str] = None):
                 list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
                 list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
                 list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()) + \
-                list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()):
+                list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()) + list(_CURVE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

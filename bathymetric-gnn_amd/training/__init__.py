@@ -4,10 +4,13 @@ training data, the last two lines of a step -- ``clip_grad_norm_`` and ``optimiz
 flat weight blob, the packed model refreshed in place), and the reference's ``Trainer`` over device-resident ``TileStore`` s
 (``tile_store.py``, ``trainer.py``: per-node targets and per-step bookkeeping as kernels of ``include/bgnn_trainer.h``), and the metrics of
 ``scripts/evaluate_model.py`` counted on the device (``evaluation.py``: ``Evaluator``, ``compute_metrics``).  The reference's dataset
-classes themselves (torch_geometric loaders, GDAL, tqdm) stay outside the path."""
+classes themselves (torch_geometric loaders, GDAL, tqdm) stay outside the path.  ``operating_curve.py`` sweeps every confidence
+threshold of a table in one pass over a classified survey and its ground truth (``OperatingCurve``, ``curve_from_block``,
+``recommend_thresholds``)."""
 from .losses import (BathymetricGNNLoss, ClassificationLoss, ConfidenceCalibrationLoss, CorrectionLoss, FeaturePreservationLoss,
                      ShoalSafetyLoss, compute_class_weights, compute_correction_delta)
 from .evaluation import Evaluator, compute_metrics, metrics_from_block
+from .operating_curve import OperatingCurve, curve_accumulate, curve_from_block, recommend_thresholds
 from .optim import FusedAdamW
 from .tile_store import (TileStore, cut_tile_boxes, dihedral_ops, keep_ground_truth_boxes, plan_ground_truth_tiles, plan_tile_boxes,
                          scan_tile_boxes, transformed_tile_table)
