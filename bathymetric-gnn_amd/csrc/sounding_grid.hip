@@ -1,0 +1,309 @@
+// Gridding a point cloud of soundings (include/bgnn_soundings.h): count, mean, standard deviation, minimum and maximum per cell
+// from one pass over (x, y, z), 20 B per sounding, bound by the scattered atomics into the cells.
+//
+//   soundings_add       grid-stride over shares of 1024 soundings, four per thread loaded before any is filed.  A sounding is
+//                       classified (not finite / outside / out of range / accepted) and an accepted one goes into its cell with
+//                       six global integer atomics: n, S1 = sum q, the low and the high words of q^2, and the two extremes under
+//                       the order-preserving map of float32 onto uint32.  The minimum is kept as the maximum of the inverted key,
+//                       so an all-zero state is the empty one.  A swath puts runs of consecutive soundings into one cell: a run of
+//                       neighbouring lanes on one cell is summed towards its first lane inside the wave (a segmented halving over
+//                       shuffles, skipped where no two neighbours of the wave share a cell) and only that lane goes to memory --
+//                       measured on 2e8 soundings: 9.2 ms against 60.7 ms in swath order, 49.6 ms either way when scattered.  The
+//                       four counters are reduced per workgroup (block_reduce) and added with one atomic per workgroup and counter.
+//   soundings_finalize  one thread per cell: the variance numerator n * S2 - S1^2 is formed exactly in 128 bits and rounded once
+//                       to float64 (its low bits folded into a sticky bit of the top 64: there is no 128-bit conversion on the
+//                       device).  Reads the state only.
+//   extent_partial      float64 min / max of the finite x and y: per thread, then the fixed halving tree, one record per
+//   extent_finish       workgroup; a second launch of one workgroup finishes the records.
+//
+// All sums are integers: the order of the atomics does not show in the result.  Compiled with -ffp-contract=off: the cell index
+// and the finalisation round operation by operation as the header states them.
+#include "bgnn_internal.h"
+#include "plane_util.h"
+#include "sounding_cell.h"
+#include "../../include/bgnn_soundings.h"
+
+namespace bgnn {
+
+constexpr int SG_THREADS = BLOCK_THREADS;
+constexpr int SG_ITEMS = 4;                           // soundings per thread and step, a workgroup's width apart: coalesced loads
+constexpr int SG_TILE = SG_THREADS * SG_ITEMS;
+constexpr int SG_FINALIZE_MAX_GRID = 1 << 20;
+constexpr int64_t SG_MAX_DIM = 2147483647;
+
+struct SoundingCell {
+  long long s1;                                       // sum q
+  unsigned long long s2_lo, s2_hi;                    // sum (q^2 & 0xFFFFFFFF), sum (q^2 >> 32): S2 = s2_hi * 2^32 + s2_lo
+  uint32_t n, min_inv, max_key, pad;                  // min_inv: the largest ~key, the key of the minimum inverted
+};
+static_assert(sizeof(SoundingCell) == BGNN_SOUNDINGS_CELL_BYTES, "the cell the header documents");
+
+struct ExtentRecord {
+  double min_x, max_x, min_y, max_y;
+  long long finite_x, finite_y;
+};
+static_assert(sizeof(ExtentRecord) == BGNN_SOUNDINGS_EXTENT_BYTES, "the record the header documents");
+
+__device__ __forceinline__ bool finite_bits64(double v) {
+  return (__double_as_longlong(v) & 0x7FF0000000000000LL) != 0x7FF0000000000000LL;
+}
+
+// float32 onto uint32, order-preserving for every non-NaN value (-0.0 below +0.0)
+__device__ __forceinline__ uint32_t order_key(float v) {
+  const uint32_t u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float order_value(uint32_t key) {
+  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+
+// One sounding per lane into its cell; every lane of the wave calls this.
+__device__ __forceinline__ void file_sounding(SoundingCell *cells, bool ok, int64_t cell, float z) {
+  const long long q = ok ? llrint((double)z * (double)BGNN_SOUNDINGS_SCALE) : 0;     // |q| < 2^31
+  const unsigned long long q2 = (unsigned long long)(q * q);                         // < 2^62
+  const uint32_t key = order_key(z);
+  uint32_t cnt = 1, lo_inv = ~key, hi_key = key;
+  unsigned long long s1 = (unsigned long long)q, s2_lo = q2 & 0xFFFFFFFFull, s2_hi = q2 >> 32;
+  // a run of neighbouring lanes on one cell is summed towards its first lane, which alone goes to memory
+  const int lane = threadIdx.x & 63;
+  const int64_t mine = ok ? cell : (int64_t)-1 - lane;                               // (a rejected lane merges with nobody)
+  const int64_t prev = __shfl_up(mine, 1);
+  const bool head = ok && (lane == 0 || prev != mine);
+  const unsigned long long starts = __ballot(lane == 0 || prev != mine);             // every run start, rejected lanes included
+  if (starts != ~0ull) {                                                             // (wave-uniform) some run is longer than one lane
+    const unsigned long long after = lane == 63 ? 0ull : starts >> (lane + 1);
+    const int room = after ? __ffsll((long long)after) : 64 - lane;                  // lanes from this one to the end of its run
+    int longest = room;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o));
+    for (int d = 1; d < longest; d <<= 1) {                                          // (wave-uniform trip count)
+      const uint32_t c2 = __shfl_down(cnt, d), l2 = __shfl_down(lo_inv, d), h2 = __shfl_down(hi_key, d);
+      const unsigned long long a2 = __shfl_down(s1, d), b2 = __shfl_down(s2_lo, d), e2 = __shfl_down(s2_hi, d);
+      if (d < room) {                                                                // lane + d lies in this lane's run
+        cnt += c2; s1 += a2; s2_lo += b2; s2_hi += e2;
+        lo_inv = max(lo_inv, l2); hi_key = max(hi_key, h2);
+      }
+    }
+  }
+  if (head) {
+    SoundingCell *c = cells + cell;
+    atomicAdd(&c->n, cnt);
+    atomicAdd(reinterpret_cast<unsigned long long *>(&c->s1), s1);
+    atomicAdd(&c->s2_lo, s2_lo);
+    atomicAdd(&c->s2_hi, s2_hi);
+    atomicMax(&c->min_inv, lo_inv);
+    atomicMax(&c->max_key, hi_key);
+  }
+}
+
+__global__ __launch_bounds__(SG_THREADS) void soundings_add(const double *__restrict__ xs, const double *__restrict__ ys,
+                                                            const float *__restrict__ zs, int64_t n, double x0, double y0, double res,
+                                                            int64_t height, int64_t width, char *__restrict__ state) {
+  __shared__ uint32_t scratch[SG_THREADS];
+  SoundingCell *cells = reinterpret_cast<SoundingCell *>(state + BGNN_SOUNDINGS_HEADER_BYTES);
+  const int t = threadIdx.x;
+  uint32_t accepted = 0, nonfinite = 0, outside = 0, out_of_range = 0;      // (a workgroup sees fewer than 2^31 soundings)
+  for (int64_t base = (int64_t)blockIdx.x * SG_TILE; base < n; base += (int64_t)gridDim.x * SG_TILE) {
+    double x[SG_ITEMS], y[SG_ITEMS];
+    float z[SG_ITEMS];
+#pragma unroll
+    for (int k = 0; k < SG_ITEMS; ++k) {
+      const int64_t i = base + k * SG_THREADS + t;
+      const bool in = i < n;
+      x[k] = in ? xs[i] : 0.0;
+      y[k] = in ? ys[i] : 0.0;
+      z[k] = in ? zs[i] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < SG_ITEMS; ++k) {
+      const bool in = base + k * SG_THREADS + t < n;
+      const bool fin = finite_bits64(x[k]) && finite_bits64(y[k]) && finite_bits(z[k]);
+      const int64_t cell = sounding_cell(x[k], y[k], x0, y0, res, height, width);
+      const bool in_range = fabsf(z[k]) < (float)BGNN_SOUNDINGS_Z_CAP;
+      const bool ok = in && fin && cell >= 0 && in_range;
+      nonfinite += in && !fin;
+      outside += in && fin && cell < 0;
+      out_of_range += in && fin && cell >= 0 && !in_range;
+      accepted += ok;
+      file_sounding(cells, ok, cell, z[k]);
+    }
+  }
+  const uint32_t mine[4] = {accepted, nonfinite, outside, out_of_range};
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(state);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t total = block_reduce(mine[j], scratch, SumOp());
+    if (t == 0 && total) atomicAdd(counters + j, (unsigned long long)total);
+  }
+}
+
+// the exact integer v rounded once, half to even, to float64
+__device__ __forceinline__ double u128_to_double(unsigned __int128 v) {
+  const unsigned long long hi = (unsigned long long)(v >> 64), lo = (unsigned long long)v;
+  if (hi == 0) return (double)lo;
+  const int shift = 64 - __clzll((long long)hi);                                     // 1 .. 64: the bits above the top 64
+  unsigned long long top = (unsigned long long)(v >> shift);
+  const unsigned long long below = shift == 64 ? lo : (lo & ((1ull << shift) - 1));
+  top |= below != 0;                                  // sticky: bit 0 lies under the rounding position of a 64-bit value
+  return ldexp((double)top, shift);
+}
+
+__global__ __launch_bounds__(SG_THREADS) void soundings_finalize(const char *__restrict__ state, int64_t n_cells, int32_t min_count,
+                                                                 float nodata, int32_t *__restrict__ count, float *__restrict__ mean,
+                                                                 float *__restrict__ stdev, float *__restrict__ zmin,
+                                                                 float *__restrict__ zmax, uint8_t *__restrict__ valid) {
+  const SoundingCell *cells = reinterpret_cast<const SoundingCell *>(state + BGNN_SOUNDINGS_HEADER_BYTES);
+  const double unscale = 1.0 / (double)BGNN_SOUNDINGS_SCALE;                          // 2^-16: exact
+  for (int64_t i = (int64_t)blockIdx.x * SG_THREADS + threadIdx.x; i < n_cells; i += (int64_t)gridDim.x * SG_THREADS) {
+    const SoundingCell c = cells[i];
+    const bool ok = c.n >= (uint32_t)min_count;       // (min_count >= 1: an empty cell is never valid)
+    float m = nodata, s = nodata, lo = nodata, hi = nodata;
+    if (ok) {
+      const double dn = (double)c.n;
+      m = (float)((double)c.s1 / dn * unscale);
+      const unsigned __int128 s2 = ((unsigned __int128)c.s2_hi << 32) + c.s2_lo;
+      const unsigned long long a1 = (unsigned long long)(c.s1 < 0 ? -c.s1 : c.s1);
+      const unsigned __int128 num = (unsigned __int128)c.n * s2 - (unsigned __int128)a1 * a1;      // >= 0 (Cauchy-Schwarz), < 2^124
+      s = (float)(sqrt(u128_to_double(num) / (dn * dn)) * unscale);
+      lo = order_value(~c.min_inv);
+      hi = order_value(c.max_key);
+    }
+    count[i] = (int32_t)c.n;
+    mean[i] = m;
+    stdev[i] = s;
+    zmin[i] = lo;
+    zmax[i] = hi;
+    valid[i] = ok ? 1 : 0;
+  }
+}
+
+struct MinOp {
+  __device__ __forceinline__ double operator()(double a, double b) const { return b < a ? b : a; }
+};
+struct MaxOp {
+  __device__ __forceinline__ double operator()(double a, double b) const { return b > a ? b : a; }
+};
+
+// every thread holds a record; the workgroup's record lands in *out (thread 0 writes)
+__device__ __forceinline__ void extent_reduce_store(const ExtentRecord &r, ExtentRecord *out) {
+  __shared__ double scratch[SG_THREADS];
+  ExtentRecord w;
+  w.min_x = block_reduce(r.min_x, scratch, MinOp());
+  w.max_x = block_reduce(r.max_x, scratch, MaxOp());
+  w.min_y = block_reduce(r.min_y, scratch, MinOp());
+  w.max_y = block_reduce(r.max_y, scratch, MaxOp());
+  w.finite_x = block_reduce(r.finite_x, scratch, SumOp());
+  w.finite_y = block_reduce(r.finite_y, scratch, SumOp());
+  if (threadIdx.x == 0) *out = w;
+}
+
+__device__ __forceinline__ ExtentRecord extent_empty() {
+  const double inf = __longlong_as_double(0x7FF0000000000000LL);
+  return ExtentRecord{inf, -inf, inf, -inf, 0, 0};
+}
+
+__global__ __launch_bounds__(SG_THREADS) void extent_partial(const double *__restrict__ xs, const double *__restrict__ ys, int64_t n,
+                                                             ExtentRecord *__restrict__ partials) {
+  ExtentRecord r = extent_empty();
+  for (int64_t i = (int64_t)blockIdx.x * SG_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * SG_THREADS) {
+    const double x = xs[i], y = ys[i];
+    if (finite_bits64(x)) { r.min_x = MinOp()(r.min_x, x); r.max_x = MaxOp()(r.max_x, x); ++r.finite_x; }
+    if (finite_bits64(y)) { r.min_y = MinOp()(r.min_y, y); r.max_y = MaxOp()(r.max_y, y); ++r.finite_y; }
+  }
+  extent_reduce_store(r, partials + blockIdx.x);
+}
+
+__global__ __launch_bounds__(SG_THREADS) void extent_finish(const ExtentRecord *__restrict__ partials, int n_partials,
+                                                            ExtentRecord *__restrict__ out) {
+  ExtentRecord r = extent_empty();
+  for (int p = threadIdx.x; p < n_partials; p += SG_THREADS) {
+    const ExtentRecord q = partials[p];
+    r.min_x = MinOp()(r.min_x, q.min_x); r.max_x = MaxOp()(r.max_x, q.max_x);
+    r.min_y = MinOp()(r.min_y, q.min_y); r.max_y = MaxOp()(r.max_y, q.max_y);
+    r.finite_x += q.finite_x; r.finite_y += q.finite_y;
+  }
+  extent_reduce_store(r, out);
+}
+
+static inline bool sg_dim_ok(int64_t v) { return v >= 1 && v <= SG_MAX_DIM; }
+static inline bool sg_aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
+static inline bool sg_finite(double v) { return v - v == 0.0; }
+
+}  // namespace bgnn
+
+using namespace bgnn;
+
+extern "C" size_t bgnn_soundings_state_bytes(int64_t height, int64_t width) {
+  if (!sg_dim_ok(height) || !sg_dim_ok(width)) return 0;
+  const unsigned __int128 bytes = (unsigned __int128)height * (unsigned __int128)width * BGNN_SOUNDINGS_CELL_BYTES + BGNN_SOUNDINGS_HEADER_BYTES;
+  return bytes > (unsigned __int128)SIZE_MAX ? 0 : (size_t)bytes;
+}
+
+#define SG_REQUIRE_GRID(fn)                                                                                                  \
+  BGNN_REQUIRE(sg_dim_ok(height) && sg_dim_ok(width), fn ": a grid of %lld x %lld cells, 1 .. 2147483647 each way expected", \
+               (long long)height, (long long)width)
+
+extern "C" int bgnn_soundings_reset(bgnn_ctx *ctx, void *state, int64_t height, int64_t width) {
+  // (the context last: what is wrong with the other arguments is reported whatever the context)
+  BGNN_REQUIRE(state, "bgnn_soundings_reset: NULL argument");
+  SG_REQUIRE_GRID("bgnn_soundings_reset");
+  BGNN_REQUIRE(bgnn_soundings_state_bytes(height, width) != 0, "bgnn_soundings_reset: the state of %lld x %lld cells exceeds size_t",
+               (long long)height, (long long)width);
+  BGNN_REQUIRE(sg_aligned8(state), "bgnn_soundings_reset: the state is not 8-byte aligned");
+  BGNN_REQUIRE(ctx, "bgnn_soundings_reset: NULL context");
+  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  BGNN_HIP_CHECK(hipMemsetAsync(state, 0, bgnn_soundings_state_bytes(height, width), ctx->stream));
+  return BGNN_OK;
+}
+
+extern "C" int bgnn_soundings_add(bgnn_ctx *ctx, const double *x, const double *y, const float *z, int64_t n, double x0, double y0,
+                                  double res, int64_t height, int64_t width, int64_t offered, void *state) {
+  BGNN_REQUIRE(n >= 0, "bgnn_soundings_add: %lld soundings", (long long)n);
+  BGNN_REQUIRE(state && (n == 0 || (x && y && z)), "bgnn_soundings_add: NULL argument");
+  BGNN_REQUIRE(sg_finite(res) && res > 0.0, "bgnn_soundings_add: a resolution of %g, a finite number above 0 expected", res);
+  BGNN_REQUIRE(sg_finite(x0) && sg_finite(y0), "bgnn_soundings_add: the origin (%g, %g) is not finite", x0, y0);
+  SG_REQUIRE_GRID("bgnn_soundings_add");
+  BGNN_REQUIRE(offered >= 0, "bgnn_soundings_add: %lld soundings offered before", (long long)offered);
+  BGNN_REQUIRE(n <= (int64_t)BGNN_SOUNDINGS_MAX_TOTAL && offered <= (int64_t)BGNN_SOUNDINGS_MAX_TOTAL - n,
+               "bgnn_soundings_add: %lld soundings after %lld offered before: a total above %lld", (long long)n, (long long)offered,
+               (long long)BGNN_SOUNDINGS_MAX_TOTAL);
+  BGNN_REQUIRE(sg_aligned8(state), "bgnn_soundings_add: the state is not 8-byte aligned");
+  BGNN_REQUIRE(ctx, "bgnn_soundings_add: NULL context");
+  if (n == 0) return BGNN_OK;
+  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  const dim3 g(capped_grid((n + SG_TILE - 1) / SG_TILE, PLANE_MAX_GRID)), b(SG_THREADS);
+  hipLaunchKernelGGL(soundings_add, g, b, 0, ctx->stream, x, y, z, n, x0, y0, res, height, width, static_cast<char *>(state));
+  BGNN_HIP_CHECK(hipGetLastError());
+  return BGNN_OK;
+}
+
+extern "C" int bgnn_soundings_finalize(bgnn_ctx *ctx, const void *state, int64_t height, int64_t width, int32_t min_count,
+                                       float nodata_value, int32_t *count, float *mean, float *std, float *min, float *max,
+                                       uint8_t *valid) {
+  BGNN_REQUIRE(state && count && mean && std && min && max && valid, "bgnn_soundings_finalize: NULL argument");
+  SG_REQUIRE_GRID("bgnn_soundings_finalize");
+  BGNN_REQUIRE(min_count >= 1, "bgnn_soundings_finalize: a min_count of %d, at least 1 expected", (int)min_count);
+  BGNN_REQUIRE(sg_aligned8(state), "bgnn_soundings_finalize: the state is not 8-byte aligned");
+  BGNN_REQUIRE(ctx, "bgnn_soundings_finalize: NULL context");
+  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  const int64_t n_cells = height * width;
+  const dim3 g(capped_grid((n_cells + SG_THREADS - 1) / SG_THREADS, SG_FINALIZE_MAX_GRID)), b(SG_THREADS);
+  hipLaunchKernelGGL(soundings_finalize, g, b, 0, ctx->stream, static_cast<const char *>(state), n_cells, min_count, nodata_value, count,
+                     mean, std, min, max, valid);
+  BGNN_HIP_CHECK(hipGetLastError());
+  return BGNN_OK;
+}
+
+extern "C" int bgnn_soundings_extent(bgnn_ctx *ctx, const double *x, const double *y, int64_t n, void *extent) {
+  BGNN_REQUIRE(n >= 0, "bgnn_soundings_extent: %lld soundings", (long long)n);
+  BGNN_REQUIRE(extent && (n == 0 || (x && y)), "bgnn_soundings_extent: NULL argument");
+  BGNN_REQUIRE(sg_aligned8(extent), "bgnn_soundings_extent: the extent buffer is not 8-byte aligned");
+  BGNN_REQUIRE(ctx, "bgnn_soundings_extent: NULL context");
+  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
+  ExtentRecord *records = static_cast<ExtentRecord *>(extent);
+  const int parts = capped_grid((n + SG_TILE - 1) / SG_TILE, BGNN_SOUNDINGS_EXTENT_MAX_GRID);
+  hipLaunchKernelGGL(extent_partial, dim3(parts), dim3(SG_THREADS), 0, ctx->stream, x, y, n, records + 1);
+  hipLaunchKernelGGL(extent_finish, dim3(1), dim3(SG_THREADS), 0, ctx->stream, records + 1, parts, records);
+  BGNN_HIP_CHECK(hipGetLastError());
+  return BGNN_OK;
+}

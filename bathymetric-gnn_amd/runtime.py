@@ -392,6 +392,26 @@ def curve_block_dtype(n_thresholds: int):
             ("base_cells", "<i8", (4,)), ("base_abs", "<i8", (4,)), ("res_skipped", "<i8")]
 
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_soundings.h declares (gridding a point cloud of soundings)
+_SOUNDINGS_SIGNATURES = {
+    "bgnn_soundings_state_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "bgnn_soundings_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "bgnn_soundings_add": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_double] * 3 + [C.c_int64] * 3 + [C.c_void_p]),
+    "bgnn_soundings_finalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_float] + [C.c_void_p] * 6),
+    "bgnn_soundings_extent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+}
+SOUNDINGS_HEADER_BYTES = 32                        # BGNN_SOUNDINGS_HEADER_BYTES
+SOUNDINGS_CELL_BYTES = 40                          # BGNN_SOUNDINGS_CELL_BYTES
+SOUNDINGS_MAX_TOTAL = 2 ** 31 - 1                  # BGNN_SOUNDINGS_MAX_TOTAL
+SOUNDINGS_Z_CAP = 32768                            # BGNN_SOUNDINGS_Z_CAP
+SOUNDINGS_SCALE = 65536                            # BGNN_SOUNDINGS_SCALE
+SOUNDINGS_EXTENT_BUFFER_BYTES = 48 * 1025          # BGNN_SOUNDINGS_EXTENT_BUFFER_BYTES
+SOUNDINGS_COUNTERS = ("accepted", "nonfinite", "outside", "out_of_range")
+# BGNN_SOUNDINGS_EXTENT_BYTES: the record in front of the extent buffer
+SOUNDINGS_EXTENT_DTYPE = np.dtype([("min_x", "<f8"), ("max_x", "<f8"), ("min_y", "<f8"), ("max_y", "<f8"), ("finite_x", "<i8"),
+                                   ("finite_y", "<i8")])
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -404,7 +424,7 @@ def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
     include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h, include/bgnn_vrtruth.h,
-    include/bgnn_augment.h and include/bgnn_curve.h.  Needs no GPU."""
+    include/bgnn_augment.h, include/bgnn_curve.h and include/bgnn_soundings.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -419,7 +439,8 @@ def load_library(path: Optional[str] = None):
                 list(_NOISE_SIGNATURES.items()) + list(_LOSS_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + list(_TRAINER_SIGNATURES.items()) + \
                 list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
                 list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()) + \
-                list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()) + list(_CURVE_SIGNATURES.items()):
+                list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()) + list(_CURVE_SIGNATURES.items()) + \
+                list(_SOUNDINGS_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
