@@ -21,6 +21,7 @@
 #include "bgnn_internal.h"
 #include "plane_util.h"
 #include "sounding_cell.h"
+#include "sounding_moments.h"
 #include "../../include/bgnn_soundings.h"
 
 namespace bgnn {
@@ -137,34 +138,18 @@ __global__ __launch_bounds__(SG_THREADS) void soundings_add(const double *__rest
   }
 }
 
-// the exact integer v rounded once, half to even, to float64
-__device__ __forceinline__ double u128_to_double(unsigned __int128 v) {
-  const unsigned long long hi = (unsigned long long)(v >> 64), lo = (unsigned long long)v;
-  if (hi == 0) return (double)lo;
-  const int shift = 64 - __clzll((long long)hi);                                     // 1 .. 64: the bits above the top 64
-  unsigned long long top = (unsigned long long)(v >> shift);
-  const unsigned long long below = shift == 64 ? lo : (lo & ((1ull << shift) - 1));
-  top |= below != 0;                                  // sticky: bit 0 lies under the rounding position of a 64-bit value
-  return ldexp((double)top, shift);
-}
-
 __global__ __launch_bounds__(SG_THREADS) void soundings_finalize(const char *__restrict__ state, int64_t n_cells, int32_t min_count,
                                                                  float nodata, int32_t *__restrict__ count, float *__restrict__ mean,
                                                                  float *__restrict__ stdev, float *__restrict__ zmin,
                                                                  float *__restrict__ zmax, uint8_t *__restrict__ valid) {
   const SoundingCell *cells = reinterpret_cast<const SoundingCell *>(state + BGNN_SOUNDINGS_HEADER_BYTES);
-  const double unscale = 1.0 / (double)BGNN_SOUNDINGS_SCALE;                          // 2^-16: exact
   for (int64_t i = (int64_t)blockIdx.x * SG_THREADS + threadIdx.x; i < n_cells; i += (int64_t)gridDim.x * SG_THREADS) {
     const SoundingCell c = cells[i];
     const bool ok = c.n >= (uint32_t)min_count;       // (min_count >= 1: an empty cell is never valid)
     float m = nodata, s = nodata, lo = nodata, hi = nodata;
     if (ok) {
-      const double dn = (double)c.n;
-      m = (float)((double)c.s1 / dn * unscale);
-      const unsigned __int128 s2 = ((unsigned __int128)c.s2_hi << 32) + c.s2_lo;
-      const unsigned long long a1 = (unsigned long long)(c.s1 < 0 ? -c.s1 : c.s1);
-      const unsigned __int128 num = (unsigned __int128)c.n * s2 - (unsigned __int128)a1 * a1;      // >= 0 (Cauchy-Schwarz), < 2^124
-      s = (float)(sqrt(u128_to_double(num) / (dn * dn)) * unscale);
+      m = sounding_mean(c.n, c.s1);                    // (sounding_moments.h: the exact numerator rounded once to float64)
+      s = sounding_std(c.n, c.s1, c.s2_lo, c.s2_hi);
       lo = order_value(~c.min_inv);
       hi = order_value(c.max_key);
     }

@@ -65,6 +65,29 @@ def _check_coordinates(x, y, z=None):
         raise TypeError("x, y and z must be all numpy arrays or all torch tensors")
 
 
+def _on_device(x, y, z, device):
+    """x, y, z as contiguous tensors, all of them on ``device`` already (``TypeError`` otherwise)."""
+    for name, t in (("x", x), ("y", y), ("z", z)):
+        if t.device != device:
+            raise TypeError(f"{name} is on {t.device}, the gridder on {device}")
+    return x.contiguous(), y.contiguous(), z.contiguous()
+
+
+def _feed(x, y, z, device, add_device):
+    """The checked x, y, z to ``add_device(x, y, z)``: device tensors as they lie, host arrays ``UPLOAD_CHUNK`` soundings at a time
+    (one call each); nothing for an empty set.  Shared by the gridders."""
+    n = int(x.shape[0])
+    if n == 0:
+        return
+    if isinstance(x, torch.Tensor) and x.device.type == "cuda":
+        add_device(x, y, z)
+        return
+    as_tensor = (lambda a: a) if isinstance(x, torch.Tensor) else (lambda a: torch.from_numpy(np.ascontiguousarray(a)))
+    for lo in range(0, n, UPLOAD_CHUNK):
+        hi = min(n, lo + UPLOAD_CHUNK)
+        add_device(*(as_tensor(a[lo:hi]).to(device) for a in (x, y, z)))
+
+
 def sounding_extent(x: torch.Tensor, y: torch.Tensor) -> Dict[str, float]:
     """``bgnn_soundings_extent`` on device tensors: the float64 ``min_x``, ``max_x``, ``min_y``, ``max_y`` over the finite values of
     each coordinate and their counts ``finite_x``, ``finite_y`` (+inf / -inf / 0 where none is finite).  One small copy to the host."""
@@ -189,10 +212,7 @@ class SoundingGridder:
 
     def _add_device(self, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor):
         n = int(x.shape[0])
-        for name, t in (("x", x), ("y", y), ("z", z)):
-            if t.device != self.device:
-                raise TypeError(f"{name} is on {t.device}, the gridder on {self.device}")
-        x, y, z = x.contiguous(), y.contiguous(), z.contiguous()
+        x, y, z = _on_device(x, y, z, self.device)
         ctx = self._ctx
         ctx.begin()
         rt.check(ctx.lib.bgnn_soundings_add(ctx.handle, rt.ptr(x), rt.ptr(y), rt.ptr(z), n, self.origin[0], self.origin[1],
@@ -206,15 +226,7 @@ class SoundingGridder:
         n = int(x.shape[0])
         if self.offered + n > MAX_TOTAL:
             raise ValueError(f"{n} soundings after {self.offered} offered before: a total above {MAX_TOTAL}")
-        if n == 0:
-            return
-        if isinstance(x, torch.Tensor) and x.device.type == "cuda":
-            self._add_device(x, y, z)
-            return
-        as_tensor = (lambda a: a) if isinstance(x, torch.Tensor) else (lambda a: torch.from_numpy(np.ascontiguousarray(a)))
-        for lo in range(0, n, UPLOAD_CHUNK):
-            hi = min(n, lo + UPLOAD_CHUNK)
-            self._add_device(*(as_tensor(a[lo:hi]).to(self.device) for a in (x, y, z)))
+        _feed(x, y, z, self.device, self._add_device)
 
     def counters(self) -> Dict[str, int]:
         """``accepted``, ``nonfinite``, ``outside``, ``out_of_range`` over everything added: one 32-byte copy to the host."""

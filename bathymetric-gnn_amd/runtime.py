@@ -411,6 +411,24 @@ SOUNDINGS_COUNTERS = ("accepted", "nonfinite", "outside", "out_of_range")
 SOUNDINGS_EXTENT_DTYPE = np.dtype([("min_x", "<f8"), ("max_x", "<f8"), ("min_y", "<f8"), ("max_y", "<f8"), ("finite_x", "<i8"),
                                    ("finite_y", "<i8")])
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_soundings_robust.h declares (robust gridding: per-cell median, MAD, flags)
+_ROBUST_SIGNATURES = {
+    "bgnn_soundings_robust_stage_bytes": (C.c_size_t, [C.c_int64]),
+    "bgnn_soundings_robust_workspace_bytes": (C.c_size_t, [C.c_int64] * 3),
+    "bgnn_soundings_robust_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bgnn_soundings_robust_add": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_double] * 3 + [C.c_int64] * 4 + [C.c_void_p]),
+    "bgnn_soundings_robust_finalize": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int64] * 4 + [C.c_double] * 2 + [C.c_int32, C.c_float,
+                                                 C.c_void_p, C.c_size_t] + [C.c_void_p] * 13),
+    "bgnn_soundings_robust_flag": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_double] * 3 + [C.c_int64] * 2 + [C.c_void_p] * 3),
+}
+ROBUST_STAGE_HEADER_BYTES = 32                     # BGNN_ROBUST_STAGE_HEADER_BYTES
+ROBUST_SLOT_BYTES = 8                              # BGNN_ROBUST_SLOT_BYTES
+ROBUST_MAX_CAPACITY = 2 ** 31 - 1                  # BGNN_ROBUST_MAX_CAPACITY
+ROBUST_MAX_CELLS = 2 ** 31 - 1                     # BGNN_ROBUST_MAX_CELLS
+ROBUST_WAVE_MAX = 64                               # BGNN_ROBUST_WAVE_MAX: the longest segment ranked inside a wave
+ROBUST_LDS_MAX = 4096                              # BGNN_ROBUST_LDS_MAX: the longest segment one workgroup sorts in LDS
+ROBUST_FLAGS = ("kept", "rejected", "not_accepted")  # BGNN_ROBUST_FLAG_*: 0, 1, 2
+
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -424,7 +442,7 @@ def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
     include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h, include/bgnn_vrtruth.h,
-    include/bgnn_augment.h, include/bgnn_curve.h and include/bgnn_soundings.h.  Needs no GPU."""
+    include/bgnn_augment.h, include/bgnn_curve.h, include/bgnn_soundings.h and include/bgnn_soundings_robust.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -440,7 +458,7 @@ def load_library(path: Optional[str] = None):
                 list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
                 list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()) + \
                 list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()) + list(_CURVE_SIGNATURES.items()) + \
-                list(_SOUNDINGS_SIGNATURES.items()):
+                list(_SOUNDINGS_SIGNATURES.items()) + list(_ROBUST_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
