@@ -2,7 +2,7 @@
 // from one pass over (x, y, z), 20 B per sounding, bound by the scattered atomics into the cells.
 //
 //   soundings_add       grid-stride over shares of 1024 soundings, four per thread loaded before any is filed.  A sounding is
-//                       classified (not finite / outside / out of range / accepted) and an accepted one goes into its cell with
+//                       classified (sounding_file.h: not finite / outside / out of range / accepted) and an accepted one goes into its cell with
 //                       six global integer atomics: n, S1 = sum q, the low and the high words of q^2, and the two extremes under
 //                       the order-preserving map of float32 onto uint32.  The minimum is kept as the maximum of the inverted key,
 //                       so an all-zero state is the empty one.  A swath puts runs of consecutive soundings into one cell: a run of
@@ -21,6 +21,7 @@
 #include "bgnn_internal.h"
 #include "plane_util.h"
 #include "sounding_cell.h"
+#include "sounding_file.h"
 #include "sounding_moments.h"
 #include "../../include/bgnn_soundings.h"
 
@@ -32,70 +33,11 @@ constexpr int SG_TILE = SG_THREADS * SG_ITEMS;
 constexpr int SG_FINALIZE_MAX_GRID = 1 << 20;
 constexpr int64_t SG_MAX_DIM = 2147483647;
 
-struct SoundingCell {
-  long long s1;                                       // sum q
-  unsigned long long s2_lo, s2_hi;                    // sum (q^2 & 0xFFFFFFFF), sum (q^2 >> 32): S2 = s2_hi * 2^32 + s2_lo
-  uint32_t n, min_inv, max_key, pad;                  // min_inv: the largest ~key, the key of the minimum inverted
-};
-static_assert(sizeof(SoundingCell) == BGNN_SOUNDINGS_CELL_BYTES, "the cell the header documents");
-
 struct ExtentRecord {
   double min_x, max_x, min_y, max_y;
   long long finite_x, finite_y;
 };
 static_assert(sizeof(ExtentRecord) == BGNN_SOUNDINGS_EXTENT_BYTES, "the record the header documents");
-
-__device__ __forceinline__ bool finite_bits64(double v) {
-  return (__double_as_longlong(v) & 0x7FF0000000000000LL) != 0x7FF0000000000000LL;
-}
-
-// float32 onto uint32, order-preserving for every non-NaN value (-0.0 below +0.0)
-__device__ __forceinline__ uint32_t order_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float order_value(uint32_t key) {
-  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
-
-// One sounding per lane into its cell; every lane of the wave calls this.
-__device__ __forceinline__ void file_sounding(SoundingCell *cells, bool ok, int64_t cell, float z) {
-  const long long q = ok ? llrint((double)z * (double)BGNN_SOUNDINGS_SCALE) : 0;     // |q| < 2^31
-  const unsigned long long q2 = (unsigned long long)(q * q);                         // < 2^62
-  const uint32_t key = order_key(z);
-  uint32_t cnt = 1, lo_inv = ~key, hi_key = key;
-  unsigned long long s1 = (unsigned long long)q, s2_lo = q2 & 0xFFFFFFFFull, s2_hi = q2 >> 32;
-  // a run of neighbouring lanes on one cell is summed towards its first lane, which alone goes to memory
-  const int lane = threadIdx.x & 63;
-  const int64_t mine = ok ? cell : (int64_t)-1 - lane;                               // (a rejected lane merges with nobody)
-  const int64_t prev = __shfl_up(mine, 1);
-  const bool head = ok && (lane == 0 || prev != mine);
-  const unsigned long long starts = __ballot(lane == 0 || prev != mine);             // every run start, rejected lanes included
-  if (starts != ~0ull) {                                                             // (wave-uniform) some run is longer than one lane
-    const unsigned long long after = lane == 63 ? 0ull : starts >> (lane + 1);
-    const int room = after ? __ffsll((long long)after) : 64 - lane;                  // lanes from this one to the end of its run
-    int longest = room;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o));
-    for (int d = 1; d < longest; d <<= 1) {                                          // (wave-uniform trip count)
-      const uint32_t c2 = __shfl_down(cnt, d), l2 = __shfl_down(lo_inv, d), h2 = __shfl_down(hi_key, d);
-      const unsigned long long a2 = __shfl_down(s1, d), b2 = __shfl_down(s2_lo, d), e2 = __shfl_down(s2_hi, d);
-      if (d < room) {                                                                // lane + d lies in this lane's run
-        cnt += c2; s1 += a2; s2_lo += b2; s2_hi += e2;
-        lo_inv = max(lo_inv, l2); hi_key = max(hi_key, h2);
-      }
-    }
-  }
-  if (head) {
-    SoundingCell *c = cells + cell;
-    atomicAdd(&c->n, cnt);
-    atomicAdd(reinterpret_cast<unsigned long long *>(&c->s1), s1);
-    atomicAdd(&c->s2_lo, s2_lo);
-    atomicAdd(&c->s2_hi, s2_hi);
-    atomicMax(&c->min_inv, lo_inv);
-    atomicMax(&c->max_key, hi_key);
-  }
-}
 
 __global__ __launch_bounds__(SG_THREADS) void soundings_add(const double *__restrict__ xs, const double *__restrict__ ys,
                                                             const float *__restrict__ zs, int64_t n, double x0, double y0, double res,
@@ -118,14 +60,13 @@ __global__ __launch_bounds__(SG_THREADS) void soundings_add(const double *__rest
 #pragma unroll
     for (int k = 0; k < SG_ITEMS; ++k) {
       const bool in = base + k * SG_THREADS + t < n;
-      const bool fin = finite_bits64(x[k]) && finite_bits64(y[k]) && finite_bits(z[k]);
       const int64_t cell = sounding_cell(x[k], y[k], x0, y0, res, height, width);
-      const bool in_range = fabsf(z[k]) < (float)BGNN_SOUNDINGS_Z_CAP;
-      const bool ok = in && fin && cell >= 0 && in_range;
-      nonfinite += in && !fin;
-      outside += in && fin && cell < 0;
-      out_of_range += in && fin && cell >= 0 && !in_range;
+      const int kind = in ? sounding_kind(x[k], y[k], z[k], cell >= 0, true) : -1;
+      const bool ok = kind == SOUNDING_ACCEPTED;
       accepted += ok;
+      nonfinite += kind == SOUNDING_NONFINITE;
+      outside += kind == SOUNDING_OUTSIDE;
+      out_of_range += kind == SOUNDING_OUT_OF_RANGE;
       file_sounding(cells, ok, cell, z[k]);
     }
   }

@@ -25,6 +25,7 @@
 #include "bgnn_internal.h"
 #include "plane_util.h"
 #include "sounding_cell.h"
+#include "sounding_file.h"
 #include "sounding_moments.h"
 #include "sounding_rank.h"
 #include "../../include/bgnn_soundings.h"
@@ -46,19 +47,11 @@ constexpr int64_t RB_MAX_DIM = 2147483647;
 static_assert(ROBUST_WAVE_MAX == 64, "robust_sort_short ranks one sounding per lane");
 static_assert((ROBUST_LDS_MAX & (ROBUST_LDS_MAX - 1)) == 0 && ROBUST_LDS_MAX >= 2 * RB_THREADS, "the bitonic network pads to a power of two");
 
-__device__ __forceinline__ bool rb_finite64(double v) {
-  return (__double_as_longlong(v) & 0x7FF0000000000000LL) != 0x7FF0000000000000LL;
-}
-
-// 0 accepted, 1 nonfinite, 2 outside, 3 out of range: the order of bgnn_soundings.h
+// 0 accepted, 1 nonfinite, 2 outside, 3 out of range: the order of bgnn_soundings.h (sounding_file.h)
 __device__ __forceinline__ int rb_classify(double x, double y, float z, double x0, double y0, double res, int64_t height,
                                            int64_t width, int64_t *cell) {
-  const bool fin = rb_finite64(x) && rb_finite64(y) && finite_bits(z);
   *cell = sounding_cell(x, y, x0, y0, res, height, width);
-  if (!fin) return 1;
-  if (*cell < 0) return 2;
-  if (!(fabsf(z) < (float)BGNN_SOUNDINGS_Z_CAP)) return 3;
-  return 0;
+  return sounding_kind(x, y, z, *cell >= 0, true);
 }
 
 __global__ __launch_bounds__(RB_THREADS) void robust_add(const double *__restrict__ xs, const double *__restrict__ ys,

@@ -1,5 +1,5 @@
 """Mirror of the reference's ``data`` package for the hot path: graph construction, tiling, synthetic training
-noise, ground truth from a clean / noisy survey pair, feature labels from charted objects and from the slope, low-confidence regions for review, gridding a point cloud of soundings (streaming sums, and the robust gridder: per-cell median, MAD and flags) and the ``BathymetricGrid`` container (file-format I/O -- GDAL / h5py -- is outside the path; VR BAGs enter as their two HDF5 arrays)."""
+noise, ground truth from a clean / noisy survey pair, feature labels from charted objects and from the slope, low-confidence regions for review, gridding a point cloud of soundings (streaming sums, the robust gridder: per-cell median, MAD and flags, and both at variable resolution: straight into the refinement records of a VR layout) and the ``BathymetricGrid`` container (file-format I/O -- GDAL / h5py -- is outside the path; VR BAGs enter as their two HDF5 arrays)."""
 from .graph_construction import GraphBuilder, GraphData, Data
 from .grid import BathymetricGrid
 from .tiling import Tile, TileSpec, TileManager, TileMerger
@@ -14,6 +14,8 @@ from .slope_features import add_feature_labels, create_feature_mask_from_slope, 
 from .vr_ground_truth import NativeGroundTruth, VRPairTable, compute_ground_truth_native, vr_pair_table
 from .sounding_grid import SoundingGrid, SoundingGridder, grid_soundings, plan_sounding_grid, sounding_extent
 from .sounding_robust import RobustSoundingGrid, RobustSoundingGridder, grid_soundings_robust
+from .sounding_vr import (RobustVRSoundingGrid, RobustVRSoundingGridder, VRLayout, VRLayoutPlanner, VRSoundingGrid, VRSoundingGridder,
+                          plan_vr_base_grid, plan_vr_layout)
 
 __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "TileSpec", "TileManager", "TileMerger",
            "RefinementGrid", "VRBagHandler", "VRBagWriter", "SRBagHandler", "SRBagWriter", "SidecarBuilder", "detect_bag_type",
@@ -25,4 +27,6 @@ __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "Tile
            "add_feature_labels", "create_feature_mask_from_slope", "slope_cut", "wreck_pixel_table",
            "NativeGroundTruth", "VRPairTable", "compute_ground_truth_native", "vr_pair_table",
            "SoundingGrid", "SoundingGridder", "grid_soundings", "plan_sounding_grid", "sounding_extent",
-           "RobustSoundingGrid", "RobustSoundingGridder", "grid_soundings_robust"]
+           "RobustSoundingGrid", "RobustSoundingGridder", "grid_soundings_robust",
+           "VRLayout", "VRLayoutPlanner", "VRSoundingGrid", "VRSoundingGridder", "RobustVRSoundingGrid", "RobustVRSoundingGridder",
+           "plan_vr_base_grid", "plan_vr_layout"]

@@ -429,6 +429,27 @@ ROBUST_WAVE_MAX = 64                               # BGNN_ROBUST_WAVE_MAX: the l
 ROBUST_LDS_MAX = 4096                              # BGNN_ROBUST_LDS_MAX: the longest segment one workgroup sorts in LDS
 ROBUST_FLAGS = ("kept", "rejected", "not_accepted")  # BGNN_ROBUST_FLAG_*: 0, 1, 2
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_soundings_vr.h declares (gridding soundings at variable resolution)
+_VR_CLOUD = [C.c_void_p] * 4 + [C.c_int64] + [C.c_double] * 3 + [C.c_int64] * 2       # ctx, x, y, z, n, x0, y0, base_res, BH, BW
+_VR_SOUNDINGS_SIGNATURES = {
+    "bgnn_vr_soundings_plan_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "bgnn_vr_soundings_density": (C.c_int, _VR_CLOUD + [C.c_void_p]),
+    "bgnn_vr_soundings_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "bgnn_vr_soundings_add": (C.c_int, _VR_CLOUD + [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bgnn_vr_soundings_stage": (C.c_int, _VR_CLOUD + [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bgnn_vr_soundings_flag": (C.c_int, _VR_CLOUD + [C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
+}
+VR_ENTRY_BYTES = 16                                # BGNN_VR_ENTRY_BYTES
+VR_ENTRY_DTYPE = np.dtype([("index", "<i8"), ("dx", "<i4"), ("dy", "<i4")])
+VR_MAX_DIM = 32768                                 # BGNN_VR_MAX_DIM
+VR_MAX_RUNGS = 16                                  # BGNN_VR_MAX_RUNGS
+VR_MAX_BASE_CELLS = 2 ** 31 - 1                    # BGNN_VR_MAX_BASE_CELLS
+VR_MAX_RECORDS = 2 ** 31 - 1                       # BGNN_VR_MAX_RECORDS
+VR_MAX_TARGET = 2 ** 31 - 1                        # BGNN_VR_MAX_TARGET
+VR_PLAN_TILE = 256                                 # BGNN_VR_PLAN_TILE
+VR_SOUNDINGS_COUNTERS = SOUNDINGS_COUNTERS + ("unrefined",)
+
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -442,7 +463,8 @@ def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
     include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h, include/bgnn_vrtruth.h,
-    include/bgnn_augment.h, include/bgnn_curve.h, include/bgnn_soundings.h and include/bgnn_soundings_robust.h.  Needs no GPU."""
+    include/bgnn_augment.h, include/bgnn_curve.h, include/bgnn_soundings.h, include/bgnn_soundings_robust.h and
+    include/bgnn_soundings_vr.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -458,7 +480,7 @@ def load_library(path: Optional[str] = None):
                 list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
                 list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()) + \
                 list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()) + list(_CURVE_SIGNATURES.items()) + \
-                list(_SOUNDINGS_SIGNATURES.items()) + list(_ROBUST_SIGNATURES.items()):
+                list(_SOUNDINGS_SIGNATURES.items()) + list(_ROBUST_SIGNATURES.items()) + list(_VR_SOUNDINGS_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
