@@ -141,6 +141,11 @@ __global__ void pad_rows8_kernel(const float *x, int in, float *x8, int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n * 8) x8[i] = (i & 7) < in ? x[(i >> 3) * in + (i & 7)] : 0.0f;
 }
+// ... -> x16 [n][16] for in > 8 (the wide node table of bgnn_aux.h)
+__global__ void pad_rows16_kernel(const float *x, int in, float *x16, int64_t n) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n * 16) x16[i] = (i & 15) < in ? x[(i >> 4) * in + (i & 15)] : 0.0f;
+}
 
 __global__ void copy_cols_kernel(const float *src, int src_stride, float *dst, int dst_stride, int n_copy, const int64_t *d_m) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -379,6 +384,11 @@ static int forward_infer(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_
   const int hid = d.hidden;
   float *X = t.X, *Y = t.Y, *asdX = t.asdX, *asdY = t.asdY;
   const bool use_fused = ctx->opts.fused;
+  // the node table: 8-column rows, or the wide table of a build with auxiliary planes (bgnn_aux.h).  Kx: rows of fe_W0t.  The
+  // forms that read the table inside another kernel (fused front, aggregate-first extractor) know 8-column rows only
+  const float *xt = g->d_x;
+  const int ldx = g->ldx, Kx = extractor_rows(d.in_channels);
+  const bool x8rows = ldx == 8;
   // matrix_path 3 (BASELINE config 3): layer activations xw are stored as bf16 and multiplied on the bf16 MFMA; it exists
   // only on the fused stencil path of the default model shape
   const bool bf16 = ctx->opts.matrix_path == 3;
@@ -393,7 +403,7 @@ static int forward_infer(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_
   if (!gat) {
     // GCN / GraphSAGE / GIN backbones (gnn.py:120-143; torch_geometric default arguments): plain gathers + GEMMs.
     // Not the hot path: no fusion beyond BatchNorm / bias / ReLU folded into the neighbouring kernel.
-    BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, 8, hid, 1));
+    BGNN_TRY(launch_gemm_f32(ctx, xt, ldx, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, Kx, hid, 1));
     BGNN_TRY(launch_gemm_f32(ctx, Y, hid, m->fe_W1t, m->fe_b1, X, hid, dm, rows, hid, hid, 0));
     float *dinv = asdX;
     if (d.gnn_type == BGNN_GNN_GCN) BGNN_TRY(launch_degree_inv_sqrt(ctx, g, dinv));
@@ -439,7 +449,8 @@ static int forward_infer(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_
       const float *wsplit = sm == 3 ? m->l0f_Wbf : sm == 2 && m->l0f_Wsp16 ? m->l0f_Wsp16 : sm ? m->l0f_Wsp : nullptr;
       // extractor layer 1 runs inside the lin_0 GEMM (same instructions, h1 never leaves the registers) wherever that GEMM takes
       // its W-resident form; below 32 768 rows (exact path) it keeps its own launch -- the results are bit-identical either way
-      const bool front = hid == 64 && gemm_front_available(ctx, rows, L0.heads * hid, smode);
+      const bool front = x8rows && hid == 64 && gemm_front_available(ctx, rows, L0.heads * hid, smode);
+      BGNN_REQUIRE(x8rows || sm != 3, "matrix_path = bf16 reads 8-column node rows: not for a graph built with auxiliary planes");
       BGNN_REQUIRE(front || sm != 3, "matrix_path = bf16 needs fused_front = 1");
       // bf16 path, default shape: layer 0 aggregates the extractor's h1 and applies lin_0 afterwards, inside the fused launch
       // (gat_layer_bf16_2p_kernel, AF) -- no lin_0 product in HBM, no front GEMM
@@ -455,7 +466,7 @@ static int forward_infer(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_
         }
       }
       if (!layer0_done) {
-      if (!front) BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, 8, hid, 1));
+      if (!front) BGNN_TRY(launch_gemm_f32(ctx, xt, ldx, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, Kx, hid, 1));
       BGNN_TRY(launch_gemm_f32(ctx, front ? g->d_x8 : Y, front ? 8 : hid, m->l0f_Wt, m->l0f_b, X, L0.heads * hid, dm, rows, hid,
                                L0.heads * hid, 0, L0.att_src, L0.att_dst, asdX, L0.heads, hid, wsplit, smode,
                                front ? m->fe_W0t : nullptr, front ? m->fe_b0 : nullptr, front && smode == 0 ? m->l0f_Wpm : nullptr,
@@ -463,7 +474,7 @@ static int forward_infer(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, float thr_
       }
     } else {
       BGNN_REQUIRE(!bf16, "matrix_path = bf16 needs fold_extractor = 1");
-      BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, X, hid, dm, rows, 8, hid, 1));
+      BGNN_TRY(launch_gemm_f32(ctx, xt, ldx, m->fe_W0t, m->fe_b0, X, hid, dm, rows, Kx, hid, 1));
       BGNN_TRY(launch_gemm_f32(ctx, X, hid, m->fe_W1t, m->fe_b1, Y, hid, dm, rows, hid, hid, 0));
       BGNN_TRY(launch_gemm_f32(ctx, Y, L0.d_in, L0.Wt, nullptr, X, L0.heads * hid, dm, rows, L0.d_in, L0.heads * hid, 0,
                                L0.att_src, L0.att_dst, asdX, L0.heads, hid, nullptr, 0, nullptr, nullptr, nullptr, L0.Wt_blk));
@@ -528,16 +539,20 @@ int bgnn_feature_extractor(bgnn_ctx *ctx, bgnn_model *m, const float *x, int64_t
   if (n_nodes == 0) return BGNN_OK;
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
   BGNN_TRY(model_sync(ctx, m));
-  const int hid = m->desc.hidden, in = m->desc.in_channels;
+  const int hid = m->desc.hidden, in = m->desc.in_channels, Kx = extractor_rows(in);
   void *px8, *ph;
-  BGNN_TRY(ctx_workspace(ctx, 0, (size_t)n_nodes * 8 * sizeof(float), &px8));
+  BGNN_TRY(ctx_workspace(ctx, 0, (size_t)n_nodes * Kx * sizeof(float), &px8));
   BGNN_TRY(ctx_workspace(ctx, 1, (size_t)n_nodes * hid * sizeof(float), &ph));
   int64_t *dn;
   BGNN_TRY(row_count_on_device(ctx, n_nodes, &dn));
-  hipLaunchKernelGGL(pad_rows8_kernel, dim3((unsigned)((n_nodes * 8 + 255) / 256)), dim3(256), 0, ctx->stream, x, in,
-                     (float *)px8, n_nodes);
+  if (Kx == 8)
+    hipLaunchKernelGGL(pad_rows8_kernel, dim3((unsigned)((n_nodes * 8 + 255) / 256)), dim3(256), 0, ctx->stream, x, in,
+                       (float *)px8, n_nodes);
+  else
+    hipLaunchKernelGGL(pad_rows16_kernel, dim3((unsigned)((n_nodes * 16 + 255) / 256)), dim3(256), 0, ctx->stream, x, in,
+                       (float *)px8, n_nodes);
   BGNN_HIP_CHECK(hipGetLastError());
-  BGNN_TRY(launch_gemm_f32(ctx, (const float *)px8, 8, m->fe_W0t, m->fe_b0, (float *)ph, hid, dn, n_nodes, 8, hid, 1));
+  BGNN_TRY(launch_gemm_f32(ctx, (const float *)px8, Kx, m->fe_W0t, m->fe_b0, (float *)ph, hid, dn, n_nodes, Kx, hid, 1));
   if (!m->padded) return launch_gemm_f32(ctx, (const float *)ph, hid, m->fe_W1t, m->fe_b1, out, hid, dn, n_nodes, hid, hid, 0);
   void *po;                                               // padded width: out is [n][logical hidden]
   BGNN_TRY(ctx_workspace(ctx, 2, (size_t)n_nodes * hid * sizeof(float), &po));
@@ -575,13 +590,23 @@ int bgnn_heads(bgnn_ctx *ctx, bgnn_model *m, const float *hidden, int64_t n_node
 int bgnn_infer_tiles(bgnn_ctx *ctx, bgnn_model *m, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, float thr_auto,
                      float thr_review, float norm_floor, float *classification, float *confidence, float *correction,
                      int64_t *n_nodes_out) {
+  return infer_tiles(ctx, m, tiles, opts, 0, nullptr, thr_auto, thr_review, norm_floor, classification, confidence, correction,
+                     n_nodes_out);
+}
+
+}  // extern "C"
+
+// bgnn_infer_tiles, and bgnn_infer_tiles_aux (node_aux.hip) with its planes
+int bgnn::infer_tiles(bgnn_ctx *ctx, bgnn_model *m, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, int32_t n_aux,
+                      const float *const *aux, float thr_auto, float thr_review, float norm_floor, float *classification,
+                      float *confidence, float *correction, int64_t *n_nodes_out) {
   BGNN_REQUIRE(ctx && m && tiles && opts, "bgnn_infer_tiles: NULL argument");
   BGNN_REQUIRE(m->ctx == ctx, "bgnn_infer_tiles: model belongs to another context");
   BGNN_TRY(model_sync(ctx, m));
   bgnn_graph *g = nullptr;
   float *const grids[3] = {classification, confidence, correction};
   // (the compaction scan writes the node count there itself; a ragged batch's canvas fill zero-fills the result grids on its way)
-  BGNN_TRY(graph_build(ctx, tiles, opts, &g, n_nodes_out, grids));
+  BGNN_TRY(graph_build(ctx, tiles, opts, &g, n_nodes_out, grids, n_aux, aux));
   const int64_t rows = g->row_capacity;
   GridOut go;
   go.cls = classification; go.conf = confidence; go.corr = correction; go.norm_floor = norm_floor;
@@ -616,6 +641,4 @@ int bgnn_infer_tiles(bgnn_ctx *ctx, bgnn_model *m, const bgnn_tiles *tiles, cons
   graph_free(g);   // buffers return to the pool; stream order keeps them valid for the work already queued
   return rc;
 }
-
-}  // extern "C"
 

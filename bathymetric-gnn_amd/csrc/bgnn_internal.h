@@ -13,6 +13,7 @@
 #include "../../include/bgnn.h"
 #include "../../include/bgnn_train.h"
 #include "../../include/bgnn_optim.h"
+#include "../../include/bgnn_aux.h"
 #include "model_images.h"   // WeightLayout, ImageMap: the weight blob's and the packed model's layouts (host only)
 #include "graph_plan.h"     // BgnnTileMeta, BgnnWorkItem, GraphPlan: the layout of a tile batch (host only)
 
@@ -176,7 +177,7 @@ struct bgnn_model {
   bgnn::WeightLayout weights; // of `desc`: where `raw` (and the gradient blob of bgnn_backward) holds which tensor
   bgnn::ImageMap images;      // of `desc`: where `blob` holds which image (fixed at creation: a refresh or a sync moves nothing)
   float *blob = nullptr;      // one device allocation holding everything below, images.total floats
-  float *fe_W0t, *fe_b0, *fe_W1t, *fe_b1;     // [in8][hid], [hid], [hid][hid], [hid]
+  float *fe_W0t, *fe_b0, *fe_W1t, *fe_b1;     // [8 or 16 rows][hid] (16: in_channels > 8), [hid], [hid][hid], [hid]
   float *l0f_Wt, *l0f_b;      // [hid][HC0], [HC0]: second extractor layer folded into lin of layer 0 (no activation between)
   float *l0f_Wsp = nullptr, *l0f_Wsp16 = nullptr;   // l0f_Wt as bf16 / float16 hi / lo split images
   float *l0f_Wbf = nullptr, *hd_W0bf = nullptr;     // l0f_Wt / hd_W0t as bf16 (hi only) images
@@ -229,6 +230,11 @@ struct bgnn_graph {
   bool tables_cached = false;         // d_tiles / d_items belong to the context's table cache (uniform batches)
   uint64_t table_cache_id = 0;        // ... the entry this graph holds a reference on (0: none)
   float *d_x8 = nullptr;              // [rows][8]
+  // the node table the model reads: d_x8 (ldx 8), or the wide table of a build with auxiliary planes (bgnn_aux.h, node_aux.hip):
+  // [rows][16], columns < F0 the words of d_x8, then the planes' values, then zeros
+  float *d_x16 = nullptr;
+  const float *d_x = nullptr;
+  int32_t ldx = 8;
   float *d_local_std = nullptr;       // [rows]
   int32_t *d_nbr = nullptr;           // grid: [rows][K] ; generic: col[E]
   // grid graphs: the stencil id table is built ON DEMAND (ensure_stencil_table): the fused layer kernels never read it -- only
@@ -284,8 +290,15 @@ int ctx_upload(bgnn_ctx *ctx, const void *host, size_t bytes, void *dev);
 
 // ---- graph handles (graph_api.hip) ----------------------------------------------------------
 // bgnn_graph_build with the two extras of bgnn_infer_tiles: the caller's copy of the node count, the result grids a canvas fill clears
+// n_aux / aux: the planes of bgnn_graph_build_aux (bgnn_aux.h), checked by aux_planes_check
 int graph_build(bgnn_ctx *ctx, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, bgnn_graph **out, int64_t *n_nodes_copy,
-                float *const *clear_grids);
+                float *const *clear_grids, int32_t n_aux = 0, const float *const *aux = nullptr);
+// the argument checks of the two entry points of bgnn_aux.h: host arithmetic only (no context, no device)
+int aux_planes_check(const char *who, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, int32_t n_aux, const float *const *aux);
+// bgnn_infer_tiles / bgnn_infer_tiles_aux (bgnn_api.hip)
+int infer_tiles(bgnn_ctx *ctx, bgnn_model *m, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, int32_t n_aux,
+                const float *const *aux, float thr_auto, float thr_review, float norm_floor, float *classification,
+                float *confidence, float *correction, int64_t *n_nodes_out);
 void graph_free(bgnn_graph *g);
 // The one way a member of a bgnn_graph gets device memory: a pool block the graph records, released by graph_free -- at build
 // time or on demand (ensure_edge_attrs, ensure_transposed_index).  Scratch of a single call is not a member: plain pool.alloc.
@@ -340,6 +353,8 @@ struct ProfScope {
 
 // ---- launchers implemented in the kernel translation units ------------------------------
 int launch_graph_build(bgnn_ctx *ctx, bgnn_graph *g, const bgnn_tiles *tiles, const bgnn_graph_opts *opts);
+// fills g->d_x16 from g->d_x8 (columns < F0) and the planes (node_aux.hip); aux: HOST array of n_aux DEVICE planes
+int launch_node_aux(bgnn_ctx *ctx, bgnn_graph *g, int F0, int n_aux, const float *const *aux);
 int launch_graph_export(bgnn_graph *g, float *x, int64_t *edge_index, float *edge_attr, float *pos,
                         int64_t *valid_rows, int64_t *valid_cols, float *local_std, int64_t *batch);
 int ensure_stencil_table(const bgnn_graph *g);

@@ -69,7 +69,8 @@ static int validate_opts(const bgnn_graph_opts *o) {
 }
 
 // the device side of a planned batch: tables, buffers, uploads, kernels (on failure the caller frees g with what it holds by then)
-static int graph_fill(bgnn_ctx *ctx, bgnn_graph *g, const GraphPlan &p, const bgnn_tiles *tiles, const bgnn_graph_opts *opts) {
+static int graph_fill(bgnn_ctx *ctx, bgnn_graph *g, const GraphPlan &p, const bgnn_tiles *tiles, const bgnn_graph_opts *opts,
+                      int32_t n_aux, const float *const *aux) {
   const int64_t cells = p.cells;
   bool upload_tables = false;
   char *blk = nullptr;                                     // ragged batch: ONE block with every host-built table
@@ -91,6 +92,7 @@ static int graph_fill(bgnn_ctx *ctx, bgnn_graph *g, const GraphPlan &p, const bg
   BGNN_TRY(graph_alloc(g, g->d_cell_of_node, cells));
   BGNN_TRY(graph_alloc(g, g->d_counts, 4));
   BGNN_TRY(graph_alloc(g, g->d_x8, cells * 8));
+  g->d_x = g->d_x8; g->ldx = 8;
   BGNN_TRY(graph_alloc(g, g->d_local_std, cells));
   BGNN_TRY(graph_alloc(g, g->d_nbr, cells * g->K));
   // every edge feature list is a selection / ordering of (distance, depth_difference, slope, zero): all of them are built compact
@@ -113,11 +115,18 @@ static int graph_fill(bgnn_ctx *ctx, bgnn_graph *g, const GraphPlan &p, const bg
     BGNN_TRY(ctx_upload(ctx, g->h_tiles.data(), sizeof(BgnnTileMeta) * g->n_tiles, g->d_tiles));
     BGNN_TRY(ctx_upload(ctx, p.items.data(), sizeof(BgnnWorkItem) * p.items.size(), g->d_items));
   }
-  return launch_graph_build(ctx, g, tiles, opts);
+  BGNN_TRY(launch_graph_build(ctx, g, tiles, opts));
+  if (n_aux > 0) {                                         // bgnn_aux.h: the wide node table, the planes behind the plain build's columns
+    const int F0 = g->F;
+    BGNN_TRY(graph_alloc(g, g->d_x16, cells * BGNN_AUX_ROW_FLOATS));
+    BGNN_TRY(launch_node_aux(ctx, g, F0, n_aux, aux));
+    g->d_x = g->d_x16; g->ldx = BGNN_AUX_ROW_FLOATS; g->F = F0 + n_aux;
+  }
+  return BGNN_OK;
 }
 
 int graph_build(bgnn_ctx *ctx, const bgnn_tiles *tiles, const bgnn_graph_opts *opts, bgnn_graph **out, int64_t *n_nodes_copy,
-                float *const *clear_grids) {
+                float *const *clear_grids, int32_t n_aux, const float *const *aux) {
   BGNN_REQUIRE(ctx && tiles && opts && out, "bgnn_graph_build: NULL argument");
   BGNN_REQUIRE(tiles->n_tiles >= 1, "bgnn_graph_build: n_tiles=%d", tiles->n_tiles);
   // (the per-grid kernels index grids by gridDim.y: 65 535 at most -- say so instead of failing the launch)
@@ -141,7 +150,7 @@ int graph_build(bgnn_ctx *ctx, const bgnn_tiles *tiles, const bgnn_graph_opts *o
   g->bh2 = p.bh2; g->bw2 = p.bw2; g->n_blocks2 = p.n_blocks2;
   g->bh3 = p.bh3; g->bw3 = p.bw3; g->n_blocks3 = p.n_blocks3;
   g->atlas_w = p.atlas_w; g->atlas_h = p.atlas_h;
-  const int rc = graph_fill(ctx, g, p, tiles, opts);
+  const int rc = graph_fill(ctx, g, p, tiles, opts, n_aux, aux);
   if (rc != BGNN_OK) { graph_free(g); return rc; }
   ctx->live_graphs.insert(g);
   *out = g;

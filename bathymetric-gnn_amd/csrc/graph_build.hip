@@ -1035,7 +1035,7 @@ __global__ __launch_bounds__(256) void tile_counts_kernel(const BgnnTileMeta *ti
 // export to the PyG layout
 // ------------------------------------------------------------------------------------------
 __global__ void export_nodes_kernel(const BgnnTileMeta *tiles, int n_tiles, const int64_t *counts,
-                                    const int32_t *cell_of_node, const float *x8, const float *lstd, int F,
+                                    const int32_t *cell_of_node, const float *xt, int ldx, const float *lstd, int F,
                                     float *x, float *pos, int64_t *rows, int64_t *cols, float *local_std,
                                     int64_t *batch) {
   int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1045,7 +1045,7 @@ __global__ void export_nodes_kernel(const BgnnTileMeta *tiles, int n_tiles, cons
   const BgnnTileMeta t = tiles[ti];
   int rel = cell - t.cell_off;
   int r = rel / t.w, c = rel % t.w;
-  if (x) for (int f = 0; f < F; ++f) x[n * F + f] = x8[n * 8 + f];
+  if (x) for (int f = 0; f < F; ++f) x[n * F + f] = xt[n * ldx + f];
   if (pos) { pos[n * 2] = (float)c; pos[n * 2 + 1] = (float)r; }   // pos = (col, row)  (:144-147)
   if (rows) rows[n] = r;
   if (cols) cols[n] = c;
@@ -1380,7 +1380,7 @@ int launch_graph_export(bgnn_graph *g, float *x, int64_t *edge_index, float *edg
   if (x || pos || valid_rows || valid_cols || local_std || batch) {
     int nb = (int)((rows + 255) / 256);
     hipLaunchKernelGGL(export_nodes_kernel, dim3(nb), dim3(256), 0, ctx->stream, g->d_tiles, g->n_tiles,
-                       g->d_counts, g->d_cell_of_node, g->d_x8, g->d_local_std, g->F, x, pos, valid_rows,
+                       g->d_counts, g->d_cell_of_node, g->d_x, g->ldx, g->d_local_std, g->F, x, pos, valid_rows,
                        valid_cols, local_std, batch);
   }
   if (edge_index || edge_attr) {
@@ -1499,6 +1499,7 @@ int launch_generic_build(bgnn_ctx *ctx, bgnn_graph *g, int64_t n_nodes, int32_t 
   const int64_t N = n_nodes, E = n_edges;
   BGNN_TRY(graph_alloc(g, g->d_counts, 4));          // (a count of 0 gives the pool's smallest block)
   BGNN_TRY(graph_alloc(g, g->d_x8, N * 8));
+  g->d_x = g->d_x8; g->ldx = 8;
   BGNN_TRY(graph_alloc(g, g->d_rowptr, N + 1));
   BGNN_TRY(graph_alloc(g, g->d_nbr, E));
   BGNN_TRY(graph_alloc(g, g->d_edge_perm, E));

@@ -302,6 +302,9 @@ struct ImageMap {
   }
 };
 
+// Rows of the first extractor image fe_W0t = the K of its GEMM: the node table's 8 columns, or the wide table's 16
+inline int extractor_rows(int in_channels) { return in_channels > 8 ? 16 : 8; }
+
 // The layout pass.  Images lie in the order of the put() calls, each rounded up to 4 floats.
 inline ImageMap image_map(const bgnn_model_desc &d) {
   const bool gat = d.gnn_type == BGNN_GNN_GAT, sage = d.gnn_type == BGNN_GNN_SAGE, gin = d.gnn_type == BGNN_GNN_GIN;
@@ -313,8 +316,8 @@ inline ImageMap image_map(const bgnn_model_desc &d) {
   m.htab_ok = m.HT <= 96 && hh == 32 && nc + nh - 1 <= 6;
   const size_t HT = m.HT, HC0 = (L > 1 ? heads : 1) * hid;
   auto put = [&](Image &im, size_t n, unsigned flags = 0) { im.off = m.total; im.floats = n; im.flags = flags; m.total += (n + 3) & ~(size_t)3; };
-  // feature extractor: W^T layouts [in, 8 rows][out]
-  put(m.fe_W0t, 8 * hid, TC); put(m.fe_b0, hid, TC); put(m.fe_W1t, hid * hid, TC); put(m.fe_b1, hid, TC);
+  // feature extractor: W^T layouts [in, 8 rows][out] (in_channels > 8: 16 rows, the wide node table of bgnn_aux.h)
+  put(m.fe_W0t, extractor_rows(d.in_channels) * hid, TC); put(m.fe_b0, hid, TC); put(m.fe_W1t, hid * hid, TC); put(m.fe_b1, hid, TC);
   m.layers.resize(L);
   for (int l = 0; l < L; ++l) {
     ImageMap::Layer &M = m.layers[l];

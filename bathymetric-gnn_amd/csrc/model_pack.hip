@@ -49,7 +49,7 @@ static int model_create_native(bgnn_ctx *ctx, const bgnn_model_desc *d, WeightLa
   //  16 and their three first layers side by side a multiple of 32; the fused kernels exist for hidden 64 only, the reference's
   //  default: config/config.py:41)
   BGNN_REQUIRE(d->hidden == 32 || d->hidden == 64 || d->hidden == 128, "hidden_channels=%d unsupported (32, 64 or 128)", d->hidden);
-  BGNN_REQUIRE(d->in_channels >= 1 && d->in_channels <= 8, "in_channels=%d unsupported (1..8)", d->in_channels);
+  BGNN_REQUIRE(d->in_channels >= 1 && d->in_channels <= 16, "in_channels=%d unsupported (1..16)", d->in_channels);
   BGNN_REQUIRE(d->num_layers >= 1 && d->num_layers <= 64, "num_gnn_layers=%d unsupported", d->num_layers);
   BGNN_REQUIRE(d->gnn_type >= BGNN_GNN_GAT && d->gnn_type <= BGNN_GNN_GIN, "gnn_type=%d unknown", d->gnn_type);
   const bool gat = d->gnn_type == BGNN_GNN_GAT;
@@ -173,7 +173,7 @@ int bgnn_model_create(bgnn_ctx *ctx, const bgnn_model_desc *d_in, const float *w
   BGNN_REQUIRE(dl.heads >= 1 && dl.heads <= 256 && pad_heads(dl.heads) * pad_hidden(dl.hidden) <= 512,
                "heads=%d x hidden_channels=%d unsupported: the layer is laid out as %d heads of %d channels (next power of two x next of "
                "32 / 64 / 128), which must stay within 512 columns", dl.heads, dl.hidden, pad_heads(dl.heads), pad_hidden(dl.hidden));
-  BGNN_REQUIRE(dl.in_channels >= 1 && dl.in_channels <= 8, "in_channels=%d unsupported (1..8)", dl.in_channels);
+  BGNN_REQUIRE(dl.in_channels >= 1 && dl.in_channels <= 16, "in_channels=%d unsupported (1..16)", dl.in_channels);
   BGNN_REQUIRE(dl.num_layers >= 1 && dl.num_layers <= 64, "num_gnn_layers=%d unsupported", dl.num_layers);
   BGNN_REQUIRE(!gat || (dl.edge_dim >= 1 && dl.edge_dim <= 4), "edge_dim=%d unsupported (1..4)", dl.edge_dim);
   BGNN_REQUIRE(dl.num_classes >= 1 && dl.num_classes <= 16, "num_classes=%d unsupported", dl.num_classes);

@@ -83,6 +83,9 @@ static int forward_train(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const bgnn
   const int hid = d.hidden;
   const int maxw = std::max(2 * hid, d.heads * hid);
   float *X = t.X, *Y = t.Y, *asdX = t.asdX;
+  // the node table: 8-column rows, or the wide table of a build with auxiliary planes (bgnn_aux.h); Kx: rows of fe_W0t
+  const float *xt = g->d_x;
+  const int ldx = g->ldx, Kx = extractor_rows(d.in_channels);
   void *bnws = nullptr;
   BGNN_TRY(ctx_workspace(ctx, 5, bn_train_workspace_bytes(maxw >= 256 ? 256 : maxw), &bnws));
   // taped forward: the saved activations are COPIES of the forward's own tables (outputs and statistics stay bit-identical)
@@ -118,7 +121,7 @@ static int forward_train(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const bgnn
   if (!gat) {
     // GCN / GraphSAGE / GIN backbones (gnn.py:120-143; torch_geometric default arguments): plain gathers + GEMMs, the layer's
     // last map unfolded (tr_bias, tr_Wt), BatchNorm afterwards
-    BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, 8, hid, 1));
+    BGNN_TRY(launch_gemm_f32(ctx, xt, ldx, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, Kx, hid, 1));
     if (dp) BGNN_TRY(drop(Y, hid, dp->p_extractor, 1));
     BGNN_TRY(launch_gemm_f32(ctx, Y, hid, m->fe_W1t, m->fe_b1, X, hid, dm, rows, hid, hid, 0));
     BGNN_TRY(save(tl.h0, Y, tab));
@@ -159,8 +162,9 @@ static int forward_train(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const bgnn
       // extractor layer 1 runs inside the lin_0 GEMM (same instructions, h1 never leaves the registers) wherever that GEMM takes
       // its W-resident form; below 32 768 rows it keeps its own launch -- the results are bit-identical either way
       // (active extractor dropout sits between the two: the first layer then keeps its own launch)
-      const bool front = hid == 64 && gemm_front_available(ctx, rows, L0.heads * hid, 0) && !(dp && dp->p_extractor > 0.0f);
-      if (!front) BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, 8, hid, 1));
+      // (... and the front form reads 8-column node rows: a graph with auxiliary planes, bgnn_aux.h, keeps the own launch too)
+      const bool front = ldx == 8 && hid == 64 && gemm_front_available(ctx, rows, L0.heads * hid, 0) && !(dp && dp->p_extractor > 0.0f);
+      if (!front) BGNN_TRY(launch_gemm_f32(ctx, xt, ldx, m->fe_W0t, m->fe_b0, Y, hid, dm, rows, Kx, hid, 1));
       if (!front && dp) BGNN_TRY(drop(Y, hid, dp->p_extractor, 1));
       if (tape) {        // the folded chain never forms h0 (front form) or h1: the tape gets them from their own launches
         float *h0 = (float *)(tape + tl.h0);
@@ -173,7 +177,7 @@ static int forward_train(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const bgnn
                                front ? m->fe_W0t : nullptr, front ? m->fe_b0 : nullptr, front ? m->l0f_Wpm : nullptr,
                                m->l0f_Wt_blk, 1.0f));
     } else {
-      BGNN_TRY(launch_gemm_f32(ctx, g->d_x8, 8, m->fe_W0t, m->fe_b0, X, hid, dm, rows, 8, hid, 1));
+      BGNN_TRY(launch_gemm_f32(ctx, xt, ldx, m->fe_W0t, m->fe_b0, X, hid, dm, rows, Kx, hid, 1));
       if (dp) BGNN_TRY(drop(X, hid, dp->p_extractor, 1));
       BGNN_TRY(launch_gemm_f32(ctx, X, hid, m->fe_W1t, m->fe_b1, Y, hid, dm, rows, hid, hid, 0));
       BGNN_TRY(save(tl.h0, X, tab));
@@ -396,7 +400,7 @@ int bgnn_backward(bgnn_ctx *ctx, bgnn_model *m, bgnn_graph *g, const void *tape,
   BGNN_TRY(launch_colsum(ctx, G0, hid, hid, nullptr, 0, 0, 1, dm, rows, gw + go.fe_b1, CS));
   BGNN_TRY(launch_gemm_f32(ctx, G0, hid, raw + go.fe_W1, nullptr, G1, hid, dm, rows, hid, hid, 0));
   BGNN_TRY(launch_relu_drop_bwd(ctx, G1, hid, T(tl.h0), hid, hid, dm, rows, s_ext));
-  BGNN_TRY(launch_wgrad(ctx, G1, hid, g->d_x8, 8, dm, rows, hid, d.in_channels, gw + go.fe_W0, d.in_channels, WG));
+  BGNN_TRY(launch_wgrad(ctx, G1, hid, g->d_x, g->ldx, dm, rows, hid, d.in_channels, gw + go.fe_W0, d.in_channels, WG));
   BGNN_TRY(launch_colsum(ctx, G1, hid, hid, nullptr, 0, 0, 1, dm, rows, gw + go.fe_b0, CS));
   return BGNN_OK;
 }

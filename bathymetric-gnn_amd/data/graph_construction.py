@@ -218,8 +218,10 @@ class GraphBuilder:
     def _ctx(self) -> rt.Context:
         return rt.get_context(self._device)
 
-    def n_node_columns(self, has_uncertainty: bool) -> int:
-        n = 0
+    def n_node_columns(self, has_uncertainty: bool, n_aux: int = 0) -> int:
+        """Columns of ``x``: the listed features, uncertainty appended when given and not listed, then ``n_aux`` auxiliary planes
+        (sounding density is one) behind them."""
+        n = int(n_aux)
         for name in self.node_features:
             if name not in rt.NODE_FEATURE_IDS:
                 continue
@@ -234,7 +236,6 @@ class GraphBuilder:
         """Host grids -> flat device tensors + tile table.  ``masks[i]`` None means
         ``np.isfinite(depth)`` (graph_construction.py:110-111).  Either every tile has an
         uncertainty grid or none has."""
-        ctx = self._ctx()
         n = len(depths)
         hw = np.empty((n, 2), np.int32)
         res = np.empty((n, 2), np.float64)
@@ -256,49 +257,78 @@ class GraphBuilder:
                 if u.shape != d.shape:
                     raise ValueError(f"uncertainty shape {u.shape} != depth shape {d.shape}")
                 ul.append(u.ravel())
-        dev = ctx.device
+        dev = self._ctx().device                             # (every host-side check comes before the device is asked for)
         depth_t = torch.from_numpy(np.concatenate(dl) if n > 1 else dl[0]).to(dev, non_blocking=False)
         mask_t = torch.from_numpy(np.concatenate(ml) if n > 1 else ml[0]).to(dev)
         unc_t = torch.from_numpy(np.concatenate(ul) if n > 1 else ul[0]).to(dev) if has_unc else None
         return hw, res, depth_t, mask_t, unc_t
 
+    def upload_density(self, densities, depths) -> List[torch.Tensor]:
+        """The sounding density grids of a batch (one per depth grid, taken as they are) as the ``aux_t`` of ``build_from_device``:
+        ``[plane]``, the grids concatenated like the depths, or ``[]`` when ``densities`` is None or holds only None.  Either every
+        grid of a batch has a density layer or none has; every check comes before the device is asked for."""
+        if densities is None or not any(a is not None for a in densities):
+            return []
+        if len(densities) != len(depths):
+            raise ValueError(f"{len(densities)} density grids for {len(depths)} depth grids")
+        al = []
+        for a, d in zip(densities, depths):
+            if a is None:
+                raise ValueError("either every grid of a batch has a sounding density layer or none has")
+            a = _as_f32(a, "density")
+            if a.shape != np.shape(d):
+                raise ValueError(f"density shape {a.shape} != depth shape {np.shape(d)}")
+            al.append(a.ravel())
+        return [torch.from_numpy(np.concatenate(al) if len(al) > 1 else al[0]).to(self._ctx().device)]
+
     def build_from_device(self, hw: np.ndarray, res: np.ndarray, depth_t: torch.Tensor, mask_t: torch.Tensor,
-                          unc_t: Optional[torch.Tensor], ctx: Optional[rt.Context] = None) -> GraphData:
+                          unc_t: Optional[torch.Tensor], ctx: Optional[rt.Context] = None,
+                          aux_t: Optional[Sequence[torch.Tensor]] = None) -> GraphData:
         """Batch entry on device-resident tiles (flat, concatenated row-major).  ``ctx``: build on this library context
-        (``rt.new_context``) instead of the device's default one; the graph lives and dies with it."""
+        (``rt.new_context``) instead of the device's default one; the graph lives and dies with it.  ``aux_t``: flat float32 device
+        planes laid out like ``depth_t``, appended as they are as node-feature columns behind the plain build's
+        (``bgnn_graph_build_aux``); sounding density is the one-plane case."""
         ctx = ctx if ctx is not None else self._ctx()
         cells = int((hw[:, 0].astype(np.int64) * hw[:, 1]).sum())
         if depth_t.numel() != cells or mask_t.numel() != cells or (unc_t is not None and unc_t.numel() != cells):
             raise ValueError("tile table and device buffers disagree on the number of cells")
         assert depth_t.dtype == torch.float32 and mask_t.dtype in (torch.uint8, torch.bool)
         tiles, keep = rt.make_tiles(hw, res, depth_t, mask_t, unc_t)
+        n_aux, aux, _keep_aux = rt.make_aux_planes(aux_t, cells)
         h = C.c_void_p()
         ctx.begin()
-        rt.check(ctx.lib.bgnn_graph_build(ctx.handle, C.byref(tiles), C.byref(self._opts), C.byref(h)))
+        if n_aux:
+            rt.check(ctx.lib.bgnn_graph_build_aux(ctx.handle, C.byref(tiles), C.byref(self._opts), n_aux, aux, C.byref(h)))
+        else:
+            rt.check(ctx.lib.bgnn_graph_build(ctx.handle, C.byref(tiles), C.byref(self._opts), C.byref(h)))
         ctx.end()
-        g = GraphData(ctx, h, keep[0], self.n_node_columns(unc_t is not None), len(self.edge_features))
+        g = GraphData(ctx, h, keep[0], self.n_node_columns(unc_t is not None, n_aux), len(self.edge_features))
         return g
 
     # ---- reference API ---------------------------------------------------------------------
     def build_graph(self, depth: np.ndarray, valid_mask: Optional[np.ndarray] = None,
                     uncertainty: Optional[np.ndarray] = None,
-                    resolution: Tuple[float, float] = (1.0, 1.0)):
-        """Build a graph from one grid (reference ``build_graph``, :91-174)."""
+                    resolution: Tuple[float, float] = (1.0, 1.0), density: Optional[np.ndarray] = None):
+        """Build a graph from one grid (reference ``build_graph``, :91-174).  ``density``: per-cell sounding density
+        (``SoundingGrid.density_plane``), one more node-feature column behind the others."""
+        a = self.upload_density([density], [depth])
         hw, res, d, m, u = self.upload_tiles([depth], [valid_mask], [uncertainty], [resolution])
-        g = self.build_from_device(hw, res, d, m, u)
+        g = self.build_from_device(hw, res, d, m, u, aux_t=a)
         if g.num_nodes == 0:
             logger.warning("No valid cells in grid")
             return self._create_empty_graph()
         return g
 
-    def build_graphs(self, depths, valid_masks=None, uncertainties=None, resolutions=None) -> GraphData:
+    def build_graphs(self, depths, valid_masks=None, uncertainties=None, resolutions=None, densities=None) -> GraphData:
         """Batch of grids -> one block-diagonal graph (what ``Batch.from_data_list`` of the
-        per-grid graphs would hold, scripts/inference_native.py:312)."""
+        per-grid graphs would hold, scripts/inference_native.py:312).  ``densities``: one sounding density grid per depth grid
+        (all or none)."""
         n = len(depths)
         if resolutions is None:
             resolutions = [(1.0, 1.0)] * n
+        a = self.upload_density(densities, depths)
         hw, res, d, m, u = self.upload_tiles(depths, valid_masks, uncertainties, resolutions)
-        return self.build_from_device(hw, res, d, m, u)
+        return self.build_from_device(hw, res, d, m, u, aux_t=a)
 
     def _create_empty_graph(self) -> Data:           # :460-469 (note: no grid_shape attribute)
         return Data(x=torch.zeros((0, len(self.node_features)), dtype=torch.float32),

@@ -20,6 +20,9 @@ class BathymetricGrid:
     resolution: Tuple[float, float] = (1.0, 1.0)
     bounds: Any = None
     source_path: Optional[Path] = None
+    # per-cell sounding density (SoundingGrid.density_plane: 1 / count, 0 where no sounding fell): the extra node plane of a model
+    # trained with "sounding_density" among its node_planes; None for a grid that does not come from a point cloud
+    density: Optional[np.ndarray] = None
 
     @property
     def shape(self) -> Tuple[int, int]:

@@ -139,6 +139,15 @@ def plan_sounding_grid(x, y, resolution) -> Tuple[Tuple[int, int], Tuple[float, 
     return (int(height), int(width)), (float(x0), float(y0))
 
 
+def density_from_count(count: torch.Tensor) -> torch.Tensor:
+    """The sounding density plane of a per-cell count: float32 ``1 / count`` where ``count >= 1``, ``0`` elsewhere -- one correctly
+    rounded float32 division per cell, on the device the count lives on.  Bounded in (0, 1] and largest on single-hit cells, the
+    cells the reference's dashboard calls "almost certainly noise"."""
+    c = count.to(torch.float32)
+    hit = count >= 1
+    return torch.where(hit, torch.ones_like(c) / torch.where(hit, c, torch.ones_like(c)), torch.zeros_like(c))
+
+
 @dataclasses.dataclass
 class SoundingGrid:
     """What ``SoundingGridder.finalize`` leaves on the device: ``[H, W]`` tensors ``count`` (int32, the true count also where the
@@ -161,19 +170,26 @@ class SoundingGrid:
             raise ValueError(f"depth={depth!r}: one of {DEPTH_PLANES} expected")
         return getattr(self, depth)
 
-    def survey_tensors(self, depth: str = "mean"):
+    def density_plane(self) -> torch.Tensor:
+        """``density_from_count(count)``: the node plane "sounding_density"."""
+        return density_from_count(self.count)
+
+    def survey_tensors(self, depth: str = "mean", density: bool = False):
         """``(depth_t, valid_t, unc_t)`` as ``BathymetricPipeline.process_survey_device`` takes them: the chosen surface
-        (``"mean"``, the shoalest ``"min"`` or the deepest ``"max"`` of the raw z), the valid plane and ``std`` as uncertainty."""
+        (``"mean"``, the shoalest ``"min"`` or the deepest ``"max"`` of the raw z), the valid plane and ``std`` as uncertainty.
+        ``density=True``: ``density_plane()`` as a fourth element (``process_survey_device(..., density_t=...)``)."""
+        if density:
+            return self._depth(depth), self.valid, self.std, self.density_plane()
         return self._depth(depth), self.valid, self.std
 
     def to_grid(self, depth: str = "mean") -> BathymetricGrid:
-        """A host ``BathymetricGrid``: the chosen surface, ``std`` as uncertainty, the nodata value, transform, resolution and
-        bounds ``(min_x, min_y, max_x, max_y)``."""
+        """A host ``BathymetricGrid``: the chosen surface, ``std`` as uncertainty, ``density_plane()`` as density, the nodata
+        value, transform, resolution and bounds ``(min_x, min_y, max_x, max_y)``."""
         height, width = (int(v) for v in self.count.shape)
         x0, res, _, y0, _, _ = self.transform
         return BathymetricGrid(depth=self._depth(depth).cpu().numpy(), uncertainty=self.std.cpu().numpy(),
                                nodata_value=self.nodata_value, transform=self.transform, resolution=self.resolution,
-                               bounds=(x0, y0 - height * res, x0 + width * res, y0))
+                               bounds=(x0, y0 - height * res, x0 + width * res, y0), density=self.density_plane().cpu().numpy())
 
 
 class SoundingGridder:

@@ -26,7 +26,7 @@ import torch
 
 from .. import runtime as rt
 from .grid import BathymetricGrid
-from .sounding_grid import _check_coordinates, _check_resolution, _feed, _on_device, plan_sounding_grid
+from .sounding_grid import _check_coordinates, _check_resolution, _feed, _on_device, density_from_count, plan_sounding_grid
 
 DEFAULT_K = 3 * 1.4826
 ROBUST_DEPTH_PLANES = ("median", "kept_mean", "kept_min", "kept_max")
@@ -77,10 +77,16 @@ class RobustSoundingGrid:
             raise ValueError(f"{what}={name!r}: one of {allowed} expected")
         return getattr(self, name)
 
-    def survey_tensors(self, depth: str = "median", uncertainty: str = "kept_std"):
-        """``(depth_t, valid_t, unc_t)`` as ``BathymetricPipeline.process_survey_device`` takes them."""
-        return (self._plane(depth, ROBUST_DEPTH_PLANES, "depth"), self.valid,
-                self._plane(uncertainty, ROBUST_UNCERTAINTY_PLANES, "uncertainty"))
+    def density_plane(self) -> torch.Tensor:
+        """``density_from_count(kept)``: the node plane "sounding_density" over the soundings the rule kept."""
+        return density_from_count(self.kept)
+
+    def survey_tensors(self, depth: str = "median", uncertainty: str = "kept_std", density: bool = False):
+        """``(depth_t, valid_t, unc_t)`` as ``BathymetricPipeline.process_survey_device`` takes them; ``density=True``:
+        ``density_plane()`` as a fourth element."""
+        t = (self._plane(depth, ROBUST_DEPTH_PLANES, "depth"), self.valid,
+             self._plane(uncertainty, ROBUST_UNCERTAINTY_PLANES, "uncertainty"))
+        return t + (self.density_plane(),) if density else t
 
     def to_grid(self, depth: str = "median", uncertainty: str = "kept_std") -> BathymetricGrid:
         """A host ``BathymetricGrid`` of the chosen surface and uncertainty, as ``SoundingGrid.to_grid``."""
@@ -89,7 +95,7 @@ class RobustSoundingGrid:
         depth_t, _, unc_t = self.survey_tensors(depth, uncertainty)
         return BathymetricGrid(depth=depth_t.cpu().numpy(), uncertainty=unc_t.cpu().numpy(), nodata_value=self.nodata_value,
                                transform=self.transform, resolution=self.resolution,
-                               bounds=(x0, y0 - height * res, x0 + width * res, y0))
+                               bounds=(x0, y0 - height * res, x0 + width * res, y0), density=self.density_plane().cpu().numpy())
 
 
 class RobustSoundingGridder:

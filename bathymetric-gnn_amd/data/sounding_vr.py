@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from .. import runtime as rt
-from .sounding_grid import DEPTH_PLANES, MAX_TOTAL, _check_coordinates, _check_resolution, _feed, _on_device, sounding_extent
+from .sounding_grid import (DEPTH_PLANES, MAX_TOTAL, _check_coordinates, _check_resolution, _feed, _on_device, density_from_count,
+                            sounding_extent)
 from .sounding_robust import DEFAULT_K, ROBUST_DEPTH_PLANES, ROBUST_UNCERTAINTY_PLANES
 from .vr_bag import VARRES_METADATA_DTYPE, VARRES_REFINEMENT_DTYPE, VRBagHandler
 
@@ -300,6 +301,10 @@ class VRSoundingGrid(_VRPlanes):
     nodata_value: float = 1.0e6
     min_count: int = 1
 
+    def density_plane(self) -> torch.Tensor:
+        """``density_from_count(count)``, one entry per record of ``layout``."""
+        return density_from_count(self.count)
+
     def records(self, depth: str = "mean", uncertainty: str = "std") -> torch.Tensor:
         """The ``[total, 2]`` float32 device tensor of (depth, depth_uncrt) records, 1.0e6 in both where the record is not valid."""
         return self._records(_pick(self, depth, DEPTH_PLANES, "depth"), _pick(self, uncertainty, UNCERTAINTY_PLANES, "uncertainty"))
@@ -333,6 +338,10 @@ class RobustVRSoundingGrid(_VRPlanes):
     min_count: int = 1
     k: float = DEFAULT_K
     floor_m: float = 0.0
+
+    def density_plane(self) -> torch.Tensor:
+        """``density_from_count(kept)``, one entry per record of ``layout``."""
+        return density_from_count(self.kept)
 
     def records(self, depth: str = "median", uncertainty: str = "kept_std") -> torch.Tensor:
         """The ``[total, 2]`` float32 device tensor of (depth, depth_uncrt) records, 1.0e6 in both where the record is not valid."""

@@ -188,13 +188,27 @@ def exchange_halo_tile_rows(plan, rank: int, local_rows: Dict[int, torch.Tensor]
     return recv
 
 
+def check_node_planes(node_planes) -> Optional[Tuple[str, ...]]:
+    """``node_planes`` of a checkpoint as a tuple: a sublist of ``rt.NODE_PLANES`` in that order (the column order), or None."""
+    if node_planes is None:
+        return None
+    planes = tuple(str(p) for p in node_planes)
+    if planes != tuple(p for p in rt.NODE_PLANES if p in planes) or len(set(planes)) != len(planes):
+        raise ValueError(f"node_planes={list(planes)!r}: a sublist of {list(rt.NODE_PLANES)} in that order expected")
+    return planes
+
+
 class TileBatchEngine:
     """Fused per-batch inference on one GPU (one engine per worker / device)."""
 
     def __init__(self, model: BathymetricGNN, graph_builder: GraphBuilder, device=None,
                  auto_correct_threshold: float = 0.85, review_threshold: float = 0.6,
-                 norm_floor: float = CORRECTION_NORM_FLOOR, ctx: Optional[rt.Context] = None):
+                 norm_floor: float = CORRECTION_NORM_FLOOR, ctx: Optional[rt.Context] = None,
+                 node_planes: Optional[Sequence[str]] = None):
         self.model = model
+        # the planes the model takes beside the computed node features (a sublist of rt.NODE_PLANES, from the checkpoint's
+        # "node_planes"); None: not stated -- uncertainty is taken when the model's width asks for it, density when it is given
+        self.node_planes = check_node_planes(node_planes)
         self.graph_builder = graph_builder
         # ``ctx``: an extra library context (``rt.new_context``) -- engines on different contexts overlap their batches
         self.ctx = ctx if ctx is not None else rt.get_context(device if device is not None else graph_builder._device)
@@ -204,13 +218,15 @@ class TileBatchEngine:
 
     def infer_device(self, hw: np.ndarray, res: np.ndarray, depth_t: torch.Tensor, mask_t: torch.Tensor,
                      unc_t: Optional[torch.Tensor], out=None,
-                     n_nodes_out: Optional[torch.Tensor] = None, defer_end: bool = False, begin: bool = True):
+                     n_nodes_out: Optional[torch.Tensor] = None, defer_end: bool = False, begin: bool = True,
+                     density_t: Optional[torch.Tensor] = None):
         """Device-resident tiles in, device-resident grids out: returns float32 [3, cells]
         (classification, confidence, correction), same cell layout as ``depth_t``.  Asynchronous
         with respect to the host.  ``defer_end``: do not order the caller's torch stream behind this batch yet (the
         caller calls ``engine.ctx.end()`` before it reads ``out``): batches given to engines on different contexts
         then run concurrently.  ``begin=False``: do not order this batch behind the caller's current torch stream either (the
-        inputs were produced on the engine's own stream, or behind an event it already waits for)."""
+        inputs were produced on the engine's own stream, or behind an event it already waits for).  ``density_t``: the tiles' sounding
+        density, laid out like ``depth_t``: one more node-feature column behind the others (``bgnn_infer_tiles_aux``)."""
         ctx = self.ctx
         cells = depth_t.numel()
         if out is None:
@@ -219,25 +235,46 @@ class TileBatchEngine:
         assert all(o.is_contiguous() and o.numel() == cells for o in (out[0], out[1], out[2]))
         tiles, keep = rt.make_tiles(hw, res, depth_t, mask_t, unc_t)
         model_h = self.model.native(ctx, int(self.graph_builder._opts.n_edge_features))
+        n_aux, aux, _keep_aux = rt.make_aux_planes([density_t] if density_t is not None else None, cells)
         if begin:
             ctx.begin()
-        rt.check(ctx.lib.bgnn_infer_tiles(
-            ctx.handle, model_h, C.byref(tiles), C.byref(self.graph_builder._opts),
-            C.c_float(self.auto_correct_threshold), C.c_float(self.review_threshold), C.c_float(self.norm_floor),
-            rt.ptr(out[0]), rt.ptr(out[1]), rt.ptr(out[2]), rt.ptr(n_nodes_out)))
+        if n_aux:
+            rt.check(ctx.lib.bgnn_infer_tiles_aux(
+                ctx.handle, model_h, C.byref(tiles), C.byref(self.graph_builder._opts), n_aux, aux,
+                C.c_float(self.auto_correct_threshold), C.c_float(self.review_threshold), C.c_float(self.norm_floor),
+                rt.ptr(out[0]), rt.ptr(out[1]), rt.ptr(out[2]), rt.ptr(n_nodes_out)))
+        else:
+            rt.check(ctx.lib.bgnn_infer_tiles(
+                ctx.handle, model_h, C.byref(tiles), C.byref(self.graph_builder._opts),
+                C.c_float(self.auto_correct_threshold), C.c_float(self.review_threshold), C.c_float(self.norm_floor),
+                rt.ptr(out[0]), rt.ptr(out[1]), rt.ptr(out[2]), rt.ptr(n_nodes_out)))
         if not defer_end:
             ctx.end()
         return out
 
     def infer(self, depths: Sequence[np.ndarray], masks: Sequence[Optional[np.ndarray]],
-              uncs: Optional[Sequence[Optional[np.ndarray]]], resolutions) -> List[Dict[str, np.ndarray]]:
-        """Host grids in, per-tile dicts of host grids out."""
+              uncs: Optional[Sequence[Optional[np.ndarray]]], resolutions,
+              densities: Optional[Sequence[Optional[np.ndarray]]] = None) -> List[Dict[str, np.ndarray]]:
+        """Host grids in, per-tile dicts of host grids out.  ``densities``: the tiles' sounding density (all or none)."""
         if len(depths) == 0:
             return []
-        use_unc = uncs if (uncs is not None and self.model.in_channels == self.graph_builder.n_node_columns(True)
-                           and any(u is not None for u in uncs)) else None
+        have_unc = uncs is not None and any(u is not None for u in uncs)
+        have_den = densities is not None and any(a is not None for a in densities)
+        if self.node_planes is not None:                 # stated by the checkpoint: exactly those planes, each of them required
+            for name, have in (("uncertainty", have_unc), ("sounding_density", have_den)):
+                if name in self.node_planes and not have:
+                    raise ValueError(f"the model takes the node plane {name!r} and the tiles carry none")
+            use_unc = uncs if "uncertainty" in self.node_planes else None
+            use_den = densities if "sounding_density" in self.node_planes else None
+        else:
+            # not stated.  Uncertainty as before: taken when the model is as wide as the builder's columns with it.  Density only
+            # where the width asks for a column beyond those (a model as wide as 7 + uncertainty never reads density in its place)
+            cols, width = self.graph_builder.n_node_columns, self.model.in_channels
+            use_unc = uncs if have_unc and width in (cols(True), cols(True, 1)) else None
+            use_den = densities if have_den and width != cols(True) and width == cols(use_unc is not None, 1) else None
+        a = self.graph_builder.upload_density(use_den, depths)
         hw, res, d, m, u = self.graph_builder.upload_tiles(depths, masks, use_unc, resolutions)
-        out = self.infer_device(hw, res, d, m, u).cpu().numpy()
+        out = self.infer_device(hw, res, d, m, u, density_t=a[0] if a else None).cpu().numpy()
         results, off = [], 0
         for i in range(hw.shape[0]):
             h, w = int(hw[i, 0]), int(hw[i, 1])
@@ -343,6 +380,7 @@ class BathymetricPipeline:
         self.graph_builder = GraphBuilder(connectivity=config.graph.connectivity,
                                           edge_features=config.graph.edge_features)
         self.model: Optional[BathymetricGNN] = None
+        self.node_planes: Optional[Tuple[str, ...]] = None
         self._engine: Optional[TileBatchEngine] = None
         self.host_stitch = False      # True: numpy TileMerger on the host even on one GPU (the multi-rank path)
         if config.device != "cuda" or not torch.cuda.is_available():
@@ -352,11 +390,21 @@ class BathymetricPipeline:
         logger.info(f"Pipeline initialized, device: {self.device}")
 
     # ---- model -----------------------------------------------------------------------------
-    def set_model(self, model: BathymetricGNN):
+    def set_model(self, model: BathymetricGNN, node_planes: Optional[Sequence[str]] = None):
+        """``node_planes``: the planes the model takes beside the computed node features, as its checkpoint states them
+        (``"node_planes"``: a sublist of ``["uncertainty", "sounding_density"]``).  The pipeline then passes exactly those; a grid
+        that lacks one raises ``ValueError``.  None: not stated -- a model of 8 input channels takes uncertainty, as before."""
+        self.node_planes = check_node_planes(node_planes)
+        if self.node_planes is not None:
+            want = self.graph_builder.n_node_columns("uncertainty" in self.node_planes, int("sounding_density" in self.node_planes))
+            if want != model.in_channels:
+                raise ValueError(f"node_planes={list(self.node_planes)} give {want} node columns, the model has in_channels="
+                                 f"{model.in_channels}")
         self.model = model.to(self.device).eval()
+        self.model.node_planes = self.node_planes        # (travels with the model: NativeVRProcessor reads it)
         self._engine = TileBatchEngine(self.model, self.graph_builder, self.device,
                                        self.config.inference.auto_correct_threshold,
-                                       self.config.inference.review_threshold)
+                                       self.config.inference.review_threshold, node_planes=self.node_planes)
 
     def load_model(self, model_path: Union[str, Path], trust_pickle: bool = False):
         """Checkpoint -> model (reference :92-132).  Accepts the trainer's dict
@@ -392,7 +440,11 @@ class BathymetricPipeline:
             num_classes=get("num_classes", 3), predict_correction=get("predict_correction", True), dropout=0.0,
             edge_dim=ckpt.get("edge_dim", 3))
         model.load_state_dict(sd)
-        self.set_model(model)
+        planes = ckpt.get("node_planes", None)
+        if planes is None:
+            self.set_model(model)                      # (no key: the in_channels == 8 rule, as before)
+        else:
+            self.set_model(model, node_planes=planes)
         logger.info(f"Model loaded from {model_path}")
 
     # ---- per tile ----------------------------------------------------------------------------
@@ -400,13 +452,42 @@ class BathymetricPipeline:
         # The reference passes tile.uncertainty unconditionally (:253), which makes x 8 columns wide
         # and fails for a 7-channel model; like NativeVRProcessor we drop the band when the model
         # does not take it.
-        return tile.uncertainty if self.model.in_channels == 8 else None
+        return tile.uncertainty if self._takes_uncertainty() else None
+
+    # ---- which planes the model takes: stated by the checkpoint ("node_planes"), else the in_channels == 8 rule ----
+    def _takes_uncertainty(self) -> bool:
+        planes = getattr(self, "node_planes", None)
+        return "uncertainty" in planes if planes is not None else self.model.in_channels == 8
+
+    def _takes_density(self) -> bool:
+        planes = getattr(self, "node_planes", None)
+        return planes is not None and "sounding_density" in planes
+
+    def _grid_planes(self, grid):
+        """(uncertainty, density) of ``grid`` as the model takes them (None: not taken).  With stated ``node_planes`` a plane the
+        grid lacks is a ``ValueError`` that names it."""
+        unc = getattr(grid, "uncertainty", None)
+        den = getattr(grid, "density", None)
+        if getattr(self, "node_planes", None) is not None:
+            for name, plane in (("uncertainty", unc), ("sounding_density", den)):
+                if name in self.node_planes and plane is None:
+                    raise ValueError(f"the model takes the node plane {name!r} and the grid has none")
+        return (unc if self._takes_uncertainty() else None), (den if self._takes_density() else None)
+
+    def _refuse_density(self, route: str):
+        if self.model is not None and self._takes_density():
+            raise NotImplementedError(f"{route} does not carry the sounding density plane yet: a model whose node_planes hold "
+                                      "'sounding_density' runs through process_grid / process_survey_device on one GPU")
 
     def _process_tiles(self, tiles, grid: BathymetricGrid) -> List[Dict[str, np.ndarray]]:
         if self.model is None:
             raise RuntimeError("Model not loaded. Call load_model() first.")
+        dens = None
+        if self._takes_density():
+            _, den = self._grid_planes(grid)
+            dens = [den[t.row_start:t.row_end, t.col_start:t.col_end] for t in tiles]
         res = self._engine.infer([t.data for t in tiles], [t.valid_mask for t in tiles],
-                                 [self._tile_uncertainty(t) for t in tiles], [grid.resolution] * len(tiles))
+                                 [self._tile_uncertainty(t) for t in tiles], [grid.resolution] * len(tiles), dens)
         for r, t in zip(res, tiles):
             r["cleaned_depth"] = t.data       # original; corrections are applied after stitching (:310)
         return res
@@ -418,7 +499,8 @@ class BathymetricPipeline:
     # ---- whole grid ----------------------------------------------------------------------------
     def process_survey_device(self, depth_t: torch.Tensor, valid_t: torch.Tensor, unc_t: Optional[torch.Tensor],
                               resolution, shard: Optional[Tuple[int, int]] = None,
-                              survey_shape: Optional[Tuple[int, int]] = None, row_offset: int = 0):
+                              survey_shape: Optional[Tuple[int, int]] = None, row_offset: int = 0,
+                              density_t: Optional[torch.Tensor] = None):
         """Survey resident in HBM in, ``[4, H, W]`` float32 device tensor out (classification, confidence,
         correction, cleaned depth): tiles are cut (``bgnn_cut_tiles``), filtered by ``min_valid_ratio``
         (``bgnn_tile_valid_counts``), classified batch by batch into three long per-tile result arrays and
@@ -434,9 +516,19 @@ class BathymetricPipeline:
 
         A rank does not need the whole survey: with ``survey_shape=(H, W)`` and ``row_offset``, ``depth_t`` / ``valid_t`` /
         ``unc_t`` hold only the survey rows ``[row_offset, row_offset + depth_t.shape[0])`` -- what the rank's own tile rows
-        span (``survey_rows_of_rank``)."""
+        span (``survey_rows_of_rank``).
+
+        ``density_t``: the survey's sounding density plane (``SoundingGrid.density_plane``), float32 of ``depth_t``'s shape, for
+        a model that takes it: its tile windows are cut like the others and go in as one more node-feature column.  One GPU only."""
         if self.model is None:
             raise RuntimeError("Model not loaded. Call load_model() first.")
+        if density_t is not None:
+            if shard is not None and shard[1] > 1:
+                raise NotImplementedError("the sharded survey path does not carry the sounding density plane yet")
+            if density_t.dtype != torch.float32 or not density_t.is_contiguous() or density_t.shape != depth_t.shape:
+                raise ValueError("density_t: a contiguous float32 plane of depth_t's shape expected")
+        elif self._takes_density():
+            raise ValueError("the model takes the node plane 'sounding_density' and density_t is None")
         eng, ctx, dev = self._engine, self._engine.ctx, self._engine.ctx.device
         tm = self.tile_manager
         LH, W = (int(v) for v in depth_t.shape)              # rows held locally
@@ -485,6 +577,7 @@ class BathymetricPipeline:
             d_b = torch.empty(nbmax * cells, dtype=torch.float32, device=dev)
             m_b = torch.empty(nbmax * cells, dtype=torch.uint8, device=dev)
             u_b = torch.empty(nbmax * cells, dtype=torch.float32, device=dev) if unc_t is not None else None
+            a_b = torch.empty(nbmax * cells, dtype=torch.float32, device=dev) if density_t is not None else None
             proc_t = torch.from_numpy(proc).to(dev)
             for b0 in range(0, n_proc, self.tile_batch):
                 nb = min(self.tile_batch, n_proc - b0)
@@ -492,11 +585,15 @@ class BathymetricPipeline:
                 ctx.begin()
                 rt.check(ctx.lib.bgnn_cut_tiles(ctx.handle, LH, W, rt.ptr(depth_t), rt.ptr(valid_u8), rt.ptr(unc_t), nb, rt.ptr(o_b),
                                                 th, tw, rt.ptr(d_b), rt.ptr(m_b), rt.ptr(u_b)))
+                if a_b is not None:      # the density windows: a second cut with the plane in the uncertainty slot (d_b, m_b: same values again)
+                    rt.check(ctx.lib.bgnn_cut_tiles(ctx.handle, LH, W, rt.ptr(depth_t), rt.ptr(valid_u8), rt.ptr(density_t), nb,
+                                                    rt.ptr(o_b), th, tw, rt.ptr(d_b), rt.ptr(m_b), rt.ptr(a_b)))
                 ctx.end()
                 lo, hi, n = b0 * cells, (b0 + nb) * cells, nb * cells
                 eng.infer_device(np.tile(np.array([[th, tw]], np.int32), (nb, 1)), np.tile(resol, (nb, 1)), d_b[:n], m_b[:n],
-                                 u_b[:n] if u_b is not None else None, out=(r_cls[lo:hi], r_conf[lo:hi], r_corr[lo:hi]))
-            del d_b, m_b, u_b
+                                 u_b[:n] if u_b is not None else None, out=(r_cls[lo:hi], r_conf[lo:hi], r_corr[lo:hi]),
+                                 density_t=a_b[:n] if a_b is not None else None)
+            del d_b, m_b, u_b, a_b
         # ---- tile offsets of my own tiles, by (tile row, tile col) ----
         off_own = np.full(len(own), -1, np.int64)
         off_own[proc] = np.arange(n_proc, dtype=np.int64) * cells
@@ -588,6 +685,7 @@ class BathymetricPipeline:
         import threading
         if self.model is None:
             raise RuntimeError("Model not loaded. Call load_model() first.")
+        self._refuse_density("process_grid_streamed")
         eng, ctx, dev = self._engine, self._engine.ctx, self._engine.ctx.device
         tm = self.tile_manager
         H, W = (int(v) for v in grid.shape)
@@ -595,7 +693,7 @@ class BathymetricPipeline:
         plain_mask = type(grid) is BathymetricGrid
         valid_h = None if plain_mask else np.ascontiguousarray(grid.valid_mask).view(np.uint8)
         nodata = grid.nodata_value if plain_mask else None
-        use_unc = self.model.in_channels == 8 and grid.uncertainty is not None
+        use_unc = self._grid_planes(grid)[0] is not None
         unc_h = np.ascontiguousarray(grid.uncertainty, dtype=np.float32) if use_unc else None
         ntr, ntc, specs = tm.compute_tile_grid((H, W))
         sa = np.array([[s.row_start, s.col_start, s.row_end, s.col_end] for s in specs], np.int64)
@@ -828,18 +926,21 @@ class BathymetricPipeline:
             raise RuntimeError("Model not loaded. Call load_model() first.")
         dev = self._engine.ctx.device
         valid_np = grid.valid_mask
-        use_unc = self.model.in_channels == 8 and grid.uncertainty is not None
+        unc_np, den_np = self._grid_planes(grid)
+        use_unc = unc_np is not None
         up = lambda a, lo, hi, dt: torch.from_numpy(np.ascontiguousarray(a[lo:hi], dtype=dt)).to(dev)
         rank, world = shard_info()
         H, W = (int(v) for v in grid.shape)
-        if world == 1 and H * W >= self.STREAM_MIN_CELLS:
+        if world == 1 and H * W >= self.STREAM_MIN_CELLS and den_np is None:
             return self.process_grid_streamed(grid)
         if world == 1:
             depth_t = up(grid.depth, 0, H, np.float32)
             valid_t = torch.from_numpy(np.ascontiguousarray(valid_np).view(np.uint8)).to(dev)
             unc_t = up(grid.uncertainty, 0, H, np.float32) if use_unc else None
-            host = self.process_survey_device(depth_t, valid_t, unc_t, grid.resolution).cpu().numpy()
+            den_t = up(den_np, 0, H, np.float32) if den_np is not None else None
+            host = self.process_survey_device(depth_t, valid_t, unc_t, grid.resolution, density_t=den_t).cpu().numpy()
         else:               # row bands: each rank holds and stitches its own rows; the bands are gathered once at the end
+            self._refuse_density("the sharded survey path")
             (lo, hi), plan = self.survey_rows_of_rank((H, W), rank, world)
             band = None
             if hi > lo:

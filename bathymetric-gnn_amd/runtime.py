@@ -450,6 +450,19 @@ VR_MAX_TARGET = 2 ** 31 - 1                        # BGNN_VR_MAX_TARGET
 VR_PLAN_TILE = 256                                 # BGNN_VR_PLAN_TILE
 VR_SOUNDINGS_COUNTERS = SOUNDINGS_COUNTERS + ("unrefined",)
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_aux.h declares (auxiliary node-feature planes: sounding density)
+_AUX_SIGNATURES = {
+    "bgnn_graph_build_aux": (C.c_int, [C.c_void_p, C.POINTER(Tiles), C.POINTER(GraphOpts), C.c_int32, C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p)]),
+    "bgnn_infer_tiles_aux": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Tiles), C.POINTER(GraphOpts), C.c_int32,
+                                       C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+}
+AUX_MAX_PLANES = 8                                 # BGNN_AUX_MAX_PLANES
+AUX_ROW_FLOATS = 16                                # BGNN_AUX_ROW_FLOATS
+# the planes a model may take beside the computed node features, in column order (checkpoints: "node_planes")
+NODE_PLANES = ("uncertainty", "sounding_density")
+
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -463,8 +476,8 @@ def load_library(path: Optional[str] = None):
     """dlopen the HIP library and bind every symbol of include/bgnn.h, include/bgnn_train.h, include/bgnn_sidecar.h,
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
     include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h, include/bgnn_vrtruth.h,
-    include/bgnn_augment.h, include/bgnn_curve.h, include/bgnn_soundings.h, include/bgnn_soundings_robust.h and
-    include/bgnn_soundings_vr.h.  Needs no GPU."""
+    include/bgnn_augment.h, include/bgnn_curve.h, include/bgnn_soundings.h, include/bgnn_soundings_robust.h,
+    include/bgnn_soundings_vr.h and include/bgnn_aux.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -480,7 +493,8 @@ def load_library(path: Optional[str] = None):
                 list(_EVAL_SIGNATURES.items()) + list(_ANALYSIS_SIGNATURES.items()) + list(_FEATURES_SIGNATURES.items()) + \
                 list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()) + \
                 list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()) + list(_CURVE_SIGNATURES.items()) + \
-                list(_SOUNDINGS_SIGNATURES.items()) + list(_ROBUST_SIGNATURES.items()) + list(_VR_SOUNDINGS_SIGNATURES.items()):
+                list(_SOUNDINGS_SIGNATURES.items()) + list(_ROBUST_SIGNATURES.items()) + list(_VR_SOUNDINGS_SIGNATURES.items()) + \
+                list(_AUX_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
@@ -684,3 +698,24 @@ def make_tiles(hw: np.ndarray, res: np.ndarray, depth: torch.Tensor, mask: torch
     t.mask = mask.data_ptr()
     t.uncertainty = unc.data_ptr() if unc is not None else None
     return t, (hw, res, depth, mask, unc)
+
+
+def make_aux_planes(planes, cells: Optional[int] = None):
+    """The HOST pointer array of ``bgnn_graph_build_aux`` / ``bgnn_infer_tiles_aux`` from a sequence of flat float32 device planes.
+    Returns (n_aux, array or None, keepalive)."""
+    planes = [] if planes is None else list(planes)
+    if len(planes) > AUX_MAX_PLANES:
+        raise ValueError(f"at most {AUX_MAX_PLANES} auxiliary node planes, got {len(planes)}")
+    keep = []
+    for i, t in enumerate(planes):
+        if t is None:
+            raise ValueError(f"auxiliary node plane {i} is None")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"auxiliary node plane {i} must be a contiguous float32 tensor")
+        if cells is not None and t.numel() != cells:
+            raise ValueError(f"auxiliary node plane {i} has {t.numel()} cells, the tile table has {cells}")
+        keep.append(t)
+    if not keep:
+        return 0, None, keep
+    arr = (C.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+    return len(keep), arr, (keep, arr)

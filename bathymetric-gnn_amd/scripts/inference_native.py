@@ -132,14 +132,27 @@ class _BagSlot:
         return self.tail_t[32:32 + 8 * g].view(torch.int64), self.tail_t[32 + 8 * g:32 + 9 * g]
 
 
+def _refuse_density(processor, route: str):
+    """The VR refinement routes carry no sounding density plane yet: refused for a processor whose ``node_planes`` name it, and for
+    a model wider than the builder's columns with uncertainty (its further columns can only be auxiliary planes)."""
+    model, gb = getattr(processor, "model", None), getattr(processor, "graph_builder", None)
+    wider = model is not None and gb is not None and getattr(model, "in_channels", 0) > gb.n_node_columns(True)
+    if wider or "sounding_density" in (getattr(processor, "node_planes", None) or ()):
+        raise NotImplementedError(f"{route} does not carry the sounding density plane yet: a model whose node_planes hold "
+                                  "'sounding_density' runs through BathymetricPipeline.process_grid / process_survey_device")
+
+
 class NativeVRProcessor:
     CLASS_NOISE = 2
     BATCH_NODE_BUDGET = 50000        # nodes to accumulate before a flush (reference :128)
     MAX_GRIDS_PER_BATCH = 32768      # the library takes at most 60 000 grids per batch (a BAG of 3 x 3 grids reaches that before any cell budget)
 
     def __init__(self, model: BathymetricGNN, graph_builder: GraphBuilder, device=None,
-                 auto_correct_threshold: float = 0.85):
+                 auto_correct_threshold: float = 0.85, node_planes=None):
         self.model = model
+        # (the checkpoint's "node_planes", when it states them: the VR refinement routes carry no sounding density plane yet)
+        # None: what the model carries (BathymetricPipeline.set_model / load_model leave the checkpoint's key on it)
+        self.node_planes = tuple(node_planes) if node_planes is not None else getattr(model, "node_planes", None)
         self.graph_builder = graph_builder
         self.device = device
         self.auto_correct_threshold = auto_correct_threshold
@@ -471,6 +484,7 @@ class NativeVRProcessor:
         from .. import runtime as rt
         if sidecar is not None and not sidecar.fresh:
             raise ValueError("process_refinements(sidecar=...) needs a fresh SidecarBuilder: this one has been added to already")
+        _refuse_density(self, "process_refinements")
         thr = self.auto_correct_threshold if auto_correct_threshold is None else auto_correct_threshold
         self._sync_options()
         tab = handler.refinement_table()
@@ -691,6 +705,7 @@ def run_refinements(processor: NativeVRProcessor, handler, writer, min_valid_rat
     (``NativeVRProcessor.process_refinements``); the sink is still fed grid by grid, in iteration order.  Any other handler /
     writer (e.g. ``SRBagHandler``, the reference's own classes) takes the loop below, where a pipelined submission gathers
     ``processor.PIPELINE_COALESCE`` reference-size batches (the results do not depend on how grids are batched)."""
+    _refuse_density(processor, "run_refinements")
     thr = processor.auto_correct_threshold if auto_correct_threshold is None else auto_correct_threshold
     can_route = (hasattr(handler, "refinement_table") and hasattr(handler, "varres_refinements") and hasattr(writer, "write_records")
                  and hasattr(processor, "process_refinements"))

@@ -263,7 +263,8 @@ class TileStore:
     store assembled by hand may leave it None.  ``Trainer`` plans its steps with it (``step_plan``)."""
 
     def __init__(self, kind: str, hw, res, depth, mask, unc=None, labels=None, difference=None, class_counts=None,
-                 graph_builder=None, noise_generator=None, augment: bool = True, seed: int = 0, device=None, node_counts=None):
+                 graph_builder=None, noise_generator=None, augment: bool = True, seed: int = 0, device=None, node_counts=None,
+                 density=None):
         from ..data import GraphBuilder, NoiseAugmentor, SyntheticNoiseGenerator
         assert kind in ("synthetic", "ground_truth")
         self.kind = kind
@@ -272,7 +273,10 @@ class TileStore:
         self.res = np.ascontiguousarray(res, np.float64).reshape(-1, 2)
         self.offsets = _tile_offsets(self.hw)
         self.depth, self.mask, self.unc, self.labels, self.difference = depth, mask, unc, labels, difference
-        for t in (depth, mask, unc, labels, difference):
+        # per-cell sounding density (SoundingGrid.density_plane), float32, or None: one more node-feature column behind the others,
+        # taken as it is (the synthetic noise leaves it untouched)
+        self.density = density
+        for t in (depth, mask, unc, labels, difference, density):
             if t is not None and t.numel() != int(self.offsets[-1]):
                 raise ValueError("tile table and planes disagree on the number of cells")
         self.uniform = len(self.hw) > 0 and bool((self.hw == self.hw[0]).all())
@@ -293,9 +297,11 @@ class TileStore:
 
     # ---- constructors --------------------------------------------------------------------------------------------------
     @classmethod
-    def from_tiles(cls, depths, valid_masks=None, uncertainties=None, resolutions=None, device=None, **kw) -> "TileStore":
+    def from_tiles(cls, depths, valid_masks=None, uncertainties=None, resolutions=None, device=None, densities=None,
+                   **kw) -> "TileStore":
         """Clean tiles (host arrays) for synthetic noise.  ``valid_masks[i]`` None: ``isfinite(depth)``; ``uncertainties``: for
-        every tile or for none; ``resolutions``: one ``(x, y)`` per tile (default 1.0).  Keywords: ``graph_builder``,
+        every tile or for none, and so ``densities`` (the tiles' sounding density); ``resolutions``: one ``(x, y)`` per tile
+        (default 1.0).  Keywords: ``graph_builder``,
         ``noise_generator``, ``augment`` (True: ``NoiseAugmentor`` with a drawn intensity per sample), ``seed``."""
         from ..data import GraphBuilder
         device = rt.resolve_device(device)
@@ -305,32 +311,36 @@ class TileStore:
         if n == 0:
             raise ValueError("a TileStore needs at least one tile")
         resolutions = [(1.0, 1.0)] * n if resolutions is None else list(resolutions)
+        a = gb.upload_density(None if densities is None else list(densities), list(depths))
         hw, res, d, m, u = gb.upload_tiles(list(depths), None if valid_masks is None else list(valid_masks), uncertainties, resolutions)
         masks = [None] * n if valid_masks is None else list(valid_masks)
         nodes = [int(np.count_nonzero(np.isfinite(np.asarray(t, dtype=np.float32)) if v is None else np.asarray(v, dtype=bool)))
                  for t, v in zip(depths, masks)]                               # (the masks upload_tiles stores)
         return cls("synthetic", hw, res, d.to(device), m.to(device), None if u is None else u.to(device), device=device,
-                   node_counts=nodes, **kw)
+                   node_counts=nodes, density=a[0].to(device) if a else None, **kw)
 
     @classmethod
     def from_grid(cls, grid, tile_manager, device=None, **kw) -> "TileStore":
         """The tiles ``tile_manager.iterate_tiles(grid, skip_empty=True)`` yields (trainer.py:351), at the grid's resolution."""
         tiles = list(tile_manager.iterate_tiles(grid, skip_empty=True))
         unc = [t.uncertainty for t in tiles] if tiles and tiles[0].uncertainty is not None else None
+        den = getattr(grid, "density", None)                   # (BathymetricGrid.density: the tiles' windows of it)
+        den = None if den is None else [np.asarray(den)[t.row_start:t.row_end, t.col_start:t.col_end] for t in tiles]
         return cls.from_tiles([t.data for t in tiles], [t.valid_mask for t in tiles], unc, [grid.resolution] * len(tiles),
-                              device=device, **kw)
+                              device=device, densities=den, **kw)
 
     @classmethod
     def from_ground_truth(cls, labels, difference, noisy_depth, uncertainty=None, resolution=(1.0, 1.0), tile_size: int = 512,
-                          overlap: int = 64, min_valid_ratio: float = 0.1, device=None, **kw) -> "TileStore":
+                          overlap: int = 64, min_valid_ratio: float = 0.1, device=None, density=None, **kw) -> "TileStore":
         """A ground-truth raster as its bands hold it: 1 labels (0 seafloor, 2 noise, -1 nodata), 2 difference (noisy - clean),
-        3 noisy depth, 5 uncertainty (optional).  Cut with ``plan_ground_truth_tiles``; a cell is valid where its label is
+        3 noisy depth, 5 uncertainty (optional); ``density``: the raster's sounding density plane (optional, of the same kind as
+        the other planes).  Cut with ``plan_ground_truth_tiles``; a cell is valid where its label is
         >= 0.  The planes are host arrays, or device tensors (``GroundTruth.training_planes()``): then only the label plane is
         copied to the host, to plan the tiles, and the tiles are cut on the device; the store is the same bit for bit."""
         device = rt.resolve_device(device)
         on_device = isinstance(labels, torch.Tensor)
         if on_device:
-            if any(p is not None and not isinstance(p, torch.Tensor) for p in (difference, noisy_depth, uncertainty)):
+            if any(p is not None and not isinstance(p, torch.Tensor) for p in (difference, noisy_depth, uncertainty, density)):
                 raise TypeError("labels is a tensor: the other planes must be tensors too")
             labels_dev = labels.to(device=device, dtype=torch.int32)
             labels = labels_dev.cpu().numpy()
@@ -343,6 +353,8 @@ class TileStore:
                   "depth": (noisy_depth, np.float32)}
         if uncertainty is not None:
             planes["unc"] = (uncertainty, np.float32)
+        if density is not None:
+            planes["density"] = (density, np.float32)
         flat = {}
         for k, (arr, dt) in planes.items():
             if not on_device:
@@ -359,13 +371,14 @@ class TileStore:
         res = np.array([(float(resolution[0]), float(resolution[1]))] * len(boxes), np.float64)
         store = cls("ground_truth", hw, res, flat["depth"], (flat["labels"] >= 0).view(torch.uint8), flat.get("unc"),
                     labels=flat["labels"], difference=flat["difference"], class_counts=counts, device=device,
-                    node_counts=[int(np.count_nonzero(labels[r0:r1, c0:c1] >= 0)) for r0, c0, r1, c1 in boxes], **kw)
+                    node_counts=[int(np.count_nonzero(labels[r0:r1, c0:c1] >= 0)) for r0, c0, r1, c1 in boxes],
+                    density=flat.get("density"), **kw)
         store.boxes = boxes
         return store
 
     @classmethod
     def from_ground_truths(cls, rasters, tile_size: int = 512, overlap: int = 64, min_valid_ratio: float = 0.1, device=None,
-                           **kw) -> "TileStore":
+                           densities=None, **kw) -> "TileStore":
         """One ``"ground_truth"`` store from several ground-truth rasters (the reference's ``GroundTruthDataset`` takes a list
         of them), planned and cut on the device: no plane leaves HBM.  ``rasters``: a sequence whose items are a
         ``data.GroundTruth`` (its ``training_planes()``, at the resolution ``(abs(transform[1]), abs(transform[5]))``, or
@@ -380,7 +393,10 @@ class TileStore:
 
         The store is ``from_ground_truth`` of every raster, concatenated, bit for bit (tiles in raster order and in the reference's
         scan order inside a raster; the mask is ``labels >= 0``); ``boxes`` lists ``(r0, c0, r1, c1)`` per tile, ``sources`` (int32)
-        the index of its raster in ``rasters``, the class counts are summed over the rasters."""
+        the index of its raster in ``rasters``, the class counts are summed over the rasters.
+
+        ``densities``: one sounding density plane per raster (of the raster's shape; all or none), cut with the same boxes in a
+        second ``bgnn_tile_cut`` per raster (the first one's four planes are taken)."""
         from ..data.ground_truth import GroundTruth
         device = rt.resolve_device(device)
         ctx = rt.get_context(device)
@@ -406,6 +422,18 @@ class TileStore:
             scanned.append({"index": k, "planes": planes, "res": (float(resolution[0]), float(resolution[1]))})
         if len({r["planes"][3] is None for r in scanned}) > 1:
             raise ValueError("some rasters have an uncertainty plane and some have none: the graphs would differ in in_channels")
+        if densities is not None:
+            densities = list(densities)
+            if len(densities) != len(scanned) or len({a is None for a in densities}) > 1:
+                raise ValueError("densities: one sounding density plane per raster, for every raster or for none")
+            if densities[0] is None:
+                densities = None
+        if densities is not None:
+            for r, a in zip(scanned, densities):
+                r["density"] = _plane_to_device(a, torch.float32, device)
+                if tuple(r["density"].shape) != tuple(r["planes"][0].shape):
+                    raise ValueError(f"raster {r['index']}: density has shape {tuple(r['density'].shape)}, labels "
+                                     f"{tuple(r['planes'][0].shape)}")
         for r in scanned:                                # first pass: every raster's scan is queued before any count is read
             height, width = r["planes"][0].shape
             r["candidates"] = plan_tile_boxes(height, width, tile_size, overlap)
@@ -424,15 +452,16 @@ class TileStore:
             raise ValueError("the ground-truth rasters yield no tile")
         hw, stores, mask = _cut_store([(r["planes"], r["boxes"]) for r in scanned], ctx=ctx)      # second pass: one cut per raster
         res = np.array([r["res"] for r in scanned for _ in r["boxes"]], np.float64)
+        den = None if densities is None else _cut_store([([r["density"]], r["boxes"]) for r in scanned], ctx=ctx)[1][0]
         store = cls("ground_truth", hw, res, stores[2], mask, stores[3], labels=stores[0], difference=stores[1],
-                    class_counts=class_counts, device=device, node_counts=[v for r in scanned for v in r["nodes"]], **kw)
+                    class_counts=class_counts, device=device, node_counts=[v for r in scanned for v in r["nodes"]], density=den, **kw)
         store.boxes = boxes
         store.sources = np.array([r["index"] for r in scanned for _ in r["boxes"]], np.int32)
         return store
 
     @classmethod
     def from_survey(cls, depth, tile_manager, uncertainty=None, nodata_value: Optional[float] = 1.0e6, resolution=(1.0, 1.0),
-                    device=None, **kw) -> "TileStore":
+                    device=None, density=None, **kw) -> "TileStore":
         """The device form of ``from_grid``: a ``"synthetic"`` store of the tiles ``tile_manager.iterate_tiles(grid,
         skip_empty=True)`` yields for ``BathymetricGrid(depth, uncertainty, nodata_value, resolution=resolution)``, without the
         survey leaving HBM.  ``depth`` / ``uncertainty``: ``[H, W]`` float32 device tensors (host arrays are uploaded once).
@@ -446,11 +475,15 @@ class TileStore:
         invalid cells keep their value, nodata sentinel, NaN payload and infinities included -- the tile's crop of the grid's valid
         mask as uint8, and the uncertainty as it is.  So here the depth and uncertainty words are moved untouched and the mask is
         the predicate on the depth.  The store equals ``from_grid``'s bit for bit: ``hw``, ``res``, ``offsets``, depth, mask,
-        uncertainty, ``uniform``."""
+        uncertainty, ``uniform``.  ``density`` (the survey's sounding density plane, ``SoundingGrid.density_plane``) is a third plane
+        of the same cut, moved untouched like the uncertainty."""
         device = rt.resolve_device(device)
         ctx = rt.get_context(device)
         planes = [_plane_to_device(depth, torch.float32, device),
-                  None if uncertainty is None else _plane_to_device(uncertainty, torch.float32, device)]
+                  None if uncertainty is None else _plane_to_device(uncertainty, torch.float32, device),
+                  None if density is None else _plane_to_device(density, torch.float32, device)]
+        if planes[2] is not None and tuple(planes[2].shape) != tuple(planes[0].shape):
+            raise ValueError(f"density has shape {tuple(planes[2].shape)}, depth {tuple(planes[0].shape)}")
         if planes[0].dim() != 2:
             raise ValueError(f"depth must be a 2-D grid, got shape {tuple(planes[0].shape)}")
         if planes[1] is not None and tuple(planes[1].shape) != tuple(planes[0].shape):
@@ -465,7 +498,8 @@ class TileStore:
             raise ValueError("a TileStore needs at least one tile")
         hw, stores, mask = _cut_store([(planes, boxes)], nodata=nodata_value, ctx=ctx)
         res = np.array([(float(resolution[0]), float(resolution[1]))] * len(boxes), np.float64)
-        store = cls("synthetic", hw, res, stores[0], mask, stores[1], device=device, node_counts=[v for _, v in kept], **kw)
+        store = cls("synthetic", hw, res, stores[0], mask, stores[1], device=device, node_counts=[v for _, v in kept],
+                    density=stores[2], **kw)
         store.boxes = boxes
         return store
 
@@ -483,6 +517,9 @@ class TileStore:
         kept grids.  ``store.grids``: per truth the indices of its kept grids (int64), ``store.sources`` (int32) the truth of every
         tile.  No grid kept at all raises ``ValueError``."""
         from ..data.vr_ground_truth import NativeGroundTruth
+        if kw.get("density") is not None or kw.pop("densities", None) is not None:
+            raise NotImplementedError("from_refinement_pairs does not carry the sounding density plane yet: VR refinement grids "
+                                      "train without it")
         device = rt.resolve_device(device)
         ctx = rt.get_context(device)
         truths = [truths] if isinstance(truths, NativeGroundTruth) else list(truths)
@@ -525,21 +562,28 @@ class TileStore:
 
     @property
     def in_channels(self) -> int:
-        return self.graph_builder.n_node_columns(self.unc is not None)
+        return self.graph_builder.n_node_columns(self.unc is not None, 0 if self.density is None else 1)
+
+    @property
+    def node_planes(self) -> List[str]:
+        """The planes the store's graphs carry beside the computed node features, in column order: what a checkpoint states as
+        ``"node_planes"`` (a sublist of ``rt.NODE_PLANES``)."""
+        return [name for name, t in zip(rt.NODE_PLANES, (self.unc, self.density)) if t is not None]
 
     def gather(self, indices: Sequence[int], ops=None):
         """``(hw, res, planes)`` of the tiles ``indices``, tile ``k`` of them under ``ops[k]`` (``dihedral_ops``;
         include/bgnn_augment.h; None: every tile as it is stored, op 0): ``hw`` / ``res`` as ``transformed_tile_table`` gives
         them, ``planes`` the dict ``depth``, ``mask``, ``unc``, ``labels``, ``difference`` (None where the store has none), every
         plane's tiles concatenated in the order of ``indices``.  One ``bgnn_tile_gather`` launch for all planes, from a table of
-        one entry per tile; a tile may be named more than once.  Asynchronous on the context's stream, ordered against the
+        one entry per tile; a tile may be named more than once.  A store with a ``density`` plane returns it as ``density`` too, from
+        a second launch with the same table (the first one's four word planes are taken).  Asynchronous on the context's stream, ordered against the
         caller's current stream."""
         idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
         if idx.size == 0 or idx.min() < 0 or idx.max() >= len(self):
             raise IndexError(f"tile indices {idx.tolist()} outside a store of {len(self)} tiles")
         ops = _ops_array(np.zeros(idx.size, np.int32) if ops is None else ops, idx.size)
         words = {"depth": self.depth, "unc": self.unc, "labels": self.labels, "difference": self.difference}
-        for k, t in list(words.items()) + [("mask", self.mask)]:
+        for k, t in list(words.items()) + [("mask", self.mask), ("density", self.density)]:
             if t is None:
                 continue
             want = (torch.uint8, torch.bool) if k == "mask" else (torch.float32, torch.int32)
@@ -559,6 +603,11 @@ class TileStore:
         rt.check(ctx.lib.bgnn_tile_gather(ctx.handle, _pointers(list(words.values())), _pointers([out[k] for k in words]), len(words),
                                           rt.ptr(self.mask), rt.ptr(out["mask"]), store_cells, total, C.c_void_p(table.ctypes.data),
                                           idx.size, rt.ptr(ws), C.c_size_t(ws_bytes)))
+        if self.density is not None:                    # (the key exists only for a store that has the plane)
+            out["density"] = torch.empty(total, dtype=self.density.dtype, device=self.device)
+            rt.check(ctx.lib.bgnn_tile_gather(ctx.handle, _pointers([self.density]), _pointers([out["density"]]), 1, None, None,
+                                              store_cells, total, C.c_void_p(table.ctypes.data), idx.size, rt.ptr(ws),
+                                              C.c_size_t(ws_bytes)))
         ctx.end()
         hw, res = transformed_tile_table(self.hw[idx], self.res[idx], ops)
         return hw, res, out
@@ -589,7 +638,8 @@ class TileStore:
         else:
             depth, mode = p["depth"], rt.TARGETS_GROUND_TRUTH
             a, b, labels, nmask = p["difference"], None, p["labels"], None
-        graph = self.graph_builder.build_from_device(hw, res, depth, p["mask"], p["unc"], ctx=ctx)
+        graph = self.graph_builder.build_from_device(hw, res, depth, p["mask"], p["unc"], ctx=ctx,
+                                                     aux_t=[p["density"]] if "density" in p else None)
         targets = training_targets_fused(graph, mode, a, b, labels, nmask)
         return graph, targets
 

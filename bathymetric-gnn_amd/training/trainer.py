@@ -466,6 +466,11 @@ class Trainer:
         }
         if self.scheduler is not None:
             checkpoint["scheduler_state_dict"] = self.scheduler.state_dict()
+        # the planes the training graphs carried beside the computed node features, in column order ("uncertainty",
+        # "sounding_density" or a sublist): BathymetricPipeline.load_model passes exactly those
+        planes = getattr(self.train_store, "node_planes", None)
+        if planes is not None:
+            checkpoint["node_planes"] = [str(p) for p in planes]
         path = self.output_dir / filename
         torch.save(checkpoint, path)
         logger.info(f"Saved checkpoint: {path}")

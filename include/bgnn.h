@@ -127,7 +127,7 @@ enum { /* GNNBackbone gnn_type (models/gnn.py:120-143); GAT is the hot path, the
   BGNN_GNN_GAT = 0, BGNN_GNN_GCN = 1, BGNN_GNN_SAGE = 2, BGNN_GNN_GIN = 3
 };
 typedef struct bgnn_model_desc {
-  int32_t in_channels;        /* 7, or 8 with the uncertainty column                     */
+  int32_t in_channels;        /* 7, or 8 with the uncertainty column; 9 .. 16 with auxiliary planes (bgnn_aux.h) */
   int32_t hidden;             /* 64 (the fused kernels' width); 32 and 128 run generic kernels */
   int32_t num_layers;         /* num_gnn_layers (>= 1)                                   */
   int32_t heads;              /* 4; GAT only, power of two, heads * hidden <= 512 (above 256: generic kernels, two column blocks); last layer: 1 head, mean (gnn.py:125-132) */
