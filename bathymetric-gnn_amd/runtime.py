@@ -463,6 +463,28 @@ AUX_ROW_FLOATS = 16                                # BGNN_AUX_ROW_FLOATS
 # the planes a model may take beside the computed node features, in column order (checkpoints: "node_planes")
 NODE_PLANES = ("uncertainty", "sounding_density")
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_quantile.h declares (exact percentiles of errors that stay on the device)
+_QUANTILE_SIGNATURES = {
+    "bgnn_quantile_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bgnn_quantile_add": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
+    "bgnn_quantile_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "bgnn_quantile_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+}
+QUANTILE_MAX_FRACTIONS = 3                         # BGNN_QUANTILE_MAX_FRACTIONS
+QUANTILE_TOP_BITS = 11                             # BGNN_QUANTILE_TOP_BITS
+QUANTILE_MAX_GRID = 2048                           # BGNN_QUANTILE_MAX_GRID
+QUANTILE_WG_ROWS = 4096                            # BGNN_QUANTILE_WG_ROWS: one workgroup's share of the rows, one slot reservation
+QUANTILE_MAX_CAPACITY = 2 ** 32 - 1
+# BGNN_QUANTILE_ST_*: the state block, BGNN_QUANTILE_STATE_BYTES
+QUANTILE_STATE_DTYPE = np.dtype([("rows", "<i8"), ("filed", "<i8"), ("nonfinite", "<i8"), ("dropped", "<i8"), ("cursor", "<i8"),
+                                 ("reserved", "<i8", (3,)), ("hist", "<u4", (1 << QUANTILE_TOP_BITS,))])
+QUANTILE_STATE_BYTES = QUANTILE_STATE_DTYPE.itemsize
+# BGNN_QUANTILE_OUT_*: the result block of a selection, BGNN_QUANTILE_OUT_BYTES
+QUANTILE_OUT_DTYPE = np.dtype([("count", "<i8"), ("nonfinite", "<i8"), ("dropped", "<i8"), ("rows", "<i8"),
+                               ("ranks", [("lo", "<i8"), ("hi", "<i8"), ("v_lo", "<f4"), ("v_hi", "<f4")], (QUANTILE_MAX_FRACTIONS,))])
+QUANTILE_OUT_BYTES = QUANTILE_OUT_DTYPE.itemsize
+
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -477,7 +499,7 @@ def load_library(path: Optional[str] = None):
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
     include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h, include/bgnn_vrtruth.h,
     include/bgnn_augment.h, include/bgnn_curve.h, include/bgnn_soundings.h, include/bgnn_soundings_robust.h,
-    include/bgnn_soundings_vr.h and include/bgnn_aux.h.  Needs no GPU."""
+    include/bgnn_soundings_vr.h, include/bgnn_aux.h and include/bgnn_quantile.h.  Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -494,7 +516,7 @@ def load_library(path: Optional[str] = None):
                 list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()) + \
                 list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()) + list(_CURVE_SIGNATURES.items()) + \
                 list(_SOUNDINGS_SIGNATURES.items()) + list(_ROBUST_SIGNATURES.items()) + list(_VR_SOUNDINGS_SIGNATURES.items()) + \
-                list(_AUX_SIGNATURES.items()):
+                list(_AUX_SIGNATURES.items()) + list(_QUANTILE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

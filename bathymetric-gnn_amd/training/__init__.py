@@ -6,9 +6,12 @@ flat weight blob, the packed model refreshed in place), and the reference's ``Tr
 ``scripts/evaluate_model.py`` counted on the device (``evaluation.py``: ``Evaluator``, ``compute_metrics``).  The reference's dataset
 classes themselves (torch_geometric loaders, GDAL, tqdm) stay outside the path.  ``operating_curve.py`` sweeps every confidence
 threshold of a table in one pass over a classified survey and its ground truth (``OperatingCurve``, ``curve_from_block``,
-``recommend_thresholds``)."""
+``recommend_thresholds``).  ``huber_delta.py`` is the adaptive Huber delta the reference defers: the per-epoch percentile of the
+correction errors measured on the device (``CorrectionErrorTracker``, ``device_percentile``) and the policy that turns it into the
+next epoch's delta (``AdaptiveHuberDelta``; ``Trainer(adaptive_delta=...)``)."""
 from .losses import (BathymetricGNNLoss, ClassificationLoss, ConfidenceCalibrationLoss, CorrectionLoss, FeaturePreservationLoss,
                      ShoalSafetyLoss, compute_class_weights, compute_correction_delta)
+from .huber_delta import AdaptiveHuberDelta, CorrectionErrorTracker, device_percentile, percentile_from_ranks
 from .evaluation import Evaluator, compute_metrics, metrics_from_block
 from .operating_curve import OperatingCurve, curve_accumulate, curve_from_block, recommend_thresholds
 from .optim import FusedAdamW

@@ -302,9 +302,16 @@ def compute_class_weights(labels: torch.Tensor, num_classes: int = 3, smoothing:
     return inverse / inverse.sum() * num_classes
 
 
-def compute_correction_delta(corrections: np.ndarray, percentile: float = 95.0, min_delta: float = 1.0) -> float:
+def compute_correction_delta(corrections, percentile: float = 95.0, min_delta: float = 1.0) -> float:
     """The Huber delta from the training data (host, numpy): the ``percentile`` of |corrections|, at least ``min_delta``, so that
-    all but the tail of the corrections fall in the quadratic range; ``min_delta`` for an empty array."""
+    all but the tail of the corrections fall in the quadratic range; ``min_delta`` for an empty array.
+
+    A float32 device tensor stays on the device (``huber_delta.device_percentile``: an exact selection, 104 bytes read back):
+    the percentile of its finite entries as numpy gives it for the same values cast to float64."""
+    if isinstance(corrections, torch.Tensor) and corrections.is_cuda:
+        from .huber_delta import device_percentile
+        value = device_percentile(corrections.detach().to(torch.float32), percentile, absolute=True)["values"][0]
+        return min_delta if value is None else max(value, min_delta)
     corrections = np.asarray(corrections)
     if corrections.size == 0:
         return min_delta

@@ -30,6 +30,7 @@ from torch.optim.lr_scheduler import CosineAnnealingWarmRestarts, ReduceLROnPlat
 
 from .. import runtime as rt
 from ..config.constants import CORRECTION_NORM_CAP, CORRECTION_NORM_FLOOR
+from .huber_delta import AdaptiveHuberDelta, CorrectionErrorTracker
 from .losses import BathymetricGNNLoss, compute_class_weights, compute_correction_delta
 from .optim import FusedAdamW
 from .tile_store import TileStore, dihedral_ops
@@ -173,10 +174,27 @@ class Trainer:
 
     ``augment_geometry`` (None or False: off, the tiles train as they are stored): True turns every training tile by one of the
     eight symmetries of the square per epoch, as the settings' ``augment_rotations`` / ``augment_flips`` allow (``augment_plan``;
-    both flags False: every op is the identity, through the same path)."""
+    both flags False: every op is the identity, through the same path).
+
+    ``adaptive_delta`` (None or False: off, the Huber delta is the one ``_compute_training_stats`` derives from the training data,
+    for the whole run -- the reference's Option 1): True, or an ``AdaptiveHuberDelta`` of the caller's, moves the training
+    criterion's delta between epochs (huber_delta.py; the reference's Options 2 and 3).  The policy starts at the Option-1 delta.
+    Every step files ``|correction - correction_targets|`` of its noise rows into a ``CorrectionErrorTracker`` (one more launch, no
+    host wait); at the end of the epoch the policy's percentile of those errors is read with the epoch's metrics, and the
+    policy's new delta is what the NEXT epoch trains with.  ``history`` gains ``huber_delta`` (the delta the epoch trained with) and
+    ``correction_error_percentile`` (the epoch's measured value, NaN when there was none), the checkpoint ``adaptive_delta`` (the
+    policy's state; ``resume`` restores it and the criterion's delta).  While the delta moves, ``train_loss`` is not comparable
+    across epochs: its correction term is measured with a different delta each epoch.  Validation therefore keeps a criterion
+    of its own (``val_criterion``: the same class weights and term weights) at the fixed Option-1 delta, so that early stopping,
+    ``ReduceLROnPlateau`` and ``best_model.pt`` compare like with like.  The tracker's stage holds one slot (4 bytes) per node of
+    the training store, which bounds the noise rows of an epoch; ``max_tracked_errors`` lowers that.  An epoch that overflows the
+    stage is reported with a warning, its percentile is discarded and the delta stays as it was."""
 
     def __init__(self, config, model, train_store: TileStore, val_store: Optional[TileStore] = None, output_dir=None,
-                 seed: int = 0, batch_nodes: Optional[int] = None, augment_geometry: Optional[bool] = None):
+                 seed: int = 0, batch_nodes: Optional[int] = None, augment_geometry: Optional[bool] = None,
+                 adaptive_delta=None, max_tracked_errors: Optional[int] = None):
+        if max_tracked_errors is not None and int(max_tracked_errors) < 1:
+            raise ValueError(f"max_tracked_errors {max_tracked_errors}: a positive number of rows, or None")
         if batch_nodes is not None and int(batch_nodes) < 1:
             raise ValueError(f"batch_nodes {batch_nodes}: a positive number of cells, or None")
         nodes = getattr(train_store, "node_counts", None)
@@ -218,10 +236,35 @@ class Trainer:
             confidence_weight=self.settings.confidence_weight,
             correction_delta=correction_delta,
         )
+        self.val_criterion = self.criterion
+        self.delta_policy: Optional[AdaptiveHuberDelta] = None
+        self.error_tracker: Optional[CorrectionErrorTracker] = None
+        if adaptive_delta is not None and adaptive_delta is not False:
+            self.delta_policy = AdaptiveHuberDelta() if adaptive_delta is True else adaptive_delta
+            if not isinstance(self.delta_policy, AdaptiveHuberDelta):
+                raise TypeError("adaptive_delta: None, a bool or an AdaptiveHuberDelta expected")
+            self.criterion.correction_loss.delta = self.delta_policy.start(correction_delta)
+            self.val_criterion = BathymetricGNNLoss(
+                class_weights=class_weights,
+                classification_weight=self.settings.classification_weight,
+                correction_weight=self.settings.correction_weight,
+                confidence_weight=self.settings.confidence_weight,
+                correction_delta=correction_delta,
+            )
+            counts = getattr(train_store, "node_counts", None)
+            capacity = int(np.sum(counts)) if counts is not None else int(np.asarray(train_store.offsets)[-1])
+            if max_tracked_errors is not None:
+                capacity = min(capacity, int(max_tracked_errors))
+            self.error_tracker = CorrectionErrorTracker(max(capacity, 1), device=self.device)
+            logger.info(f"Adaptive Huber delta ({self.delta_policy.mode}): p{self.delta_policy.percentile:g} of the epoch's "
+                        f"correction errors, {self.error_tracker.capacity} tracked rows")
 
         self.current_epoch = 0
         self.stop_rule = StopRule(self.settings.patience, self.settings.min_delta)
         self.history: Dict[str, List[float]] = {"train_loss": [], "val_loss": [], "train_acc": [], "val_acc": []}
+        if self.delta_policy is not None:
+            self.history["huber_delta"] = []
+            self.history["correction_error_percentile"] = []
         self._next_epoch = 0
         self.train_metrics = EpochMetrics(self.device)
         self.val_metrics = EpochMetrics(self.device)
@@ -372,6 +415,9 @@ class Trainer:
         self.model.train()
         metrics = self.train_metrics
         metrics.reset()
+        tracker = getattr(self, "error_tracker", None)
+        if tracker is not None:
+            tracker.reset()
         ops = self.augment_plan(self.current_epoch) if getattr(self, "augment_geometry", False) else None
         for indices, drop_seed in self.step_plan(self.current_epoch):
             graph, targets = self.train_store.batch(indices, self.current_epoch, ops=None if ops is None else ops[indices])
@@ -379,10 +425,32 @@ class Trainer:
             self.optimizer.zero_grad()
             outputs = self.model(graph)
             losses = self.criterion(outputs, targets)
+            if tracker is not None and outputs.get("correction") is not None and targets.get("correction_targets") is not None:
+                tracker.add(outputs["correction"], targets["correction_targets"], targets.get("noise_mask"))
             losses["total"].backward()
             self.optimizer.step()
             metrics.update(graph, losses, self.criterion)
-        return metrics.result()
+        result = metrics.result()
+        if tracker is not None:
+            result.update(self._adapt_delta())
+        return result
+
+    def _adapt_delta(self) -> Dict[str, float]:
+        """The end of an epoch under ``adaptive_delta``: the epoch's error percentile (the tracker's single read-back) through
+        the policy; the training criterion gets the new delta.  Returns the epoch's two history entries."""
+        policy, tracker = self.delta_policy, self.error_tracker
+        trained_with = float(self.criterion.correction_loss.delta)
+        measured = tracker.percentiles([policy.percentile])
+        q = measured["values"][0]
+        if measured["dropped"] > 0:
+            logger.warning(f"Epoch {self.current_epoch + 1}: {measured['dropped']} correction errors found the tracker's "
+                           f"{tracker.capacity} slots full; the epoch's percentile is discarded and the Huber delta stays "
+                           f"{trained_with:.4f}")
+        self.criterion.correction_loss.delta = policy.update(q)
+        if q is not None:
+            logger.info(f"Epoch {self.current_epoch + 1}: p{policy.percentile:g} of |correction error| = {q:.4f} over "
+                        f"{measured['count']} rows; Huber delta {trained_with:.4f} -> {self.criterion.correction_loss.delta:.4f}")
+        return {"huber_delta": trained_with, "correction_error_percentile": float("nan") if q is None else float(q)}
 
     def _validate_epoch(self) -> Dict[str, float]:
         """Run one validation epoch."""
@@ -393,13 +461,15 @@ class Trainer:
             for indices, _ in self.step_plan(self.current_epoch, validation=True):
                 graph, targets = self.val_store.batch(indices, self.current_epoch)
                 outputs = self.model(graph)
-                losses = self.criterion(outputs, targets)
-                metrics.update(graph, losses, self.criterion)
+                criterion = getattr(self, "val_criterion", self.criterion)
+                losses = criterion(outputs, targets)
+                metrics.update(graph, losses, criterion)
         return metrics.result()
 
     def train(self) -> Dict[str, List[float]]:
         """Run the full training loop (trainer.py:662-728; after ``resume`` it continues at the epoch after the checkpoint's).
-        Returns the history: ``train_loss``, ``val_loss``, ``train_acc``, ``val_acc``."""
+        Returns the history: ``train_loss``, ``val_loss``, ``train_acc``, ``val_acc``; under ``adaptive_delta`` also ``huber_delta``
+        and ``correction_error_percentile``."""
         history = self.history
         epochs = int(self.settings.epochs)
         for epoch in range(self._next_epoch, epochs):
@@ -407,6 +477,9 @@ class Trainer:
             train_metrics = self._train_epoch()
             history["train_loss"].append(train_metrics["loss"])
             history["train_acc"].append(train_metrics["accuracy"])
+            if "huber_delta" in train_metrics:
+                history["huber_delta"].append(train_metrics["huber_delta"])
+                history["correction_error_percentile"].append(train_metrics["correction_error_percentile"])
             if self.val_store is not None:
                 val_metrics = self._validate_epoch()
                 history["val_loss"].append(val_metrics["loss"])
@@ -471,13 +544,16 @@ class Trainer:
         planes = getattr(self.train_store, "node_planes", None)
         if planes is not None:
             checkpoint["node_planes"] = [str(p) for p in planes]
+        if getattr(self, "delta_policy", None) is not None:
+            checkpoint["adaptive_delta"] = self.delta_policy.state_dict()
         path = self.output_dir / filename
         torch.save(checkpoint, path)
         logger.info(f"Saved checkpoint: {path}")
 
     def resume(self, path):
         """Restore model, optimizer, scheduler, epoch, best loss, patience counter and history from a checkpoint of this
-        class; the next ``train()`` continues at the following epoch."""
+        class; the next ``train()`` continues at the following epoch.  Under ``adaptive_delta`` the policy's state and the
+        training criterion's delta come back too (a checkpoint without them resumes at the Option-1 delta)."""
         ckpt = torch.load(Path(path), map_location="cpu", weights_only=True)
         self.model.load_state_dict(ckpt["model_state_dict"])
         self.model.to(self.device)
@@ -490,4 +566,11 @@ class Trainer:
         self.patience_counter = int(ckpt.get("patience_counter", 0))
         hist = ckpt.get("history") or {}
         self.history = {k: [float(v) for v in hist.get(k, [])] for k in ("train_loss", "val_loss", "train_acc", "val_acc")}
+        policy = getattr(self, "delta_policy", None)
+        if policy is not None:
+            for k in ("huber_delta", "correction_error_percentile"):
+                self.history[k] = [float(v) for v in hist.get(k, [])]
+            if "adaptive_delta" in ckpt:
+                policy.load_state_dict(ckpt["adaptive_delta"])
+                self.criterion.correction_loss.delta = policy.delta
         return ckpt
