@@ -39,4 +39,45 @@ struct SumOp {
   __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
 };
 
+// The exclusive scan of one integer per thread over the workgroup; *total: the sum.  scratch: BLOCK_THREADS / 64 values of LDS,
+// free again on return.  Every thread calls it.
+template <typename T>
+__device__ __forceinline__ T block_exclusive_scan(T v, T *scratch, T *total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  T incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T up = __shfl_up(incl, o);
+    if (lane >= o) incl += up;
+  }
+  __syncthreads();
+  if (lane == 63) scratch[wave] = incl;
+  __syncthreads();
+  T before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < BLOCK_THREADS / 64; ++w) {
+    const T c = scratch[w];
+    before += w < wave ? c : 0;
+    all += c;
+  }
+  *total = all;
+  return before + incl - v;
+}
+
+// One workgroup: sums[] (one sum per tile of some tiled scan) becomes its own exclusive scan; the sum of it all goes to *total.
+template <typename T, typename Total>
+__global__ __launch_bounds__(BLOCK_THREADS) void scan_tile_sums(T *__restrict__ sums, int64_t n_tiles, Total *__restrict__ total) {
+  __shared__ T scratch[BLOCK_THREADS / 64];
+  T running = 0;
+  for (int64_t base = 0; base < n_tiles; base += BLOCK_THREADS) {
+    const int64_t i = base + threadIdx.x;
+    const T v = i < n_tiles ? sums[i] : 0;
+    T all;
+    const T before = block_exclusive_scan(v, scratch, &all);
+    if (i < n_tiles) sums[i] = running + before;
+    running += all;
+  }
+  if (threadIdx.x == 0) *total = (Total)running;
+}
+
 }  // namespace bgnn

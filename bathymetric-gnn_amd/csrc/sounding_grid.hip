@@ -1,15 +1,17 @@
 // Gridding a point cloud of soundings (include/bgnn_soundings.h): count, mean, standard deviation, minimum and maximum per cell
 // from one pass over (x, y, z), 20 B per sounding, bound by the scattered atomics into the cells.
 //
-//   soundings_add       grid-stride over shares of 1024 soundings, four per thread loaded before any is filed.  A sounding is
-//                       classified (sounding_file.h: not finite / outside / out of range / accepted) and an accepted one goes into its cell with
-//                       six global integer atomics: n, S1 = sum q, the low and the high words of q^2, and the two extremes under
-//                       the order-preserving map of float32 onto uint32.  The minimum is kept as the maximum of the inverted key,
-//                       so an all-zero state is the empty one.  A swath puts runs of consecutive soundings into one cell: a run of
-//                       neighbouring lanes on one cell is summed towards its first lane inside the wave (a segmented halving over
-//                       shuffles, skipped where no two neighbours of the wave share a cell) and only that lane goes to memory --
-//                       measured on 2e8 soundings: 9.2 ms against 60.7 ms in swath order, 49.6 ms either way when scattered.  The
-//                       four counters are reduced per workgroup (block_reduce) and added with one atomic per workgroup and counter.
+//   sounding_pass<UniformAddress, FileSink>
+//                       the cloud pass of sounding_pass.h: grid-stride over shares of 1024 soundings, four per thread loaded before
+//                       any is filed.  A sounding is classified (sounding_file.h: not finite / outside / out of range /
+//                       accepted) and an accepted one goes into its cell with six global integer atomics: n, S1 = sum q, the low
+//                       and the high words of q^2, and the two extremes under the order-preserving map of float32 onto uint32.
+//                       The minimum is kept as the maximum of the inverted key, so an all-zero state is the empty one.  A swath
+//                       puts runs of consecutive soundings into one cell: a run of neighbouring lanes on one cell is summed
+//                       towards its first lane inside the wave (a segmented halving over shuffles, skipped where no two
+//                       neighbours of the wave share a cell) and only that lane goes to memory -- measured on 2e8 soundings:
+//                       9.2 ms against 60.7 ms in swath order, 49.6 ms either way when scattered.  The four counters are reduced
+//                       per workgroup (block_reduce) and added with one atomic per workgroup and counter.
 //   soundings_finalize  one thread per cell: the variance numerator n * S2 - S1^2 is formed exactly in 128 bits and rounded once
 //                       to float64 (its low bits folded into a sticky bit of the top 64: there is no 128-bit conversion on the
 //                       device).  Reads the state only.
@@ -19,65 +21,21 @@
 // All sums are integers: the order of the atomics does not show in the result.  Compiled with -ffp-contract=off: the cell index
 // and the finalisation round operation by operation as the header states them.
 #include "bgnn_internal.h"
-#include "plane_util.h"
-#include "sounding_cell.h"
-#include "sounding_file.h"
+#include "sounding_args.h"
 #include "sounding_moments.h"
-#include "../../include/bgnn_soundings.h"
+#include "sounding_pass.h"
 
 namespace bgnn {
 
 constexpr int SG_THREADS = BLOCK_THREADS;
-constexpr int SG_ITEMS = 4;                           // soundings per thread and step, a workgroup's width apart: coalesced loads
-constexpr int SG_TILE = SG_THREADS * SG_ITEMS;
 constexpr int SG_FINALIZE_MAX_GRID = 1 << 20;
-constexpr int64_t SG_MAX_DIM = 2147483647;
+constexpr int SG_EXTENT_SHARE = 4 * SG_THREADS;        // soundings per workgroup of extent_partial, up to its grid cap
 
 struct ExtentRecord {
   double min_x, max_x, min_y, max_y;
   long long finite_x, finite_y;
 };
 static_assert(sizeof(ExtentRecord) == BGNN_SOUNDINGS_EXTENT_BYTES, "the record the header documents");
-
-__global__ __launch_bounds__(SG_THREADS) void soundings_add(const double *__restrict__ xs, const double *__restrict__ ys,
-                                                            const float *__restrict__ zs, int64_t n, double x0, double y0, double res,
-                                                            int64_t height, int64_t width, char *__restrict__ state) {
-  __shared__ uint32_t scratch[SG_THREADS];
-  SoundingCell *cells = reinterpret_cast<SoundingCell *>(state + BGNN_SOUNDINGS_HEADER_BYTES);
-  const int t = threadIdx.x;
-  uint32_t accepted = 0, nonfinite = 0, outside = 0, out_of_range = 0;      // (a workgroup sees fewer than 2^31 soundings)
-  for (int64_t base = (int64_t)blockIdx.x * SG_TILE; base < n; base += (int64_t)gridDim.x * SG_TILE) {
-    double x[SG_ITEMS], y[SG_ITEMS];
-    float z[SG_ITEMS];
-#pragma unroll
-    for (int k = 0; k < SG_ITEMS; ++k) {
-      const int64_t i = base + k * SG_THREADS + t;
-      const bool in = i < n;
-      x[k] = in ? xs[i] : 0.0;
-      y[k] = in ? ys[i] : 0.0;
-      z[k] = in ? zs[i] : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < SG_ITEMS; ++k) {
-      const bool in = base + k * SG_THREADS + t < n;
-      const int64_t cell = sounding_cell(x[k], y[k], x0, y0, res, height, width);
-      const int kind = in ? sounding_kind(x[k], y[k], z[k], cell >= 0, true) : -1;
-      const bool ok = kind == SOUNDING_ACCEPTED;
-      accepted += ok;
-      nonfinite += kind == SOUNDING_NONFINITE;
-      outside += kind == SOUNDING_OUTSIDE;
-      out_of_range += kind == SOUNDING_OUT_OF_RANGE;
-      file_sounding(cells, ok, cell, z[k]);
-    }
-  }
-  const uint32_t mine[4] = {accepted, nonfinite, outside, out_of_range};
-  unsigned long long *counters = reinterpret_cast<unsigned long long *>(state);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t total = block_reduce(mine[j], scratch, SumOp());
-    if (t == 0 && total) atomicAdd(counters + j, (unsigned long long)total);
-  }
-}
 
 __global__ __launch_bounds__(SG_THREADS) void soundings_finalize(const char *__restrict__ state, int64_t n_cells, int32_t min_count,
                                                                  float nodata, int32_t *__restrict__ count, float *__restrict__ mean,
@@ -151,31 +109,23 @@ __global__ __launch_bounds__(SG_THREADS) void extent_finish(const ExtentRecord *
   extent_reduce_store(r, out);
 }
 
-static inline bool sg_dim_ok(int64_t v) { return v >= 1 && v <= SG_MAX_DIM; }
-static inline bool sg_aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
-static inline bool sg_finite(double v) { return v - v == 0.0; }
-
 }  // namespace bgnn
 
 using namespace bgnn;
 
 extern "C" size_t bgnn_soundings_state_bytes(int64_t height, int64_t width) {
-  if (!sg_dim_ok(height) || !sg_dim_ok(width)) return 0;
+  if (!dim_ok(height) || !dim_ok(width)) return 0;
   const unsigned __int128 bytes = (unsigned __int128)height * (unsigned __int128)width * BGNN_SOUNDINGS_CELL_BYTES + BGNN_SOUNDINGS_HEADER_BYTES;
   return bytes > (unsigned __int128)SIZE_MAX ? 0 : (size_t)bytes;
 }
 
-#define SG_REQUIRE_GRID(fn)                                                                                                  \
-  BGNN_REQUIRE(sg_dim_ok(height) && sg_dim_ok(width), fn ": a grid of %lld x %lld cells, 1 .. 2147483647 each way expected", \
-               (long long)height, (long long)width)
-
 extern "C" int bgnn_soundings_reset(bgnn_ctx *ctx, void *state, int64_t height, int64_t width) {
   // (the context last: what is wrong with the other arguments is reported whatever the context)
   BGNN_REQUIRE(state, "bgnn_soundings_reset: NULL argument");
-  SG_REQUIRE_GRID("bgnn_soundings_reset");
+  BGNN_TRY(require_grid("bgnn_soundings_reset", height, width, "grid", 0, ""));
   BGNN_REQUIRE(bgnn_soundings_state_bytes(height, width) != 0, "bgnn_soundings_reset: the state of %lld x %lld cells exceeds size_t",
                (long long)height, (long long)width);
-  BGNN_REQUIRE(sg_aligned8(state), "bgnn_soundings_reset: the state is not 8-byte aligned");
+  BGNN_REQUIRE(aligned8(state), "bgnn_soundings_reset: the state is not 8-byte aligned");
   BGNN_REQUIRE(ctx, "bgnn_soundings_reset: NULL context");
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
   BGNN_HIP_CHECK(hipMemsetAsync(state, 0, bgnn_soundings_state_bytes(height, width), ctx->stream));
@@ -184,32 +134,21 @@ extern "C" int bgnn_soundings_reset(bgnn_ctx *ctx, void *state, int64_t height, 
 
 extern "C" int bgnn_soundings_add(bgnn_ctx *ctx, const double *x, const double *y, const float *z, int64_t n, double x0, double y0,
                                   double res, int64_t height, int64_t width, int64_t offered, void *state) {
-  BGNN_REQUIRE(n >= 0, "bgnn_soundings_add: %lld soundings", (long long)n);
-  BGNN_REQUIRE(state && (n == 0 || (x && y && z)), "bgnn_soundings_add: NULL argument");
-  BGNN_REQUIRE(sg_finite(res) && res > 0.0, "bgnn_soundings_add: a resolution of %g, a finite number above 0 expected", res);
-  BGNN_REQUIRE(sg_finite(x0) && sg_finite(y0), "bgnn_soundings_add: the origin (%g, %g) is not finite", x0, y0);
-  SG_REQUIRE_GRID("bgnn_soundings_add");
-  BGNN_REQUIRE(offered >= 0, "bgnn_soundings_add: %lld soundings offered before", (long long)offered);
-  BGNN_REQUIRE(n <= (int64_t)BGNN_SOUNDINGS_MAX_TOTAL && offered <= (int64_t)BGNN_SOUNDINGS_MAX_TOTAL - n,
-               "bgnn_soundings_add: %lld soundings after %lld offered before: a total above %lld", (long long)n, (long long)offered,
-               (long long)BGNN_SOUNDINGS_MAX_TOTAL);
-  BGNN_REQUIRE(sg_aligned8(state), "bgnn_soundings_add: the state is not 8-byte aligned");
-  BGNN_REQUIRE(ctx, "bgnn_soundings_add: NULL context");
-  if (n == 0) return BGNN_OK;
-  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
-  const dim3 g(capped_grid((n + SG_TILE - 1) / SG_TILE, PLANE_MAX_GRID)), b(SG_THREADS);
-  hipLaunchKernelGGL(soundings_add, g, b, 0, ctx->stream, x, y, z, n, x0, y0, res, height, width, static_cast<char *>(state));
-  BGNN_HIP_CHECK(hipGetLastError());
-  return BGNN_OK;
+  const char *fn = "bgnn_soundings_add";
+  BGNN_TRY(require_cloud(fn, x, y, z, n, res, x0, y0, "resolution", state != nullptr));
+  BGNN_TRY(require_grid(fn, height, width, "grid", 0, ""));
+  BGNN_TRY(require_offered_total(fn, n, offered));
+  BGNN_REQUIRE(aligned8(state), "%s: the state is not 8-byte aligned", fn);
+  return launch_sounding_pass(fn, ctx, x, y, z, n, UniformAddress{x0, y0, res, height, width}, FileSink{static_cast<char *>(state)});
 }
 
 extern "C" int bgnn_soundings_finalize(bgnn_ctx *ctx, const void *state, int64_t height, int64_t width, int32_t min_count,
                                        float nodata_value, int32_t *count, float *mean, float *std, float *min, float *max,
                                        uint8_t *valid) {
   BGNN_REQUIRE(state && count && mean && std && min && max && valid, "bgnn_soundings_finalize: NULL argument");
-  SG_REQUIRE_GRID("bgnn_soundings_finalize");
+  BGNN_TRY(require_grid("bgnn_soundings_finalize", height, width, "grid", 0, ""));
   BGNN_REQUIRE(min_count >= 1, "bgnn_soundings_finalize: a min_count of %d, at least 1 expected", (int)min_count);
-  BGNN_REQUIRE(sg_aligned8(state), "bgnn_soundings_finalize: the state is not 8-byte aligned");
+  BGNN_REQUIRE(aligned8(state), "bgnn_soundings_finalize: the state is not 8-byte aligned");
   BGNN_REQUIRE(ctx, "bgnn_soundings_finalize: NULL context");
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
   const int64_t n_cells = height * width;
@@ -223,11 +162,11 @@ extern "C" int bgnn_soundings_finalize(bgnn_ctx *ctx, const void *state, int64_t
 extern "C" int bgnn_soundings_extent(bgnn_ctx *ctx, const double *x, const double *y, int64_t n, void *extent) {
   BGNN_REQUIRE(n >= 0, "bgnn_soundings_extent: %lld soundings", (long long)n);
   BGNN_REQUIRE(extent && (n == 0 || (x && y)), "bgnn_soundings_extent: NULL argument");
-  BGNN_REQUIRE(sg_aligned8(extent), "bgnn_soundings_extent: the extent buffer is not 8-byte aligned");
+  BGNN_REQUIRE(aligned8(extent), "bgnn_soundings_extent: the extent buffer is not 8-byte aligned");
   BGNN_REQUIRE(ctx, "bgnn_soundings_extent: NULL context");
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
   ExtentRecord *records = static_cast<ExtentRecord *>(extent);
-  const int parts = capped_grid((n + SG_TILE - 1) / SG_TILE, BGNN_SOUNDINGS_EXTENT_MAX_GRID);
+  const int parts = capped_grid((n + SG_EXTENT_SHARE - 1) / SG_EXTENT_SHARE, BGNN_SOUNDINGS_EXTENT_MAX_GRID);
   hipLaunchKernelGGL(extent_partial, dim3(parts), dim3(SG_THREADS), 0, ctx->stream, x, y, n, records + 1);
   hipLaunchKernelGGL(extent_finish, dim3(1), dim3(SG_THREADS), 0, ctx->stream, records + 1, parts, records);
   BGNN_HIP_CHECK(hipGetLastError());

@@ -1,12 +1,14 @@
 // Robust gridding of a point cloud of soundings (include/bgnn_soundings_robust.h): the accepted soundings are staged, filed by
 // cell, sorted per cell, and the median, the MAD and the kept / rejected rule of every cell are read off the sorted segments.
 //
-//   robust_add          the classification of soundings_add (sounding_grid.hip), but a sounding goes into its own slot of the stage
-//                       as (cell, q), cell = -1 where it is not accepted: one 8-byte store, no atomics but the four counters.
+//   sounding_pass<UniformAddress, StageSink>
+//                       the cloud pass of sounding_pass.h under the address rule of sounding_grid.hip, but a sounding goes into its
+//                       own slot of the stage as (cell, q), cell = -1 where it is not accepted: one 8-byte store, no atomics but
+//                       the four counters.
 //   robust_count        one integer atomic per accepted slot into the count of its cell.
 //   robust_tile_sums    the exclusive scan of the counts over the cells in three launches: the sum of every tile of RB_SCAN_TILE
-//   robust_scan_sums    cells, the scan of those sums by one workgroup, and the scan inside every tile, which writes start[] and
-//   robust_scan_cells   appends every cell with more than ROBUST_WAVE_MAX soundings to the list of long segments.
+//   scan_tile_sums      cells, the scan of those sums by one workgroup (plane_util.h), and the scan inside every tile, which writes
+//   robust_scan_cells   start[] and appends every cell with more than ROBUST_WAVE_MAX soundings to the list of long segments.
 //   robust_scatter      q into sorted_q[start[cell] + cursor], the cursor taken by counting the cell's count back down to zero.
 //   robust_sort_short   a wave takes 64 cells at a time and ranks every segment of 2 .. ROBUST_WAVE_MAX soundings by counting:
 //                       lane i holds s_i and counts the s_j below it (ties by lane), n shuffles for a segment of n.
@@ -18,79 +20,29 @@
 //   robust_stats_short  one thread per cell with up to ROBUST_WAVE_MAX soundings (the empty ones included): the MAD by the merge
 //                       walk of sounding_rank.h, the kept range by two binary searches, the sums over it in a loop.
 //   robust_stats_long   one workgroup per listed cell: thread 0 finds the MAD by bisection and the kept range, all threads sum.
-//   robust_flag         one streaming pass: the sounding's cell, its q, |2q - center2| against limit.
+//   sounding_pass<UniformAddress, FlagSink>
+//                       one streaming pass: the sounding's cell, its q, |2q - center2| against limit.
 //
 // The only arrival order that shows anywhere is that of the cursors and of the list; the sort removes the first, and nothing
 // depends on the second.  Compiled with -ffp-contract=off.
 #include "bgnn_internal.h"
-#include "plane_util.h"
-#include "sounding_cell.h"
-#include "sounding_file.h"
+#include "sounding_args.h"
 #include "sounding_moments.h"
+#include "sounding_pass.h"
 #include "sounding_rank.h"
-#include "../../include/bgnn_soundings.h"
-#include "../../include/bgnn_soundings_robust.h"
 
 namespace bgnn {
 
 constexpr int RB_THREADS = BLOCK_THREADS;
 constexpr int RB_WAVES = RB_THREADS / 64;
-constexpr int RB_ITEMS = 4;                           // soundings per thread and step of robust_add and robust_flag
-constexpr int RB_TILE = RB_THREADS * RB_ITEMS;
 constexpr int RB_SCAN_ITEMS = 16;                     // consecutive cells per thread of the scan
 constexpr int RB_SCAN_TILE = RB_THREADS * RB_SCAN_ITEMS;
 constexpr int RB_LONG_GRID = 1024;                    // workgroups that walk the list of long segments
 constexpr int RB_CELL_MAX_GRID = 1 << 16;
 constexpr int ROBUST_WAVE_MAX = BGNN_ROBUST_WAVE_MAX;
 constexpr int ROBUST_LDS_MAX = BGNN_ROBUST_LDS_MAX;
-constexpr int64_t RB_MAX_DIM = 2147483647;
 static_assert(ROBUST_WAVE_MAX == 64, "robust_sort_short ranks one sounding per lane");
 static_assert((ROBUST_LDS_MAX & (ROBUST_LDS_MAX - 1)) == 0 && ROBUST_LDS_MAX >= 2 * RB_THREADS, "the bitonic network pads to a power of two");
-
-// 0 accepted, 1 nonfinite, 2 outside, 3 out of range: the order of bgnn_soundings.h (sounding_file.h)
-__device__ __forceinline__ int rb_classify(double x, double y, float z, double x0, double y0, double res, int64_t height,
-                                           int64_t width, int64_t *cell) {
-  *cell = sounding_cell(x, y, x0, y0, res, height, width);
-  return sounding_kind(x, y, z, *cell >= 0, true);
-}
-
-__global__ __launch_bounds__(RB_THREADS) void robust_add(const double *__restrict__ xs, const double *__restrict__ ys,
-                                                         const float *__restrict__ zs, int64_t n, double x0, double y0, double res,
-                                                         int64_t height, int64_t width, char *__restrict__ stage, int64_t offered) {
-  __shared__ uint32_t scratch[RB_THREADS];
-  int2 *slots = reinterpret_cast<int2 *>(stage + BGNN_ROBUST_STAGE_HEADER_BYTES) + offered;
-  const int t = threadIdx.x;
-  uint32_t tally[4] = {0, 0, 0, 0};                   // (a workgroup sees fewer than 2^31 soundings)
-  for (int64_t base = (int64_t)blockIdx.x * RB_TILE; base < n; base += (int64_t)gridDim.x * RB_TILE) {
-    double x[RB_ITEMS], y[RB_ITEMS];
-    float z[RB_ITEMS];
-#pragma unroll
-    for (int k = 0; k < RB_ITEMS; ++k) {
-      const int64_t i = base + k * RB_THREADS + t;
-      const bool in = i < n;
-      x[k] = in ? xs[i] : 0.0;
-      y[k] = in ? ys[i] : 0.0;
-      z[k] = in ? zs[i] : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < RB_ITEMS; ++k) {
-      const int64_t i = base + k * RB_THREADS + t;
-      if (i >= n) continue;
-      int64_t cell;
-      const int kind = rb_classify(x[k], y[k], z[k], x0, y0, res, height, width, &cell);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tally[j] += kind == j;
-      const long long q = kind == 0 ? llrint((double)z[k] * (double)BGNN_SOUNDINGS_SCALE) : 0;      // |q| < 2^31
-      slots[i] = make_int2(kind == 0 ? (int)cell : -1, (int)q);
-    }
-  }
-  unsigned long long *counters = reinterpret_cast<unsigned long long *>(stage);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t total = block_reduce(tally[j], scratch, SumOp());
-    if (t == 0 && total) atomicAdd(counters + j, (unsigned long long)total);
-  }
-}
 
 __global__ __launch_bounds__(RB_THREADS) void robust_count(const int2 *__restrict__ slots, int64_t offered, uint32_t n_cells,
                                                            uint32_t *__restrict__ cnt) {
@@ -109,29 +61,6 @@ __global__ __launch_bounds__(RB_THREADS) void robust_scatter(const int2 *__restr
   }
 }
 
-// The exclusive scan of one value per thread over the workgroup; *total: the sum.  scratch: RB_WAVES words of LDS, free again on return.
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *scratch, uint32_t *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t up = __shfl_up(incl, o);
-    if (lane >= o) incl += up;
-  }
-  __syncthreads();
-  if (lane == 63) scratch[wave] = incl;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < RB_WAVES; ++w) {
-    const uint32_t c = scratch[w];
-    before += w < wave ? c : 0;
-    all += c;
-  }
-  *total = all;
-  return before + incl - v;
-}
-
 __global__ __launch_bounds__(RB_THREADS) void robust_tile_sums(const uint32_t *__restrict__ cnt, int64_t n_cells, int64_t n_tiles,
                                                                uint32_t *__restrict__ sums) {
   __shared__ uint32_t scratch[RB_THREADS];
@@ -146,21 +75,6 @@ __global__ __launch_bounds__(RB_THREADS) void robust_tile_sums(const uint32_t *_
     const uint32_t total = block_reduce(v, scratch, SumOp());
     if (threadIdx.x == 0) sums[tile] = total;
   }
-}
-
-// one workgroup: sums[] becomes its own exclusive scan; the total (the accepted soundings) goes to *last = start[n_cells]
-__global__ __launch_bounds__(RB_THREADS) void robust_scan_sums(uint32_t *__restrict__ sums, int64_t n_tiles, uint32_t *__restrict__ last) {
-  __shared__ uint32_t scratch[RB_WAVES];
-  uint32_t running = 0;
-  for (int64_t base = 0; base < n_tiles; base += RB_THREADS) {
-    const int64_t i = base + threadIdx.x;
-    const uint32_t v = i < n_tiles ? sums[i] : 0u;
-    uint32_t total;
-    const uint32_t before = block_exclusive_scan(v, scratch, &total);
-    if (i < n_tiles) sums[i] = running + before;
-    running += total;
-  }
-  if (threadIdx.x == 0) *last = running;
 }
 
 __global__ __launch_bounds__(RB_THREADS) void robust_scan_cells(const uint32_t *__restrict__ cnt, int64_t n_cells, int64_t n_tiles,
@@ -402,35 +316,7 @@ __global__ __launch_bounds__(RB_THREADS) void robust_stats_long(const uint32_t *
   }
 }
 
-__global__ __launch_bounds__(RB_THREADS) void robust_flag(const double *__restrict__ xs, const double *__restrict__ ys,
-                                                          const float *__restrict__ zs, int64_t n, double x0, double y0, double res,
-                                                          int64_t height, int64_t width, const int64_t *__restrict__ center2,
-                                                          const int64_t *__restrict__ limit, uint8_t *__restrict__ flags) {
-  for (int64_t base = (int64_t)blockIdx.x * RB_TILE; base < n; base += (int64_t)gridDim.x * RB_TILE) {
-#pragma unroll
-    for (int j = 0; j < RB_ITEMS; ++j) {
-      const int64_t i = base + j * RB_THREADS + threadIdx.x;
-      if (i >= n) continue;
-      const float z = zs[i];
-      int64_t cell;
-      uint8_t f = BGNN_ROBUST_FLAG_NOT_ACCEPTED;
-      if (rb_classify(xs[i], ys[i], z, x0, y0, res, height, width, &cell) == 0) {
-        const long long q = llrint((double)z * (double)BGNN_SOUNDINGS_SCALE);
-        const int64_t d = 2 * (int64_t)q - center2[cell];
-        f = (d < 0 ? -d : d) > limit[cell] ? BGNN_ROBUST_FLAG_REJECTED : BGNN_ROBUST_FLAG_KEPT;     // (limit -1: an empty cell)
-      }
-      flags[i] = f;
-    }
-  }
-}
-
 // ---- the host side --------------------------------------------------------------------------------------------------------------------
-
-static inline bool rb_dim_ok(int64_t v) { return v >= 1 && v <= RB_MAX_DIM; }
-static inline bool rb_capacity_ok(int64_t v) { return v >= 1 && v <= (int64_t)BGNN_ROBUST_MAX_CAPACITY; }
-static inline bool rb_cells_ok(int64_t height, int64_t width) { return height <= (int64_t)BGNN_ROBUST_MAX_CELLS / width; }
-static inline bool rb_aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
-static inline bool rb_finite(double v) { return v - v == 0.0; }
 
 // the workspace of finalize: every part a multiple of 256 bytes
 struct RobustWorkspace {
@@ -454,33 +340,20 @@ static RobustWorkspace rb_workspace(int64_t n_cells, int64_t capacity) {
 using namespace bgnn;
 
 extern "C" size_t bgnn_soundings_robust_stage_bytes(int64_t capacity) {
-  if (!rb_capacity_ok(capacity)) return 0;
+  if (!stage_capacity_ok(capacity)) return 0;
   const unsigned __int128 bytes = (unsigned __int128)capacity * BGNN_ROBUST_SLOT_BYTES + BGNN_ROBUST_STAGE_HEADER_BYTES;
   return bytes > (unsigned __int128)SIZE_MAX ? 0 : (size_t)bytes;
 }
 
 extern "C" size_t bgnn_soundings_robust_workspace_bytes(int64_t height, int64_t width, int64_t capacity) {
-  if (!rb_dim_ok(height) || !rb_dim_ok(width) || !rb_cells_ok(height, width) || !rb_capacity_ok(capacity)) return 0;
+  if (!dim_ok(height) || !dim_ok(width) || !cells_ok(height, width, BGNN_ROBUST_MAX_CELLS) || !stage_capacity_ok(capacity)) return 0;
   if (sizeof(size_t) < 8) return 0;                    // (fewer than 2^31 cells and soundings of 4 bytes each: 64 bits hold it all)
   return rb_workspace(height * width, capacity).bytes;
 }
 
-#define RB_REQUIRE_GRID(fn)                                                                                                  \
-  BGNN_REQUIRE(rb_dim_ok(height) && rb_dim_ok(width), fn ": a grid of %lld x %lld cells, 1 .. 2147483647 each way expected", \
-               (long long)height, (long long)width);                                                                         \
-  if (!rb_cells_ok(height, width)) {                                                                                         \
-    set_error(fn ": a grid of %lld x %lld cells: more than %lld in all, a cell would not fit the int32 of the stage",        \
-              (long long)height, (long long)width, (long long)BGNN_ROBUST_MAX_CELLS);                                        \
-    return BGNN_ERR_UNSUPPORTED;                                                                                             \
-  }
-
-#define RB_REQUIRE_CAPACITY(fn)                                                                                         \
-  BGNN_REQUIRE(rb_capacity_ok(capacity), fn ": a capacity of %lld soundings, 1 .. %lld expected", (long long)capacity, \
-               (long long)BGNN_ROBUST_MAX_CAPACITY)
-
 extern "C" int bgnn_soundings_robust_reset(bgnn_ctx *ctx, void *stage) {
   BGNN_REQUIRE(stage, "bgnn_soundings_robust_reset: NULL argument");
-  BGNN_REQUIRE(rb_aligned8(stage), "bgnn_soundings_robust_reset: the stage is not 8-byte aligned");
+  BGNN_REQUIRE(aligned8(stage), "bgnn_soundings_robust_reset: the stage is not 8-byte aligned");
   BGNN_REQUIRE(ctx, "bgnn_soundings_robust_reset: NULL context");
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
   BGNN_HIP_CHECK(hipMemsetAsync(stage, 0, BGNN_ROBUST_STAGE_HEADER_BYTES, ctx->stream));
@@ -490,24 +363,14 @@ extern "C" int bgnn_soundings_robust_reset(bgnn_ctx *ctx, void *stage) {
 extern "C" int bgnn_soundings_robust_add(bgnn_ctx *ctx, const double *x, const double *y, const float *z, int64_t n, double x0, double y0,
                                          double res, int64_t height, int64_t width, int64_t offered, int64_t capacity, void *stage) {
   // (the context last: what is wrong with the other arguments is reported whatever the context)
-  BGNN_REQUIRE(n >= 0, "bgnn_soundings_robust_add: %lld soundings", (long long)n);
-  BGNN_REQUIRE(stage && (n == 0 || (x && y && z)), "bgnn_soundings_robust_add: NULL argument");
-  BGNN_REQUIRE(rb_finite(res) && res > 0.0, "bgnn_soundings_robust_add: a resolution of %g, a finite number above 0 expected", res);
-  BGNN_REQUIRE(rb_finite(x0) && rb_finite(y0), "bgnn_soundings_robust_add: the origin (%g, %g) is not finite", x0, y0);
-  RB_REQUIRE_GRID("bgnn_soundings_robust_add");
-  RB_REQUIRE_CAPACITY("bgnn_soundings_robust_add");
-  BGNN_REQUIRE(offered >= 0, "bgnn_soundings_robust_add: %lld soundings offered before", (long long)offered);
-  BGNN_REQUIRE(n <= capacity && offered <= capacity - n,
-               "bgnn_soundings_robust_add: %lld soundings after %lld offered before: more than the capacity of %lld", (long long)n,
-               (long long)offered, (long long)capacity);
-  BGNN_REQUIRE(rb_aligned8(stage), "bgnn_soundings_robust_add: the stage is not 8-byte aligned");
-  BGNN_REQUIRE(ctx, "bgnn_soundings_robust_add: NULL context");
-  if (n == 0) return BGNN_OK;
-  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
-  const dim3 g(capped_grid((n + RB_TILE - 1) / RB_TILE, PLANE_MAX_GRID)), b(RB_THREADS);
-  hipLaunchKernelGGL(robust_add, g, b, 0, ctx->stream, x, y, z, n, x0, y0, res, height, width, static_cast<char *>(stage), offered);
-  BGNN_HIP_CHECK(hipGetLastError());
-  return BGNN_OK;
+  const char *fn = "bgnn_soundings_robust_add";
+  BGNN_TRY(require_cloud(fn, x, y, z, n, res, x0, y0, "resolution", stage != nullptr));
+  BGNN_TRY(require_robust_grid(fn, height, width));
+  BGNN_TRY(require_capacity(fn, capacity));
+  BGNN_TRY(require_offered_capacity(fn, n, offered, capacity));
+  BGNN_REQUIRE(aligned8(stage), "%s: the stage is not 8-byte aligned", fn);
+  return launch_sounding_pass(fn, ctx, x, y, z, n, UniformAddress{x0, y0, res, height, width},
+                              StageSink{static_cast<char *>(stage), offered});
 }
 
 extern "C" int bgnn_soundings_robust_finalize(bgnn_ctx *ctx, const void *stage, int64_t offered, int64_t capacity, int64_t height,
@@ -518,20 +381,20 @@ extern "C" int bgnn_soundings_robust_finalize(bgnn_ctx *ctx, const void *stage, 
   BGNN_REQUIRE(stage && workspace && start && sorted_q && count && kept && median && mad && kept_mean && kept_std && kept_min &&
                    kept_max && valid && center2 && limit,
                "bgnn_soundings_robust_finalize: NULL argument");
-  RB_REQUIRE_GRID("bgnn_soundings_robust_finalize");
-  RB_REQUIRE_CAPACITY("bgnn_soundings_robust_finalize");
+  BGNN_TRY(require_robust_grid("bgnn_soundings_robust_finalize", height, width));
+  BGNN_TRY(require_capacity("bgnn_soundings_robust_finalize", capacity));
   BGNN_REQUIRE(offered >= 0 && offered <= capacity, "bgnn_soundings_robust_finalize: %lld soundings offered, 0 .. the capacity of %lld expected",
                (long long)offered, (long long)capacity);
-  BGNN_REQUIRE(rb_finite(k) && k >= 1.0, "bgnn_soundings_robust_finalize: a multiplier k of %g, a finite number of at least 1 expected", k);
-  BGNN_REQUIRE(rb_finite(floor_m) && floor_m >= 0.0, "bgnn_soundings_robust_finalize: a floor of %g m, a finite number of at least 0 expected",
+  BGNN_REQUIRE(finite_arg(k) && k >= 1.0, "bgnn_soundings_robust_finalize: a multiplier k of %g, a finite number of at least 1 expected", k);
+  BGNN_REQUIRE(finite_arg(floor_m) && floor_m >= 0.0, "bgnn_soundings_robust_finalize: a floor of %g m, a finite number of at least 0 expected",
                floor_m);
   BGNN_REQUIRE(min_count >= 1, "bgnn_soundings_robust_finalize: a min_count of %d, at least 1 expected", (int)min_count);
   const int64_t n_cells = height * width;
   const RobustWorkspace w = rb_workspace(n_cells, capacity);
   BGNN_REQUIRE(workspace_bytes >= w.bytes, "bgnn_soundings_robust_finalize: a workspace of %zu bytes, %zu expected", workspace_bytes, w.bytes);
-  BGNN_REQUIRE(rb_aligned8(stage), "bgnn_soundings_robust_finalize: the stage is not 8-byte aligned");
-  BGNN_REQUIRE(rb_aligned8(workspace), "bgnn_soundings_robust_finalize: the workspace is not 8-byte aligned");
-  BGNN_REQUIRE(rb_aligned8(center2) && rb_aligned8(limit), "bgnn_soundings_robust_finalize: center2 or limit is not 8-byte aligned");
+  BGNN_REQUIRE(aligned8(stage), "bgnn_soundings_robust_finalize: the stage is not 8-byte aligned");
+  BGNN_REQUIRE(aligned8(workspace), "bgnn_soundings_robust_finalize: the workspace is not 8-byte aligned");
+  BGNN_REQUIRE(aligned8(center2) && aligned8(limit), "bgnn_soundings_robust_finalize: center2 or limit is not 8-byte aligned");
   BGNN_REQUIRE(ctx, "bgnn_soundings_robust_finalize: NULL context");
   BGNN_HIP_CHECK(hipSetDevice(ctx->device));
   char *ws = static_cast<char *>(workspace);
@@ -547,7 +410,7 @@ extern "C" int bgnn_soundings_robust_finalize(bgnn_ctx *ctx, const void *stage, 
   BGNN_HIP_CHECK(hipMemsetAsync(ws, 0, w.list, ctx->stream));                                     // the counts, the sums, the list's length
   if (offered > 0) hipLaunchKernelGGL(robust_count, g_slots, b, 0, ctx->stream, slots, offered, (uint32_t)n_cells, cnt);
   hipLaunchKernelGGL(robust_tile_sums, g_tiles, b, 0, ctx->stream, cnt, n_cells, w.n_tiles, sums);
-  hipLaunchKernelGGL(robust_scan_sums, dim3(1), b, 0, ctx->stream, sums, w.n_tiles, start + n_cells);
+  hipLaunchKernelGGL((scan_tile_sums<uint32_t, uint32_t>), dim3(1), b, 0, ctx->stream, sums, w.n_tiles, start + n_cells);      // (the accepted)
   hipLaunchKernelGGL(robust_scan_cells, g_tiles, b, 0, ctx->stream, cnt, n_cells, w.n_tiles, sums, start, list_count, list);
   if (offered > 0) {
     hipLaunchKernelGGL(robust_scatter, g_slots, b, 0, ctx->stream, slots, offered, (uint32_t)n_cells, start, cnt, sorted_q);
@@ -565,17 +428,9 @@ extern "C" int bgnn_soundings_robust_finalize(bgnn_ctx *ctx, const void *stage, 
 extern "C" int bgnn_soundings_robust_flag(bgnn_ctx *ctx, const double *x, const double *y, const float *z, int64_t n, double x0, double y0,
                                           double res, int64_t height, int64_t width, const int64_t *center2, const int64_t *limit,
                                           uint8_t *flags) {
-  BGNN_REQUIRE(n >= 0, "bgnn_soundings_robust_flag: %lld soundings", (long long)n);
-  BGNN_REQUIRE(center2 && limit && (n == 0 || (x && y && z && flags)), "bgnn_soundings_robust_flag: NULL argument");
-  BGNN_REQUIRE(rb_finite(res) && res > 0.0, "bgnn_soundings_robust_flag: a resolution of %g, a finite number above 0 expected", res);
-  BGNN_REQUIRE(rb_finite(x0) && rb_finite(y0), "bgnn_soundings_robust_flag: the origin (%g, %g) is not finite", x0, y0);
-  RB_REQUIRE_GRID("bgnn_soundings_robust_flag");
-  BGNN_REQUIRE(rb_aligned8(center2) && rb_aligned8(limit), "bgnn_soundings_robust_flag: center2 or limit is not 8-byte aligned");
-  BGNN_REQUIRE(ctx, "bgnn_soundings_robust_flag: NULL context");
-  if (n == 0) return BGNN_OK;
-  BGNN_HIP_CHECK(hipSetDevice(ctx->device));
-  const dim3 g(capped_grid((n + RB_TILE - 1) / RB_TILE, PLANE_MAX_GRID)), b(RB_THREADS);
-  hipLaunchKernelGGL(robust_flag, g, b, 0, ctx->stream, x, y, z, n, x0, y0, res, height, width, center2, limit, flags);
-  BGNN_HIP_CHECK(hipGetLastError());
-  return BGNN_OK;
+  const char *fn = "bgnn_soundings_robust_flag";
+  BGNN_TRY(require_cloud(fn, x, y, z, n, res, x0, y0, "resolution", center2 && limit && (n == 0 || flags)));
+  BGNN_TRY(require_robust_grid(fn, height, width));
+  BGNN_REQUIRE(aligned8(center2) && aligned8(limit), "%s: center2 or limit is not 8-byte aligned", fn);
+  return launch_sounding_pass(fn, ctx, x, y, z, n, UniformAddress{x0, y0, res, height, width}, FlagSink{center2, limit, flags});
 }

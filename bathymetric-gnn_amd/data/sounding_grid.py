@@ -88,6 +88,144 @@ def _feed(x, y, z, device, add_device):
         add_device(*(as_tensor(a[lo:hi]).to(device) for a in (x, y, z)))
 
 
+def _check_shape(shape, what: str = "shape") -> Tuple[int, int]:
+    shape = (int(shape[0]), int(shape[1]))
+    if shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"{what} {shape}: at least one row and one column expected")
+    return shape
+
+
+def _check_origin(origin) -> Tuple[float, float]:
+    origin = (float(origin[0]), float(origin[1]))
+    if not all(math.isfinite(v) for v in origin):
+        raise ValueError(f"origin {origin}: finite coordinates expected")
+    return origin
+
+
+def _check_min_count(min_count) -> int:
+    if int(min_count) < 1:
+        raise ValueError(f"min_count {min_count}: at least 1 expected")
+    return int(min_count)
+
+
+def _check_robust_rule(capacity, k, floor_m) -> Tuple[int, float, float]:
+    """The capacity of a stage and the rule of the robust gridders, as ``(int, float, float)``."""
+    if not 1 <= int(capacity) <= rt.ROBUST_MAX_CAPACITY:
+        raise ValueError(f"capacity {capacity}: 1 .. {rt.ROBUST_MAX_CAPACITY} soundings expected")
+    if not (math.isfinite(float(k)) and float(k) >= 1):
+        raise ValueError(f"k {k!r}: a finite number of at least 1 expected")
+    if not (math.isfinite(float(floor_m)) and float(floor_m) >= 0):
+        raise ValueError(f"floor_m {floor_m!r}: a finite number of at least 0 expected")
+    return int(capacity), float(k), float(floor_m)
+
+
+def _pick_plane(result, name: str, allowed, what: str) -> torch.Tensor:
+    """The plane ``name`` of a finalize result, one of ``allowed``; ``what``: the argument the name came in."""
+    if name not in allowed:
+        raise ValueError(f"{what}={name!r}: one of {allowed} expected")
+    return getattr(result, name)
+
+
+def _call(ctx, fn: str, *args):
+    ctx.begin()
+    rt.check(getattr(ctx.lib, fn)(ctx.handle, *args))
+    ctx.end()
+
+
+class _OfferedSoundings:
+    """Something that is offered soundings over many ``add`` calls, on ``self.device`` under ``self._ctx``: ``offered`` so far, of
+    at most ``self.capacity`` where the class has one and ``MAX_TOTAL`` otherwise.  A subclass hands one set of device tensors on
+    in ``_offer(x, y, z, n)``."""
+    offered = 0
+    capacity = None
+
+    def _call(self, fn: str, *args):
+        _call(self._ctx, fn, *args)
+
+    def _add_device(self, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor):
+        n = int(x.shape[0])
+        self._offer(*_on_device(x, y, z, self.device), n)
+        self.offered += n
+
+    def add(self, x, y, z):
+        """Offer one set of soundings (``ValueError`` beyond the limit, before anything is launched).  No host wait for device
+        tensors."""
+        _check_coordinates(x, y, z)
+        n = int(x.shape[0])
+        limit, what = (MAX_TOTAL, f"a total above {MAX_TOTAL}") if self.capacity is None else \
+            (self.capacity, f"more than the capacity of {self.capacity}")
+        if self.offered + n > limit:
+            raise ValueError(f"{n} soundings after {self.offered} offered before: {what}")
+        _feed(x, y, z, self.device, self._add_device)
+
+
+class _GridderBase(_OfferedSoundings):
+    """A gridder: ``self._buffer`` is its state or stage with the four counters in front, ``self._reset_call`` the arguments of
+    ``_call`` that empty it; ``self._unrefined``, where the gridder has one, is the fifth counter."""
+    _unrefined = None
+
+    def reset(self):
+        self._call(*self._reset_call)
+        if self._unrefined is not None:
+            self._unrefined.zero_()
+        self.offered = 0
+
+    def counters(self) -> Dict[str, int]:
+        """``accepted``, ``nonfinite``, ``outside``, ``out_of_range`` (and ``unrefined`` on a VR layout) over everything added:
+        one small copy to the host."""
+        assert rt.ROBUST_STAGE_HEADER_BYTES == rt.SOUNDINGS_HEADER_BYTES        # a state and a stage begin alike
+        head = self._buffer[:rt.SOUNDINGS_HEADER_BYTES // 8]
+        if self._unrefined is None:
+            return {name: int(v) for name, v in zip(rt.SOUNDINGS_COUNTERS, head.cpu().numpy())}
+        return {name: int(v) for name, v in zip(rt.VR_SOUNDINGS_COUNTERS, torch.cat([head, self._unrefined]).cpu().numpy())}
+
+
+def _new_state(ctx, height: int, width: int, device) -> torch.Tensor:
+    """An empty state of ``bgnn_soundings_add`` (all zero), or ``None`` where there is none of that size."""
+    nbytes = int(ctx.lib.bgnn_soundings_state_bytes(height, width))
+    assert nbytes in (0, rt.SOUNDINGS_HEADER_BYTES + CELL_BYTES * height * width)
+    return torch.zeros(nbytes // 8, dtype=torch.int64, device=device) if nbytes else None
+
+
+def _new_stage(ctx, capacity: int, device) -> torch.Tensor:
+    """An empty stage of ``bgnn_soundings_robust_add``: an all-zero header in front of ``capacity`` slots."""
+    nbytes = int(ctx.lib.bgnn_soundings_robust_stage_bytes(capacity))
+    assert nbytes == rt.ROBUST_STAGE_HEADER_BYTES + rt.ROBUST_SLOT_BYTES * capacity
+    stage = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+    stage[:rt.ROBUST_STAGE_HEADER_BYTES // 8].zero_()
+    return stage
+
+
+def _finalize_plain(ctx, state, height, width, shape, min_count, nodata) -> Dict[str, torch.Tensor]:
+    """``bgnn_soundings_finalize`` on a ``height x width`` state: the six planes, each of ``shape``.  Reads the state only."""
+    dev = state.device
+    p = {name: torch.empty(shape, dtype=dtype, device=dev) for name, dtype in (
+        ("count", torch.int32), ("valid", torch.uint8), ("mean", torch.float32), ("std", torch.float32), ("min", torch.float32),
+        ("max", torch.float32))}
+    _call(ctx, "bgnn_soundings_finalize", rt.ptr(state), height, width, min_count, nodata,
+          *(rt.ptr(p[name]) for name in ("count", "mean", "std", "min", "max", "valid")))
+    return p
+
+
+def _finalize_robust(ctx, stage, offered, capacity, height, width, shape, k, floor_m, min_count, nodata) -> Dict[str, torch.Tensor]:
+    """``bgnn_soundings_robust_finalize`` on a stage of ``height x width`` cells: the eleven planes, each of ``shape`` (a tuple, or
+    the number of records of a flat result), ``sorted_q`` and ``start``.  Reads the stage only."""
+    dev, cells = stage.device, height * width
+    ws_bytes = int(ctx.lib.bgnn_soundings_robust_workspace_bytes(height, width, capacity))
+    if ws_bytes == 0:
+        what = f"shape {shape}" if isinstance(shape, tuple) else f"{shape} records"
+        raise ValueError(f"{what}, capacity {capacity}: no workspace of that size")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    out = {"start": torch.empty(cells + 1, dtype=torch.int32, device=dev), "sorted_q": torch.empty(capacity, dtype=torch.int32, device=dev)}
+    out.update((name, torch.empty(shape, dtype=dtype, device=dev)) for name, dtype in (
+        ("count", torch.int32), ("kept", torch.int32), ("median", torch.float32), ("mad", torch.float32), ("kept_mean", torch.float32),
+        ("kept_std", torch.float32), ("kept_min", torch.float32), ("kept_max", torch.float32), ("valid", torch.uint8),
+        ("center2", torch.int64), ("limit", torch.int64)))
+    _call(ctx, "bgnn_soundings_robust_finalize", rt.ptr(stage), offered, capacity, height, width, k, floor_m, min_count, nodata, rt.ptr(ws),
+          ws_bytes, *(rt.ptr(t) for t in out.values()))       # (the workspace may go: the caller's stream waits)
+    return out
+
+
 def sounding_extent(x: torch.Tensor, y: torch.Tensor) -> Dict[str, float]:
     """``bgnn_soundings_extent`` on device tensors: the float64 ``min_x``, ``max_x``, ``min_y``, ``max_y`` over the finite values of
     each coordinate and their counts ``finite_x``, ``finite_y`` (+inf / -inf / 0 where none is finite).  One small copy to the host."""
@@ -165,11 +303,6 @@ class SoundingGrid:
     nodata_value: float = 1.0e6
     min_count: int = 1
 
-    def _depth(self, depth: str) -> torch.Tensor:
-        if depth not in DEPTH_PLANES:
-            raise ValueError(f"depth={depth!r}: one of {DEPTH_PLANES} expected")
-        return getattr(self, depth)
-
     def density_plane(self) -> torch.Tensor:
         """``density_from_count(count)``: the node plane "sounding_density"."""
         return density_from_count(self.count)
@@ -179,92 +312,48 @@ class SoundingGrid:
         (``"mean"``, the shoalest ``"min"`` or the deepest ``"max"`` of the raw z), the valid plane and ``std`` as uncertainty.
         ``density=True``: ``density_plane()`` as a fourth element (``process_survey_device(..., density_t=...)``)."""
         if density:
-            return self._depth(depth), self.valid, self.std, self.density_plane()
-        return self._depth(depth), self.valid, self.std
+            return _pick_plane(self, depth, DEPTH_PLANES, "depth"), self.valid, self.std, self.density_plane()
+        return _pick_plane(self, depth, DEPTH_PLANES, "depth"), self.valid, self.std
 
     def to_grid(self, depth: str = "mean") -> BathymetricGrid:
         """A host ``BathymetricGrid``: the chosen surface, ``std`` as uncertainty, ``density_plane()`` as density, the nodata
         value, transform, resolution and bounds ``(min_x, min_y, max_x, max_y)``."""
         height, width = (int(v) for v in self.count.shape)
         x0, res, _, y0, _, _ = self.transform
-        return BathymetricGrid(depth=self._depth(depth).cpu().numpy(), uncertainty=self.std.cpu().numpy(),
+        return BathymetricGrid(depth=_pick_plane(self, depth, DEPTH_PLANES, "depth").cpu().numpy(), uncertainty=self.std.cpu().numpy(),
                                nodata_value=self.nodata_value, transform=self.transform, resolution=self.resolution,
                                bounds=(x0, y0 - height * res, x0 + width * res, y0), density=self.density_plane().cpu().numpy())
 
 
-class SoundingGridder:
+class SoundingGridder(_GridderBase):
     """``add(x, y, z)`` as often as the survey has line files, then ``finalize()``; more may be added after a ``finalize``.
     ``shape = (H, W)``, ``origin = (x0, y0)`` the upper-left corner, ``resolution`` the cell size in metres.  Device tensors are
     taken as they lie; host arrays are uploaded ``UPLOAD_CHUNK`` (2^24) soundings at a time.  ``min_count``: the soundings a
     cell needs to be valid.  At most 2^31 - 1 soundings may be offered in all (``ValueError`` beyond, before anything is launched)."""
 
     def __init__(self, shape, origin, resolution, device=None, min_count: int = 1, nodata_value: float = 1.0e6):
-        self.shape = (int(shape[0]), int(shape[1]))
-        self.origin = (float(origin[0]), float(origin[1]))
         self.resolution = _check_resolution(resolution)
-        self.min_count = int(min_count)
+        self.shape = _check_shape(shape)
+        self.min_count = _check_min_count(min_count)
+        self.origin = _check_origin(origin)
         self.nodata_value = float(nodata_value)
-        if self.shape[0] < 1 or self.shape[1] < 1:
-            raise ValueError(f"shape {self.shape}: at least one row and one column expected")
-        if self.min_count < 1:
-            raise ValueError(f"min_count {min_count}: at least 1 expected")
-        if not all(math.isfinite(v) for v in self.origin):
-            raise ValueError(f"origin {self.origin}: finite coordinates expected")
         self.device = rt.resolve_device(device)
         self._ctx = rt.get_context(self.device)
-        nbytes = int(self._ctx.lib.bgnn_soundings_state_bytes(*self.shape))
-        if nbytes == 0:
+        self._state = self._buffer = _new_state(self._ctx, *self.shape, self.device)
+        if self._state is None:
             raise ValueError(f"shape {self.shape}: no state of that size")
-        assert nbytes == rt.SOUNDINGS_HEADER_BYTES + CELL_BYTES * self.shape[0] * self.shape[1]
-        self._state = torch.zeros(nbytes // 8, dtype=torch.int64, device=self.device)       # an all-zero state is the empty one
-        self.offered = 0
+        self._reset_call = ("bgnn_soundings_reset", rt.ptr(self._state), *self.shape)
 
-    def reset(self):
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_reset(ctx.handle, rt.ptr(self._state), *self.shape))
-        ctx.end()
-        self.offered = 0
-
-    def _add_device(self, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor):
-        n = int(x.shape[0])
-        x, y, z = _on_device(x, y, z, self.device)
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_add(ctx.handle, rt.ptr(x), rt.ptr(y), rt.ptr(z), n, self.origin[0], self.origin[1],
-                                            self.resolution, self.shape[0], self.shape[1], self.offered, rt.ptr(self._state)))
-        ctx.end()
-        self.offered += n
-
-    def add(self, x, y, z):
-        """File one set of soundings.  No host wait for device tensors."""
-        _check_coordinates(x, y, z)
-        n = int(x.shape[0])
-        if self.offered + n > MAX_TOTAL:
-            raise ValueError(f"{n} soundings after {self.offered} offered before: a total above {MAX_TOTAL}")
-        _feed(x, y, z, self.device, self._add_device)
-
-    def counters(self) -> Dict[str, int]:
-        """``accepted``, ``nonfinite``, ``outside``, ``out_of_range`` over everything added: one 32-byte copy to the host."""
-        head = self._state[:rt.SOUNDINGS_HEADER_BYTES // 8].cpu().numpy()
-        return {name: int(v) for name, v in zip(rt.SOUNDINGS_COUNTERS, head)}
+    def _offer(self, x, y, z, n):
+        self._call("bgnn_soundings_add", rt.ptr(x), rt.ptr(y), rt.ptr(z), n, self.origin[0], self.origin[1], self.resolution,
+                   self.shape[0], self.shape[1], self.offered, rt.ptr(self._state))
 
     def finalize(self) -> SoundingGrid:
         """The planes of everything added so far.  Reads the state only."""
-        ctx, dev = self._ctx, self.device
-        f32 = lambda: torch.empty(self.shape, dtype=torch.float32, device=dev)
-        count = torch.empty(self.shape, dtype=torch.int32, device=dev)
-        valid = torch.empty(self.shape, dtype=torch.uint8, device=dev)
-        mean, std, zmin, zmax = f32(), f32(), f32(), f32()
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_finalize(ctx.handle, rt.ptr(self._state), self.shape[0], self.shape[1], self.min_count,
-                                                 self.nodata_value, rt.ptr(count), rt.ptr(mean), rt.ptr(std), rt.ptr(zmin), rt.ptr(zmax),
-                                                 rt.ptr(valid)))
-        ctx.end()
+        planes = _finalize_plain(self._ctx, self._state, self.shape[0], self.shape[1], self.shape, self.min_count, self.nodata_value)
         res = self.resolution
-        return SoundingGrid(count=count, mean=mean, std=std, min=zmin, max=zmax, valid=valid, counters=self.counters(),
-                            transform=(self.origin[0], res, 0.0, self.origin[1], 0.0, -res), resolution=(res, res),
-                            nodata_value=self.nodata_value, min_count=self.min_count)
+        return SoundingGrid(**planes, counters=self.counters(), transform=(self.origin[0], res, 0.0, self.origin[1], 0.0, -res),
+                            resolution=(res, res), nodata_value=self.nodata_value, min_count=self.min_count)
 
 
 def grid_soundings(x, y, z, resolution, shape=None, origin=None, device=None, min_count: int = 1,

@@ -19,14 +19,14 @@ every run.  Limits: ``H * W <= 2^31 - 1`` cells, ``capacity <= 2^31 - 1`` soundi
 from __future__ import annotations
 
 import dataclasses
-import math
 from typing import Dict, Tuple
 
 import torch
 
 from .. import runtime as rt
 from .grid import BathymetricGrid
-from .sounding_grid import _check_coordinates, _check_resolution, _feed, _on_device, density_from_count, plan_sounding_grid
+from .sounding_grid import (_GridderBase, _check_coordinates, _check_min_count, _check_origin, _check_resolution, _check_robust_rule,
+                            _check_shape, _finalize_robust, _new_stage, _on_device, _pick_plane, density_from_count, plan_sounding_grid)
 
 DEFAULT_K = 3 * 1.4826
 ROBUST_DEPTH_PLANES = ("median", "kept_mean", "kept_min", "kept_max")
@@ -72,11 +72,6 @@ class RobustSoundingGrid:
         lo, hi = (int(v) & 0xFFFFFFFF for v in self.start[cell:cell + 2].tolist())
         return self.sorted_q[lo:hi].to(torch.float64) * (2.0 ** -16)
 
-    def _plane(self, name: str, allowed, what: str) -> torch.Tensor:
-        if name not in allowed:
-            raise ValueError(f"{what}={name!r}: one of {allowed} expected")
-        return getattr(self, name)
-
     def density_plane(self) -> torch.Tensor:
         """``density_from_count(kept)``: the node plane "sounding_density" over the soundings the rule kept."""
         return density_from_count(self.kept)
@@ -84,8 +79,8 @@ class RobustSoundingGrid:
     def survey_tensors(self, depth: str = "median", uncertainty: str = "kept_std", density: bool = False):
         """``(depth_t, valid_t, unc_t)`` as ``BathymetricPipeline.process_survey_device`` takes them; ``density=True``:
         ``density_plane()`` as a fourth element."""
-        t = (self._plane(depth, ROBUST_DEPTH_PLANES, "depth"), self.valid,
-             self._plane(uncertainty, ROBUST_UNCERTAINTY_PLANES, "uncertainty"))
+        t = (_pick_plane(self, depth, ROBUST_DEPTH_PLANES, "depth"), self.valid,
+             _pick_plane(self, uncertainty, ROBUST_UNCERTAINTY_PLANES, "uncertainty"))
         return t + (self.density_plane(),) if density else t
 
     def to_grid(self, depth: str = "median", uncertainty: str = "kept_std") -> BathymetricGrid:
@@ -98,7 +93,7 @@ class RobustSoundingGrid:
                                bounds=(x0, y0 - height * res, x0 + width * res, y0), density=self.density_plane().cpu().numpy())
 
 
-class RobustSoundingGridder:
+class RobustSoundingGridder(_GridderBase):
     """``add(x, y, z)`` as often as the survey has line files, up to ``capacity`` soundings in all (``ValueError`` beyond, before
     anything is launched), then ``finalize()``; more may be added after a ``finalize``.  ``shape``, ``origin``, ``resolution``,
     ``min_count``, ``nodata_value`` as for ``SoundingGridder``; ``k`` (finite, >= 1) and ``floor_m`` (finite, >= 0) set the rule.
@@ -107,92 +102,31 @@ class RobustSoundingGridder:
 
     def __init__(self, shape, origin, resolution, capacity, device=None, k: float = DEFAULT_K, floor_m: float = 0.0,
                  min_count: int = 1, nodata_value: float = 1.0e6):
-        self.shape = (int(shape[0]), int(shape[1]))
-        self.origin = (float(origin[0]), float(origin[1]))
         self.resolution = _check_resolution(resolution)
-        self.capacity = int(capacity)
-        self.k, self.floor_m = float(k), float(floor_m)
-        self.min_count = int(min_count)
-        self.nodata_value = float(nodata_value)
-        if self.shape[0] < 1 or self.shape[1] < 1:
-            raise ValueError(f"shape {self.shape}: at least one row and one column expected")
+        self.shape = _check_shape(shape)
         if self.shape[0] * self.shape[1] > rt.ROBUST_MAX_CELLS:
             raise NotImplementedError(f"shape {self.shape}: more than {rt.ROBUST_MAX_CELLS} cells")
-        if not 1 <= self.capacity <= rt.ROBUST_MAX_CAPACITY:
-            raise ValueError(f"capacity {capacity}: 1 .. {rt.ROBUST_MAX_CAPACITY} soundings expected")
-        if not (math.isfinite(self.k) and self.k >= 1):
-            raise ValueError(f"k {k!r}: a finite number of at least 1 expected")
-        if not (math.isfinite(self.floor_m) and self.floor_m >= 0):
-            raise ValueError(f"floor_m {floor_m!r}: a finite number of at least 0 expected")
-        if self.min_count < 1:
-            raise ValueError(f"min_count {min_count}: at least 1 expected")
-        if not all(math.isfinite(v) for v in self.origin):
-            raise ValueError(f"origin {self.origin}: finite coordinates expected")
+        self.capacity, self.k, self.floor_m = _check_robust_rule(capacity, k, floor_m)
+        self.min_count = _check_min_count(min_count)
+        self.origin = _check_origin(origin)
+        self.nodata_value = float(nodata_value)
         self.device = rt.resolve_device(device)
         self._ctx = rt.get_context(self.device)
-        nbytes = int(self._ctx.lib.bgnn_soundings_robust_stage_bytes(self.capacity))
-        assert nbytes == rt.ROBUST_STAGE_HEADER_BYTES + rt.ROBUST_SLOT_BYTES * self.capacity
-        self._stage = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
-        self._stage[:rt.ROBUST_STAGE_HEADER_BYTES // 8].zero_()                             # an all-zero header is the empty stage
-        self.offered = 0
+        self._stage = self._buffer = _new_stage(self._ctx, self.capacity, self.device)
+        self._reset_call = ("bgnn_soundings_robust_reset", rt.ptr(self._stage))
 
-    def reset(self):
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_robust_reset(ctx.handle, rt.ptr(self._stage)))
-        ctx.end()
-        self.offered = 0
-
-    def _add_device(self, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor):
-        n = int(x.shape[0])
-        x, y, z = _on_device(x, y, z, self.device)
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_robust_add(ctx.handle, rt.ptr(x), rt.ptr(y), rt.ptr(z), n, self.origin[0], self.origin[1],
-                                                   self.resolution, self.shape[0], self.shape[1], self.offered, self.capacity,
-                                                   rt.ptr(self._stage)))
-        ctx.end()
-        self.offered += n
-
-    def add(self, x, y, z):
-        """Stage one set of soundings.  No host wait for device tensors."""
-        _check_coordinates(x, y, z)
-        n = int(x.shape[0])
-        if self.offered + n > self.capacity:
-            raise ValueError(f"{n} soundings after {self.offered} offered before: more than the capacity of {self.capacity}")
-        _feed(x, y, z, self.device, self._add_device)
-
-    def counters(self) -> Dict[str, int]:
-        """``accepted``, ``nonfinite``, ``outside``, ``out_of_range`` over everything added: one 32-byte copy to the host."""
-        head = self._stage[:rt.ROBUST_STAGE_HEADER_BYTES // 8].cpu().numpy()
-        return {name: int(v) for name, v in zip(rt.SOUNDINGS_COUNTERS, head)}
+    def _offer(self, x, y, z, n):
+        self._call("bgnn_soundings_robust_add", rt.ptr(x), rt.ptr(y), rt.ptr(z), n, self.origin[0], self.origin[1], self.resolution,
+                   self.shape[0], self.shape[1], self.offered, self.capacity, rt.ptr(self._stage))
 
     def finalize(self) -> RobustSoundingGrid:
         """The planes and the per-cell sounding lists of everything added so far.  Reads the stage only."""
-        ctx, dev, (height, width) = self._ctx, self.device, self.shape
-        ws_bytes = int(ctx.lib.bgnn_soundings_robust_workspace_bytes(height, width, self.capacity))
-        if ws_bytes == 0:
-            raise ValueError(f"shape {self.shape}, capacity {self.capacity}: no workspace of that size")
-        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
-        new = lambda dtype: torch.empty(self.shape, dtype=dtype, device=dev)
-        start = torch.empty(height * width + 1, dtype=torch.int32, device=dev)
-        sorted_q = torch.empty(self.capacity, dtype=torch.int32, device=dev)
-        count, kept = new(torch.int32), new(torch.int32)
-        median, mad, kept_mean, kept_std, kept_min, kept_max = (new(torch.float32) for _ in range(6))
-        valid, center2, limit = new(torch.uint8), new(torch.int64), new(torch.int64)
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_robust_finalize(
-            ctx.handle, rt.ptr(self._stage), self.offered, self.capacity, height, width, self.k, self.floor_m, self.min_count,
-            self.nodata_value, rt.ptr(ws), ws_bytes, rt.ptr(start), rt.ptr(sorted_q), rt.ptr(count), rt.ptr(kept), rt.ptr(median),
-            rt.ptr(mad), rt.ptr(kept_mean), rt.ptr(kept_std), rt.ptr(kept_min), rt.ptr(kept_max), rt.ptr(valid), rt.ptr(center2),
-            rt.ptr(limit)))
-        ctx.end()                                                                            # (the workspace may go: the caller's stream waits)
+        out = _finalize_robust(self._ctx, self._stage, self.offered, self.capacity, self.shape[0], self.shape[1], self.shape, self.k,
+                               self.floor_m, self.min_count, self.nodata_value)
         res = self.resolution
-        return RobustSoundingGrid(count=count, kept=kept, median=median, mad=mad, kept_mean=kept_mean, kept_std=kept_std,
-                                  kept_min=kept_min, kept_max=kept_max, valid=valid, center2=center2, limit=limit,
-                                  sorted_q=sorted_q, start=start, counters=self.counters(),
-                                  transform=(self.origin[0], res, 0.0, self.origin[1], 0.0, -res), resolution=(res, res),
-                                  nodata_value=self.nodata_value, min_count=self.min_count, k=self.k, floor_m=self.floor_m)
+        return RobustSoundingGrid(**out, counters=self.counters(), transform=(self.origin[0], res, 0.0, self.origin[1], 0.0, -res),
+                                  resolution=(res, res), nodata_value=self.nodata_value, min_count=self.min_count, k=self.k,
+                                  floor_m=self.floor_m)
 
     def flag(self, x, y, z, grid: RobustSoundingGrid) -> torch.Tensor:
         """One uint8 per sounding under the rule of ``grid`` (a ``finalize`` of this gridder's geometry): 0 kept, 1 accepted but
@@ -206,12 +140,8 @@ class RobustSoundingGridder:
         x, y, z = _on_device(x, y, z, self.device)
         n = int(x.shape[0])
         flags = torch.empty(n, dtype=torch.uint8, device=self.device)
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_robust_flag(ctx.handle, rt.ptr(x), rt.ptr(y), rt.ptr(z), n, self.origin[0], self.origin[1],
-                                                    self.resolution, self.shape[0], self.shape[1], rt.ptr(grid.center2),
-                                                    rt.ptr(grid.limit), rt.ptr(flags)))
-        ctx.end()
+        self._call("bgnn_soundings_robust_flag", rt.ptr(x), rt.ptr(y), rt.ptr(z), n, self.origin[0], self.origin[1], self.resolution,
+                   self.shape[0], self.shape[1], rt.ptr(grid.center2), rt.ptr(grid.limit), rt.ptr(flags))
         return flags
 
 

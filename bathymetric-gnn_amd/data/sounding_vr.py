@@ -29,8 +29,9 @@ import numpy as np
 import torch
 
 from .. import runtime as rt
-from .sounding_grid import (DEPTH_PLANES, MAX_TOTAL, _check_coordinates, _check_resolution, _feed, _on_device, density_from_count,
-                            sounding_extent)
+from .sounding_grid import (DEPTH_PLANES, _GridderBase, _OfferedSoundings, _check_coordinates, _check_min_count, _check_origin,
+                            _check_resolution, _check_robust_rule, _check_shape, _finalize_plain, _finalize_robust, _new_stage,
+                            _new_state, _on_device, _pick_plane, density_from_count, sounding_extent)
 from .sounding_robust import DEFAULT_K, ROBUST_DEPTH_PLANES, ROBUST_UNCERTAINTY_PLANES
 from .vr_bag import VARRES_METADATA_DTYPE, VARRES_REFINEMENT_DTYPE, VRBagHandler
 
@@ -41,16 +42,11 @@ UNCERTAINTY_PLANES = ("std",)
 
 
 def _check_base(base_shape, origin, base_resolution):
-    shape = (int(base_shape[0]), int(base_shape[1]))
-    org = (float(origin[0]), float(origin[1]))
+    shape = _check_shape(base_shape, "base shape")
     res = _check_resolution(base_resolution)
-    if shape[0] < 1 or shape[1] < 1:
-        raise ValueError(f"base shape {shape}: at least one row and one column expected")
     if shape[0] * shape[1] > rt.VR_MAX_BASE_CELLS:
         raise NotImplementedError(f"base shape {shape}: more than {rt.VR_MAX_BASE_CELLS} base cells")
-    if not all(math.isfinite(v) for v in org):
-        raise ValueError(f"origin {org}: finite coordinates expected")
-    return shape, org, res
+    return shape, _check_origin(origin), res
 
 
 def _check_ladder(ladder) -> Tuple[int, ...]:
@@ -156,7 +152,7 @@ class VRLayout:
         return int(self.index[base_row, base_col]), dy, dx
 
 
-class VRLayoutPlanner:
+class VRLayoutPlanner(_OfferedSoundings):
     """``add(x, y, z)`` as often as the survey has line files (the density pass: a count per base cell of the soundings that are
     finite, on the base grid and in range), then ``plan(...)``.  The density is a pass of its own under the base-cell arithmetic
     of the add pass: the plan sees the cells the soundings will be filed under."""
@@ -166,25 +162,10 @@ class VRLayoutPlanner:
         self.device = rt.resolve_device(device)
         self._ctx = rt.get_context(self.device)
         self._counts = torch.zeros(self.base_shape, dtype=torch.int32, device=self.device)      # (uint32 bits)
-        self.offered = 0
 
-    def _add_device(self, x, y, z):
-        n = int(x.shape[0])
-        x, y, z = _on_device(x, y, z, self.device)
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_vr_soundings_density(ctx.handle, rt.ptr(x), rt.ptr(y), rt.ptr(z), n, self.origin[0], self.origin[1],
-                                                   self.base_resolution, self.base_shape[0], self.base_shape[1], rt.ptr(self._counts)))
-        ctx.end()
-        self.offered += n
-
-    def add(self, x, y, z):
-        """Count one set of soundings.  No host wait for device tensors."""
-        _check_coordinates(x, y, z)
-        n = int(x.shape[0])
-        if self.offered + n > MAX_TOTAL:
-            raise ValueError(f"{n} soundings after {self.offered} offered before: a total above {MAX_TOTAL}")
-        _feed(x, y, z, self.device, self._add_device)
+    def _offer(self, x, y, z, n):
+        self._call("bgnn_vr_soundings_density", rt.ptr(x), rt.ptr(y), rt.ptr(z), n, self.origin[0], self.origin[1], self.base_resolution,
+                   self.base_shape[0], self.base_shape[1], rt.ptr(self._counts))
 
     def counts(self) -> torch.Tensor:
         """The soundings per base cell so far, ``[BH, BW]`` int64 on the device, base row 0 the southmost."""
@@ -206,11 +187,8 @@ class VRLayoutPlanner:
         ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
         out = torch.empty(2 * cells + 1, dtype=torch.int64, device=dev)                      # the table, total behind it
         host_ladder = np.asarray(rungs, np.int32)
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_vr_soundings_plan(ctx.handle, rt.ptr(self._counts), BH, BW, host_ladder.ctypes.data, len(rungs),
-                                                target_count, min_base_count, rt.ptr(ws), ws_bytes, rt.ptr(out),
-                                                rt.ptr(out[2 * cells:])))
-        ctx.end()
+        self._call("bgnn_vr_soundings_plan", rt.ptr(self._counts), BH, BW, host_ladder.ctypes.data, len(rungs), target_count,
+                   min_base_count, rt.ptr(ws), ws_bytes, rt.ptr(out), rt.ptr(out[2 * cells:]))
         host = out.cpu().numpy()
         total = int(host[2 * cells])
         if total > rt.VR_MAX_RECORDS:
@@ -280,12 +258,6 @@ class _VRPlanes:
                                         geotransform=self.layout.geotransform)
 
 
-def _pick(obj, name: str, allowed, what: str) -> torch.Tensor:
-    if name not in allowed:
-        raise ValueError(f"{what}={name!r}: one of {allowed} expected")
-    return getattr(obj, name)
-
-
 @dataclasses.dataclass
 class VRSoundingGrid(_VRPlanes):
     """What ``VRSoundingGridder.finalize`` leaves on the device: the planes of ``SoundingGrid`` as flat ``[total]`` tensors, one
@@ -307,7 +279,7 @@ class VRSoundingGrid(_VRPlanes):
 
     def records(self, depth: str = "mean", uncertainty: str = "std") -> torch.Tensor:
         """The ``[total, 2]`` float32 device tensor of (depth, depth_uncrt) records, 1.0e6 in both where the record is not valid."""
-        return self._records(_pick(self, depth, DEPTH_PLANES, "depth"), _pick(self, uncertainty, UNCERTAINTY_PLANES, "uncertainty"))
+        return self._records(_pick_plane(self, depth, DEPTH_PLANES, "depth"), _pick_plane(self, uncertainty, UNCERTAINTY_PLANES, "uncertainty"))
 
     def handler(self, depth: str = "mean", uncertainty: str = "std") -> VRBagHandler:
         """A ``VRBagHandler`` over ``layout.metadata()`` and the records (one copy to the host), geotransform
@@ -345,16 +317,16 @@ class RobustVRSoundingGrid(_VRPlanes):
 
     def records(self, depth: str = "median", uncertainty: str = "kept_std") -> torch.Tensor:
         """The ``[total, 2]`` float32 device tensor of (depth, depth_uncrt) records, 1.0e6 in both where the record is not valid."""
-        return self._records(_pick(self, depth, ROBUST_DEPTH_PLANES, "depth"),
-                             _pick(self, uncertainty, ROBUST_UNCERTAINTY_PLANES, "uncertainty"))
+        return self._records(_pick_plane(self, depth, ROBUST_DEPTH_PLANES, "depth"),
+                             _pick_plane(self, uncertainty, ROBUST_UNCERTAINTY_PLANES, "uncertainty"))
 
     def handler(self, depth: str = "median", uncertainty: str = "kept_std") -> VRBagHandler:
         """As ``VRSoundingGrid.handler``."""
         return self._handler(self.records(depth, uncertainty))
 
 
-class _VRGridderBase:
-    """The geometry, the ``unrefined`` counter and ``add`` of the two gridders."""
+class _VRGridderBase(_GridderBase):
+    """The geometry and the ``unrefined`` counter of the two gridders."""
 
     def _init_layout(self, layout: VRLayout, device, min_count, nodata_value):
         if not isinstance(layout, VRLayout):
@@ -362,25 +334,18 @@ class _VRGridderBase:
         if layout.total < 1:
             raise ValueError("layout: no refinement grid, nothing to file soundings under")
         self.layout = layout
-        self.min_count = int(min_count)
+        self.min_count = _check_min_count(min_count)
         self.nodata_value = float(nodata_value)
-        if self.min_count < 1:
-            raise ValueError(f"min_count {min_count}: at least 1 expected")
         self.device = layout.device if device is None else rt.resolve_device(device)
         if layout.table.device != self.device:
             raise TypeError(f"the layout is on {layout.table.device}, the gridder on {self.device}")
         self._ctx = rt.get_context(self.device)
         self._unrefined = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.offered = 0
 
     def _cloud_args(self, x, y, z):
         lay = self.layout
-        return (self._ctx.handle, rt.ptr(x), rt.ptr(y), rt.ptr(z), int(x.shape[0]), lay.origin[0], lay.origin[1], lay.base_resolution,
-                lay.base_shape[0], lay.base_shape[1], rt.ptr(lay.table), lay.total)
-
-    def _counters(self, header: torch.Tensor) -> Dict[str, int]:
-        head = torch.cat([header, self._unrefined]).cpu().numpy()
-        return {name: int(v) for name, v in zip(rt.VR_SOUNDINGS_COUNTERS, head)}
+        return (rt.ptr(x), rt.ptr(y), rt.ptr(z), int(x.shape[0]), lay.origin[0], lay.origin[1], lay.base_resolution, lay.base_shape[0],
+                lay.base_shape[1], rt.ptr(lay.table), lay.total)
 
 
 class VRSoundingGridder(_VRGridderBase):
@@ -389,52 +354,19 @@ class VRSoundingGridder(_VRGridderBase):
 
     def __init__(self, layout: VRLayout, device=None, min_count: int = 1, nodata_value: float = 1.0e6):
         self._init_layout(layout, device, min_count, nodata_value)
-        nbytes = int(self._ctx.lib.bgnn_soundings_state_bytes(1, layout.total))
-        assert nbytes == layout.state_bytes
-        self._state = torch.zeros(nbytes // 8, dtype=torch.int64, device=self.device)       # an all-zero state is the empty one
+        self._state = self._buffer = _new_state(self._ctx, 1, layout.total, self.device)
+        assert self._state.numel() * 8 == layout.state_bytes
+        self._reset_call = ("bgnn_soundings_reset", rt.ptr(self._state), 1, layout.total)
 
-    def reset(self):
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_reset(ctx.handle, rt.ptr(self._state), 1, self.layout.total))
-        ctx.end()
-        self._unrefined.zero_()
-        self.offered = 0
-
-    def _add_device(self, x, y, z):
-        n = int(x.shape[0])
-        x, y, z = _on_device(x, y, z, self.device)
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_vr_soundings_add(*self._cloud_args(x, y, z), self.offered, rt.ptr(self._state), rt.ptr(self._unrefined)))
-        ctx.end()
-        self.offered += n
-
-    def add(self, x, y, z):
-        """File one set of soundings.  No host wait for device tensors."""
-        _check_coordinates(x, y, z)
-        n = int(x.shape[0])
-        if self.offered + n > MAX_TOTAL:
-            raise ValueError(f"{n} soundings after {self.offered} offered before: a total above {MAX_TOTAL}")
-        _feed(x, y, z, self.device, self._add_device)
-
-    def counters(self) -> Dict[str, int]:
-        """``accepted``, ``nonfinite``, ``outside``, ``out_of_range``, ``unrefined`` over everything added: one small copy."""
-        return self._counters(self._state[:rt.SOUNDINGS_HEADER_BYTES // 8])
+    def _offer(self, x, y, z, n):
+        self._call("bgnn_vr_soundings_add", *self._cloud_args(x, y, z), self.offered, rt.ptr(self._state), rt.ptr(self._unrefined))
 
     def finalize(self) -> VRSoundingGrid:
         """The planes of everything added so far (``bgnn_soundings_finalize`` on a ``1 x total`` grid).  Reads the state only."""
-        ctx, dev, total = self._ctx, self.device, self.layout.total
-        f32 = lambda: torch.empty(total, dtype=torch.float32, device=dev)
-        count = torch.empty(total, dtype=torch.int32, device=dev)
-        valid = torch.empty(total, dtype=torch.uint8, device=dev)
-        mean, std, zmin, zmax = f32(), f32(), f32(), f32()
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_finalize(ctx.handle, rt.ptr(self._state), 1, total, self.min_count, self.nodata_value,
-                                                 rt.ptr(count), rt.ptr(mean), rt.ptr(std), rt.ptr(zmin), rt.ptr(zmax), rt.ptr(valid)))
-        ctx.end()
-        return VRSoundingGrid(count=count, mean=mean, std=std, min=zmin, max=zmax, valid=valid, counters=self.counters(),
-                              layout=self.layout, nodata_value=self.nodata_value, min_count=self.min_count)
+        total = self.layout.total
+        planes = _finalize_plain(self._ctx, self._state, 1, total, total, self.min_count, self.nodata_value)
+        return VRSoundingGrid(**planes, counters=self.counters(), layout=self.layout, nodata_value=self.nodata_value,
+                              min_count=self.min_count)
 
 
 class RobustVRSoundingGridder(_VRGridderBase):
@@ -443,75 +375,23 @@ class RobustVRSoundingGridder(_VRGridderBase):
 
     def __init__(self, layout: VRLayout, capacity, device=None, k: float = DEFAULT_K, floor_m: float = 0.0, min_count: int = 1,
                  nodata_value: float = 1.0e6):
-        self.capacity = int(capacity)
-        self.k, self.floor_m = float(k), float(floor_m)
-        if not 1 <= self.capacity <= rt.ROBUST_MAX_CAPACITY:
-            raise ValueError(f"capacity {capacity}: 1 .. {rt.ROBUST_MAX_CAPACITY} soundings expected")
-        if not (math.isfinite(self.k) and self.k >= 1):
-            raise ValueError(f"k {k!r}: a finite number of at least 1 expected")
-        if not (math.isfinite(self.floor_m) and self.floor_m >= 0):
-            raise ValueError(f"floor_m {floor_m!r}: a finite number of at least 0 expected")
+        self.capacity, self.k, self.floor_m = _check_robust_rule(capacity, k, floor_m)
         self._init_layout(layout, device, min_count, nodata_value)
-        nbytes = int(self._ctx.lib.bgnn_soundings_robust_stage_bytes(self.capacity))
-        assert nbytes == rt.ROBUST_STAGE_HEADER_BYTES + rt.ROBUST_SLOT_BYTES * self.capacity
-        self._stage = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
-        self._stage[:rt.ROBUST_STAGE_HEADER_BYTES // 8].zero_()                             # an all-zero header is the empty stage
+        self._stage = self._buffer = _new_stage(self._ctx, self.capacity, self.device)
+        self._reset_call = ("bgnn_soundings_robust_reset", rt.ptr(self._stage))
 
-    def reset(self):
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_robust_reset(ctx.handle, rt.ptr(self._stage)))
-        ctx.end()
-        self._unrefined.zero_()
-        self.offered = 0
-
-    def _add_device(self, x, y, z):
-        n = int(x.shape[0])
-        x, y, z = _on_device(x, y, z, self.device)
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_vr_soundings_stage(*self._cloud_args(x, y, z), self.offered, self.capacity, rt.ptr(self._stage),
-                                                 rt.ptr(self._unrefined)))
-        ctx.end()
-        self.offered += n
-
-    def add(self, x, y, z):
-        """Stage one set of soundings.  No host wait for device tensors."""
-        _check_coordinates(x, y, z)
-        n = int(x.shape[0])
-        if self.offered + n > self.capacity:
-            raise ValueError(f"{n} soundings after {self.offered} offered before: more than the capacity of {self.capacity}")
-        _feed(x, y, z, self.device, self._add_device)
-
-    def counters(self) -> Dict[str, int]:
-        """``accepted``, ``nonfinite``, ``outside``, ``out_of_range``, ``unrefined`` over everything added: one small copy."""
-        return self._counters(self._stage[:rt.ROBUST_STAGE_HEADER_BYTES // 8])
+    def _offer(self, x, y, z, n):
+        self._call("bgnn_vr_soundings_stage", *self._cloud_args(x, y, z), self.offered, self.capacity, rt.ptr(self._stage),
+                   rt.ptr(self._unrefined))
 
     def finalize(self) -> RobustVRSoundingGrid:
         """The planes and the per-record sounding lists of everything added so far (``bgnn_soundings_robust_finalize`` on a
         ``1 x total`` grid).  Reads the stage only."""
-        ctx, dev, total = self._ctx, self.device, self.layout.total
-        ws_bytes = int(ctx.lib.bgnn_soundings_robust_workspace_bytes(1, total, self.capacity))
-        if ws_bytes == 0:
-            raise ValueError(f"{total} records, capacity {self.capacity}: no workspace of that size")
-        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
-        new = lambda dtype: torch.empty(total, dtype=dtype, device=dev)
-        start = torch.empty(total + 1, dtype=torch.int32, device=dev)
-        sorted_q = torch.empty(self.capacity, dtype=torch.int32, device=dev)
-        count, kept = new(torch.int32), new(torch.int32)
-        median, mad, kept_mean, kept_std, kept_min, kept_max = (new(torch.float32) for _ in range(6))
-        valid, center2, limit = new(torch.uint8), new(torch.int64), new(torch.int64)
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_soundings_robust_finalize(
-            ctx.handle, rt.ptr(self._stage), self.offered, self.capacity, 1, total, self.k, self.floor_m, self.min_count,
-            self.nodata_value, rt.ptr(ws), ws_bytes, rt.ptr(start), rt.ptr(sorted_q), rt.ptr(count), rt.ptr(kept), rt.ptr(median),
-            rt.ptr(mad), rt.ptr(kept_mean), rt.ptr(kept_std), rt.ptr(kept_min), rt.ptr(kept_max), rt.ptr(valid), rt.ptr(center2),
-            rt.ptr(limit)))
-        ctx.end()                                                                            # (the workspace may go: the caller's stream waits)
-        return RobustVRSoundingGrid(count=count, kept=kept, median=median, mad=mad, kept_mean=kept_mean, kept_std=kept_std,
-                                    kept_min=kept_min, kept_max=kept_max, valid=valid, center2=center2, limit=limit,
-                                    sorted_q=sorted_q, start=start, counters=self.counters(), layout=self.layout,
-                                    nodata_value=self.nodata_value, min_count=self.min_count, k=self.k, floor_m=self.floor_m)
+        total = self.layout.total
+        out = _finalize_robust(self._ctx, self._stage, self.offered, self.capacity, 1, total, total, self.k, self.floor_m, self.min_count,
+                               self.nodata_value)
+        return RobustVRSoundingGrid(**out, counters=self.counters(), layout=self.layout, nodata_value=self.nodata_value,
+                                    min_count=self.min_count, k=self.k, floor_m=self.floor_m)
 
     def flag(self, x, y, z, grid: RobustVRSoundingGrid) -> torch.Tensor:
         """One uint8 per sounding under the rule of ``grid`` (a ``finalize`` on this gridder's layout): 0 kept, 1 accepted but
@@ -524,8 +404,5 @@ class RobustVRSoundingGridder(_VRGridderBase):
             raise ValueError("flag: the grid is not one of this gridder's layout")
         x, y, z = _on_device(x, y, z, self.device)
         flags = torch.empty(int(x.shape[0]), dtype=torch.uint8, device=self.device)
-        ctx = self._ctx
-        ctx.begin()
-        rt.check(ctx.lib.bgnn_vr_soundings_flag(*self._cloud_args(x, y, z), rt.ptr(grid.center2), rt.ptr(grid.limit), rt.ptr(flags)))
-        ctx.end()
+        self._call("bgnn_vr_soundings_flag", *self._cloud_args(x, y, z), rt.ptr(grid.center2), rt.ptr(grid.limit), rt.ptr(flags))
         return flags

@@ -2,12 +2,12 @@
 restatements of _soundings_cpu.py, _robust_cpu.py and _vr_soundings_cpu.py, for equal bits.  The other sounding suites are careful
 about values and make one trip through every grid-stride loop; here the sizes are chosen so that each loop makes a second trip:
 
-  * one cloud of N = 2048 * 1024 + 3 * 1024 + 37 soundings in one call: workgroups 0 .. 3 of soundings_add, robust_add, robust_flag,
-    vr_density, vr_add, vr_stage and vr_flag take two tiles (workgroup 3 a ragged one of 37), the other 2044 take one;
+  * one cloud of N = 2048 * 1024 + 3 * 1024 + 37 soundings in one call: workgroups 0 .. 3 of the six
+    instantiations of sounding_pass (sounding_pass.h) and of vr_stage take two tiles (workgroup 3 a ragged one of 37), the other 2044 take one;
     robust_count and robust_scatter (256 slots a trip, 2048 workgroups) make five trips in workgroups 0 .. 12 and four in the rest;
   * its 2528 cells of more than 64 soundings: the 1024 walkers of robust_sort_long / robust_stats_long take two segments each and
     walkers 0 .. 479 a third, the radix class and the bitonic class in arrival order;
-  * a dense grid of 1100 x 1000 cells: 269 scan tiles with non-zero counts, so robust_scan_sums carries over its first 256;
+  * a dense grid of 1100 x 1000 cells: 269 scan tiles with non-zero counts, so scan_tile_sums carries over its first 256;
   * a three-call split whose first call is itself past one grid, so ``offered`` > 0 sits behind a strided call.
 
 The restatement of the large cloud walks every sounding as a Python integer (seconds); it is computed once per module."""
@@ -29,7 +29,7 @@ MAX_GRID = 2048                # PLANE_MAX_GRID (plane_util.h): the grid cap of 
 SLOT_TRIP = 256                # RB_THREADS: slots per workgroup and trip of robust_count and robust_scatter
 LONG_GRID = 1024               # RB_LONG_GRID: the workgroups that walk the list of long segments
 SCAN_TILE = 4096               # RB_SCAN_TILE: cells per tile of robust_tile_sums / robust_scan_cells
-SCAN_SUMS_STEP = 256           # RB_THREADS: tiles per step of robust_scan_sums
+SCAN_SUMS_STEP = 256           # RB_THREADS: tiles per step of scan_tile_sums
 WAVE_MAX, LDS_MAX = 64, 4096   # BGNN_ROBUST_WAVE_MAX, BGNN_ROBUST_LDS_MAX (checked against the runtime's below)
 
 N = MAX_GRID * TILE + 3 * TILE + 37
@@ -205,8 +205,8 @@ def _robust_run(device, x, y, z, cuts=(0, N)):
 
 @pytest.mark.parametrize("layout", ["swath", "permuted"])
 def test_first_gridder_past_one_grid(layout, gpu_device):
-    """soundings_add: 2051 tiles and the ragged 37 over 2048 workgroups, in one call; swath order is where file_sounding merges
-    runs across the boundaries."""
+    """sounding_pass<UniformAddress, FileSink>: 2051 tiles and the ragged 37 over 2048 workgroups, in one call; swath order is
+    where file_sounding merges runs across the boundaries."""
     want = _want_plain()
     _want_robust()                                                               # (the conditions of the cloud)
     grid = _plain_run(gpu_device, *_layout_of(layout))
@@ -215,8 +215,8 @@ def test_first_gridder_past_one_grid(layout, gpu_device):
 
 
 def test_robust_gridder_past_one_grid(gpu_device):
-    """robust_add, robust_count, robust_scatter and robust_flag past one grid; 2528 listed cells over 1024 list walkers.  Swath
-    order against rc.grid, the permuted cloud against it and against the swath run."""
+    """sounding_pass with StageSink and FlagSink, robust_count and robust_scatter past one grid; 2528 listed cells over 1024 list
+    walkers.  Swath order against rc.grid, the permuted cloud against it and against the swath run."""
     want = _want_robust()
     grid, flags = _robust_run(gpu_device, *_layout_of("swath"))
     a = _check_robust(grid, want, SHAPE)
@@ -266,7 +266,7 @@ DENSE_SHAPE, DENSE_N = (1100, 1000), 2200000
 
 def test_dense_grid_past_256_scan_tiles(gpu_device):
     """2.2 x 10^6 soundings spread over 1 100 000 cells (0 to about 12 a cell: the short class only): 269 scan tiles, every one
-    with counts, 13 of them behind the first step of robust_scan_sums.  ``count``, all of ``start`` and ``sorted_q`` against
+    with counts, 13 of them behind the first step of scan_tile_sums.  ``count``, all of ``start`` and ``sorted_q`` against
     bincount, cumsum and lexsort; the other planes against rc's rule on the cells around every tile border and every 53rd."""
     from bathymetric_gnn_amd.data import RobustSoundingGridder, SoundingGridder
     (H, W), (x0, y0), res = DENSE_SHAPE, ORIGIN, 0.5
@@ -347,8 +347,8 @@ def _device_layout(device, lay):
 
 
 def test_vr_density_and_plan_past_one_grid(gpu_device):
-    """vr_density over the cloud in one call: the counts of the planner and the layout of ``plan_vr_layout`` against the
-    restatement's density and plan."""
+    """sounding_pass<VRBaseAddress, DensitySink> over the cloud in one call: the counts of the planner and the layout of
+    ``plan_vr_layout`` against the restatement's density and plan."""
     from bathymetric_gnn_amd.data import VRLayoutPlanner, plan_vr_layout
     x, y, z = _layout_of("permuted")
     counts = vc.density(x, y, z, VR_ORIGIN, VR_B, VR_BASE)
@@ -368,7 +368,8 @@ def test_vr_density_and_plan_past_one_grid(gpu_device):
 
 @pytest.mark.parametrize("layout", ["swath", "permuted"])
 def test_vr_gridder_past_one_grid(layout, gpu_device):
-    """vr_add over the cloud in one call on the mixed layout: every plane and the five counters against the restatement."""
+    """sounding_pass<VRAddress, FileSink> over the cloud in one call on the mixed layout: every plane and the five counters against
+    the restatement."""
     from bathymetric_gnn_amd.data import VRSoundingGridder
     lay = _vr_layout()
     x, y, z = _layout_of(layout)
@@ -382,7 +383,8 @@ def test_vr_gridder_past_one_grid(layout, gpu_device):
 
 
 def test_robust_vr_gridder_past_one_grid(gpu_device):
-    """vr_stage, finalize and vr_flag over the cloud in one call on the mixed layout, against the restatement directly."""
+    """vr_stage, finalize and sounding_pass<VRAddress, FlagSink> over the cloud in one call on the mixed
+    layout, against the restatement directly."""
     from bathymetric_gnn_amd.data import RobustVRSoundingGridder
     lay = _vr_layout()
     x, y, z = _layout_of("permuted")
