@@ -1,5 +1,5 @@
 """Mirror of the reference's ``data`` package for the hot path: graph construction, tiling, synthetic training
-noise, ground truth from a clean / noisy survey pair, feature labels from charted objects and from the slope, low-confidence regions for review, gridding a point cloud of soundings (streaming sums, the robust gridder: per-cell median, MAD and flags, and both at variable resolution: straight into the refinement records of a VR layout) and the ``BathymetricGrid`` container (file-format I/O -- GDAL / h5py -- is outside the path; VR BAGs enter as their two HDF5 arrays)."""
+noise, ground truth from a clean / noisy survey pair, feature labels from charted objects and from the slope, low-confidence regions for review, gridding a point cloud of soundings (streaming sums, the robust gridder: per-cell median, MAD and flags, and both at variable resolution: straight into the refinement records of a VR layout; depth hypotheses per cell from the robust gridders' sorted lists) and the ``BathymetricGrid`` container (file-format I/O -- GDAL / h5py -- is outside the path; VR BAGs enter as their two HDF5 arrays)."""
 from .graph_construction import GraphBuilder, GraphData, Data
 from .grid import BathymetricGrid
 from .tiling import Tile, TileSpec, TileManager, TileMerger
@@ -16,6 +16,7 @@ from .sounding_grid import SoundingGrid, SoundingGridder, grid_soundings, plan_s
 from .sounding_robust import RobustSoundingGrid, RobustSoundingGridder, grid_soundings_robust
 from .sounding_vr import (RobustVRSoundingGrid, RobustVRSoundingGridder, VRLayout, VRLayoutPlanner, VRSoundingGrid, VRSoundingGridder,
                           plan_vr_base_grid, plan_vr_layout)
+from .sounding_hypotheses import HypothesisGrid, VRHypothesisGrid
 
 __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "TileSpec", "TileManager", "TileMerger",
            "RefinementGrid", "VRBagHandler", "VRBagWriter", "SRBagHandler", "SRBagWriter", "SidecarBuilder", "detect_bag_type",
@@ -29,4 +30,4 @@ __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "Tile
            "SoundingGrid", "SoundingGridder", "grid_soundings", "plan_sounding_grid", "sounding_extent",
            "RobustSoundingGrid", "RobustSoundingGridder", "grid_soundings_robust",
            "VRLayout", "VRLayoutPlanner", "VRSoundingGrid", "VRSoundingGridder", "RobustVRSoundingGrid", "RobustVRSoundingGridder",
-           "plan_vr_base_grid", "plan_vr_layout"]
+           "plan_vr_base_grid", "plan_vr_layout", "HypothesisGrid", "VRHypothesisGrid"]

@@ -311,6 +311,12 @@ class RobustVRSoundingGrid(_VRPlanes):
     k: float = DEFAULT_K
     floor_m: float = 0.0
 
+    def hypotheses(self, gap_m, rule: str = "count", guide=None, min_count=None, records: bool = True):
+        """As ``RobustSoundingGrid.hypotheses``, per record of ``layout`` (``guide``: a flat ``[total]`` tensor): a
+        ``VRHypothesisGrid``."""
+        from .sounding_hypotheses import hypotheses_of_records
+        return hypotheses_of_records(self, gap_m, rule, guide, min_count, records)
+
     def density_plane(self) -> torch.Tensor:
         """``density_from_count(kept)``, one entry per record of ``layout``."""
         return density_from_count(self.kept)
