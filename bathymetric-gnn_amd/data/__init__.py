@@ -17,6 +17,7 @@ from .sounding_robust import RobustSoundingGrid, RobustSoundingGridder, grid_sou
 from .sounding_vr import (RobustVRSoundingGrid, RobustVRSoundingGridder, VRLayout, VRLayoutPlanner, VRSoundingGrid, VRSoundingGridder,
                           plan_vr_base_grid, plan_vr_layout)
 from .sounding_hypotheses import HypothesisGrid, VRHypothesisGrid
+from .locale_guide import guide_from_coarser, locale_guide, locale_guide_planes
 
 __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "TileSpec", "TileManager", "TileMerger",
            "RefinementGrid", "VRBagHandler", "VRBagWriter", "SRBagHandler", "SRBagWriter", "SidecarBuilder", "detect_bag_type",
@@ -30,4 +31,5 @@ __all__ = ["GraphBuilder", "GraphData", "Data", "BathymetricGrid", "Tile", "Tile
            "SoundingGrid", "SoundingGridder", "grid_soundings", "plan_sounding_grid", "sounding_extent",
            "RobustSoundingGrid", "RobustSoundingGridder", "grid_soundings_robust",
            "VRLayout", "VRLayoutPlanner", "VRSoundingGrid", "VRSoundingGridder", "RobustVRSoundingGrid", "RobustVRSoundingGridder",
-           "plan_vr_base_grid", "plan_vr_layout", "HypothesisGrid", "VRHypothesisGrid"]
+           "plan_vr_base_grid", "plan_vr_layout", "HypothesisGrid", "VRHypothesisGrid",
+           "guide_from_coarser", "locale_guide", "locale_guide_planes"]

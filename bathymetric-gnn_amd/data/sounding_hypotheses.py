@@ -7,7 +7,9 @@ into runs without a gap of more than ``gap_m`` -- one run, one depth hypothesis 
 (include/bgnn_hypotheses.h): under ``rule="count"`` the run with the most soundings, then the one nearest to the cell's median;
 under ``rule="guide"`` the run nearest to a guide surface, then the one with the most soundings.  A guide is any float32 plane of
 the result's shape; the usual one is the ``median`` of a coarser robust gridding of the same cloud, ``repeat_interleave``d to
-this resolution.  Cells whose guide is not finite or out of range fall back to the count rule.
+this resolution (``guide_from_coarser``).  Cells whose guide is not finite or out of range fall back to the count rule.
+``rule="locale"`` (uniform grids only, data/locale_guide.py) makes the guide itself: per cell the median of the neighbouring
+cells that have exactly one hypothesis.
 
 Everything is an integer function of the sorted lists: equal bits in any order of the cloud, in any split over ``add`` calls, on
 every run.  ``center2`` / ``limit`` follow the robust planes' convention (``|2q - center2| <= limit`` iff the sounding lies inside
@@ -15,7 +17,8 @@ the chosen run), so ``RobustSoundingGridder.flag`` and ``RobustVRSoundingGridder
 point cloud is cleaned by hypothesis without another pass.
 
 Out of scope: CUBE's sequential Kalman estimator (it depends on the order of arrival), spreading a sounding over neighbouring
-nodes, a helper that makes the guide, ``ambiguity`` as a node plane of the model, and the streamed and sharded routes."""
+nodes, iterating the locale rule so that resolved cells become witnesses, the locale rule on variable-resolution layouts,
+``ambiguity`` as a node plane of the model, and the streamed and sharded routes."""
 from __future__ import annotations
 
 import dataclasses
@@ -146,7 +149,8 @@ class HypothesisGrid(_HypothesisPlanes):
     ``limit`` (int64: the rule ``flag`` applies, ``limit == -1`` where none is chosen); the float planes hold ``nodata_value``
     where not valid.  The records, or ``None``: the hypotheses of cell ``c`` are entries ``hyp_start[c] .. hyp_start[c + 1]`` of
     ``hyp_first`` (the index into ``sorted_q`` of each one's first sounding) and ``hyp_count`` (uint32 bits in int32 tensors, as
-    ``start``).  ``sorted_q`` and ``start`` are those of the robust result, by reference."""
+    ``start``).  ``sorted_q`` and ``start`` are those of the robust result, by reference.  ``guide`` and ``support``: ``None`` but
+    under ``rule="locale"``, where they are the ``[H, W]`` planes of ``data.locale_guide`` the result was chosen by."""
     n_hyp: torch.Tensor
     chosen: torch.Tensor
     kept: torch.Tensor
@@ -169,6 +173,8 @@ class HypothesisGrid(_HypothesisPlanes):
     resolution: Tuple[float, float]
     nodata_value: float = 1.0e6
     min_count: int = 1
+    guide: Optional[torch.Tensor] = None               # rule="locale": the float32 guide the result was built with (NaN: by count)
+    support: Optional[torch.Tensor] = None             # rule="locale": int32, the witnesses in each cell's window
 
     def hypotheses_of(self, row: int, col: int) -> List[Dict[str, object]]:
         """The hypotheses of one cell in ascending depth, a host list of dicts: ``first`` (index into ``sorted_q``), ``count``,
@@ -238,13 +244,23 @@ class VRHypothesisGrid(_HypothesisPlanes, _VRPlanes):
         return self._handler(self.records(depth, uncertainty))
 
 
-def hypotheses_of_grid(robust, gap_m, rule="count", guide=None, min_count=None, records=True) -> HypothesisGrid:
+def hypotheses_of_grid(robust, gap_m, rule="count", guide=None, min_count=None, records=True, radius=None,
+                       min_support=None) -> HypothesisGrid:
     """``RobustSoundingGrid.hypotheses``."""
+    if rule == "locale":
+        if guide is not None:
+            raise ValueError('rule="locale" makes its own guide: it takes none')
+        from .locale_guide import hypotheses_by_locale
+        return hypotheses_by_locale(robust, gap_m, radius, min_support, min_count, records)
+    if radius is not None or min_support is not None:
+        raise ValueError(f'radius and min_support go with rule="locale", not with rule={rule!r}')
     out = build_hypotheses(robust, gap_m, rule, guide, min_count, records)
     return HypothesisGrid(**out, transform=robust.transform, resolution=robust.resolution)
 
 
 def hypotheses_of_records(robust, gap_m, rule="count", guide=None, min_count=None, records=True) -> VRHypothesisGrid:
     """``RobustVRSoundingGrid.hypotheses``."""
+    if rule == "locale":
+        raise ValueError('rule="locale" is for uniform grids: the neighbours of a record across refinement grids are not defined')
     out = build_hypotheses(robust, gap_m, rule, guide, min_count, records)
     return VRHypothesisGrid(**out, layout=robust.layout)

@@ -72,14 +72,17 @@ class RobustSoundingGrid:
         lo, hi = (int(v) & 0xFFFFFFFF for v in self.start[cell:cell + 2].tolist())
         return self.sorted_q[lo:hi].to(torch.float64) * (2.0 ** -16)
 
-    def hypotheses(self, gap_m, rule: str = "count", guide=None, min_count=None, records: bool = True):
+    def hypotheses(self, gap_m, rule: str = "count", guide=None, min_count=None, records: bool = True, radius=None, min_support=None):
         """The depth hypotheses of every cell (data/sounding_hypotheses.py): the runs of its sorted soundings without a gap of
         more than ``gap_m`` metres (required, finite, 0 .. 65536: what separates two surfaces is the survey's to say), and one
         chosen per cell -- ``rule="count"``: the most soundings, then the nearest to the cell's median; ``rule="guide"``: the
-        nearest to ``guide`` (a float32 device tensor ``[H, W]``), then the most soundings.  ``min_count`` defaults to this
-        grid's; ``records=False`` leaves the per-hypothesis records out.  A ``HypothesisGrid``."""
+        nearest to ``guide`` (a float32 device tensor ``[H, W]``), then the most soundings; ``rule="locale"``
+        (data/locale_guide.py): by a guide made here, the median of the cells within ``radius`` (default 2, 1 .. 8) that have
+        one hypothesis only, by count where fewer than ``min_support`` (default 3) of them are found; the result carries that
+        ``guide`` and its ``support``.  ``radius`` and ``min_support`` go with ``rule="locale"`` alone, which takes no ``guide``.
+        ``min_count`` defaults to this grid's; ``records=False`` leaves the per-hypothesis records out.  A ``HypothesisGrid``."""
         from .sounding_hypotheses import hypotheses_of_grid
-        return hypotheses_of_grid(self, gap_m, rule, guide, min_count, records)
+        return hypotheses_of_grid(self, gap_m, rule, guide, min_count, records, radius, min_support)
 
     def density_plane(self) -> torch.Tensor:
         """``density_from_count(kept)``: the node plane "sounding_density" over the soundings the rule kept."""

@@ -313,7 +313,7 @@ class RobustVRSoundingGrid(_VRPlanes):
 
     def hypotheses(self, gap_m, rule: str = "count", guide=None, min_count=None, records: bool = True):
         """As ``RobustSoundingGrid.hypotheses``, per record of ``layout`` (``guide``: a flat ``[total]`` tensor): a
-        ``VRHypothesisGrid``."""
+        ``VRHypothesisGrid``.  ``rule="locale"`` is for uniform grids: ``ValueError`` here."""
         from .sounding_hypotheses import hypotheses_of_records
         return hypotheses_of_records(self, gap_m, rule, guide, min_count, records)
 

@@ -461,6 +461,13 @@ HYP_MAX_CELLS = 2 ** 31 - 1                        # BGNN_HYP_MAX_CELLS
 HYP_MAX_CAPACITY = 2 ** 31 - 1                     # BGNN_HYP_MAX_CAPACITY
 HYP_MAX_GAP_Q = 2 ** 32                            # BGNN_HYP_MAX_GAP_Q
 
+# symbol -> (restype, argtypes); every symbol include/bgnn_locale.h declares (the locale rule: a guide from single-hypothesis neighbours)
+_LOCALE_SIGNATURES = {
+    "bgnn_locale_guide": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] * 2 + [C.c_int32] * 2 + [C.c_void_p] * 2),
+}
+LOCALE_MAX_RADIUS = 8                              # BGNN_LOCALE_MAX_RADIUS
+LOCALE_MAX_CELLS = 2 ** 31 - 1                     # height * width of bgnn_locale_guide
+
 # symbol -> (restype, argtypes); every symbol include/bgnn_aux.h declares (auxiliary node-feature planes: sounding density)
 _AUX_SIGNATURES = {
     "bgnn_graph_build_aux": (C.c_int, [C.c_void_p, C.POINTER(Tiles), C.POINTER(GraphOpts), C.c_int32, C.POINTER(C.c_void_p),
@@ -510,7 +517,8 @@ def load_library(path: Optional[str] = None):
     include/bgnn_noise.h, include/bgnn_loss.h, include/bgnn_optim.h, include/bgnn_trainer.h, include/bgnn_eval.h, include/bgnn_analysis.h,
     include/bgnn_features.h, include/bgnn_tilestore.h, include/bgnn_review.h, include/bgnn_slope.h, include/bgnn_vrtruth.h,
     include/bgnn_augment.h, include/bgnn_curve.h, include/bgnn_soundings.h, include/bgnn_soundings_robust.h,
-    include/bgnn_soundings_vr.h, include/bgnn_hypotheses.h, include/bgnn_aux.h and include/bgnn_quantile.h.  Needs no GPU."""
+    include/bgnn_soundings_vr.h, include/bgnn_hypotheses.h, include/bgnn_locale.h, include/bgnn_aux.h and include/bgnn_quantile.h.
+    Needs no GPU."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -527,7 +535,8 @@ def load_library(path: Optional[str] = None):
                 list(_TILESTORE_SIGNATURES.items()) + list(_REVIEW_SIGNATURES.items()) + list(_SLOPE_SIGNATURES.items()) + \
                 list(_VRTRUTH_SIGNATURES.items()) + list(_AUGMENT_SIGNATURES.items()) + list(_CURVE_SIGNATURES.items()) + \
                 list(_SOUNDINGS_SIGNATURES.items()) + list(_ROBUST_SIGNATURES.items()) + list(_VR_SOUNDINGS_SIGNATURES.items()) + \
-                list(_HYPOTHESES_SIGNATURES.items()) + list(_AUX_SIGNATURES.items()) + list(_QUANTILE_SIGNATURES.items()):
+                list(_HYPOTHESES_SIGNATURES.items()) + list(_LOCALE_SIGNATURES.items()) + list(_AUX_SIGNATURES.items()) + \
+                list(_QUANTILE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
