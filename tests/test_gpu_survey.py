@@ -113,6 +113,48 @@ def test_streamed_host_survey_equals_the_resident_one(in_channels, band, foreign
     assert all(np.array_equal(res2[k].view(np.uint32), res[k].view(np.uint32)) for k in res)
 
 
+def test_streamed_equals_resident_at_the_corners_of_the_shared_loop(gpu_device):
+    """Where a classify / stitch loop shared by both routes can go wrong: a survey smaller than one tile (one 40 x 50 tile, a ring of
+    one slot), and a 200 x 170 survey whose first 70 rows are nodata, so that the whole first tile row is skipped and the first band
+    classifies nothing -- each with bands of 1 and of 5 tile rows (more than there are).  Streamed == resident bit for bit, with
+    equal tile counts; on 200 x 170 both also equal the host merge of per-tile results, the independent reference."""
+    from bathymetric_gnn_amd import synthetic
+    from bathymetric_gnn_amd.config import Config
+    from bathymetric_gnn_amd.data import BathymetricGrid
+    from bathymetric_gnn_amd.models import BathymetricGNN, BathymetricPipeline
+    cfg = Config(); cfg.tile.tile_size, cfg.tile.overlap = 64, 16          # stride 48
+    pipe = BathymetricPipeline(cfg, tile_batch=3)
+    sd = synthetic.synthetic_state_dict(seed=1234)
+    m = BathymetricGNN(in_channels=7, edge_dim=3, dropout=0.0); m.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
+    pipe.set_model(m.to(gpu_device).eval())
+    names = ("classification", "confidence", "correction", "cleaned_depth")
+    for (H, W), counts in (((40, 50), (1, 0)), ((200, 170), (12, 4))):
+        d, _, _ = synthetic.synthetic_tile(H, W, 7, "V1")
+        if H == 200:
+            d[:70] = 1.0e6
+        else:
+            d[3:9, 10:20] = 1.0e6
+        grid = BathymetricGrid(depth=d, nodata_value=1.0e6, resolution=(0.5, 0.5))
+        valid_np = grid.valid_mask
+        full = pipe.process_survey_device(torch.from_numpy(d).to(gpu_device), torch.from_numpy(valid_np).to(gpu_device), None,
+                                          (0.5, 0.5)).cpu().numpy()
+        assert pipe.last_tile_counts == counts
+        for band in (1, 5):
+            res = pipe.process_grid_streamed(grid, band_tile_rows=band)
+            assert pipe.last_tile_counts == counts, (H, W, band)
+            for k, name in enumerate(names):
+                assert res[name].shape == d.shape and np.array_equal(res[name].view(np.uint32), full[k].view(np.uint32)), (H, W, band, name)
+            assert np.array_equal(res["valid_mask"], valid_np.astype(np.float32)), (H, W, band)
+        if H == 200:
+            assert np.isnan(full[0][:48]).all() and not np.isnan(full[0][70:]).any()      # rows only the skipped tile row covers
+            pipe.host_stitch = True
+            host = pipe.process_grid(grid)
+            pipe.host_stitch = False
+            for k, name in enumerate(names):
+                assert np.array_equal(np.isnan(full[k]), np.isnan(host[name])), name
+                assert np.array_equal(np.nan_to_num(full[k]).view(np.uint32), np.nan_to_num(host[name]).view(np.uint32)), name
+
+
 @pytest.mark.parametrize("S", [60000, 20000])
 def test_config5_full_size_survey_resident_in_hbm(gpu_device, S):
     """BASELINE config 5 at FULL size on one GPU (models/pipeline.py:170-190 is the loop it stands for): a 60000 x 60000
